@@ -7,9 +7,23 @@ warm start -> corrector) on the configs[1] workload of BASELINE.json: the 69^3-h
 
 Prints ONE JSON line (rank 0). value = PCG DOF-iterations per second over the whole job
 (sum over ranks of DOFs x PCG iterations / max-over-ranks wall time of the K timed steps).
-Extra fields: pcg_iterations_per_sec, dof_updates_per_sec (D x steps/s), the live roofline of the
-dominant kernel (K_eff, timed with hipEvents on the handle's stream inside the timed steps) and a
-bounded single-thread CPU baseline (the oracle restatement of the reference's solve_pcg).
+Extra fields: ms_per_step, pcg_iterations_per_sec, dof_updates_per_sec (D x steps/s) and the live
+roofline of the dominant kernel (K_eff, timed with hipEvents on the handle's stream inside the timed
+steps). A plain run does nothing else: it sets up, warms up, times the K steps and prints the line.
+The trajectory starts again from rest every RESTART_PERIOD steps (warm-up included), because the state
+of these configs grows by about 2.5x per step and would leave fp32 after about 90; runs of up to
+RESTART_PERIOD steps in all, the default among them, never restart.
+
+--dump-outputs DIR writes what the last timed step left a caller of Stepper to read, after the timed
+region: DIR/displacement.npy, velocity.npy and acceleration.npy (float32 [3N], the stepper's state through
+Stepper.get_state). Above 64 MB in all, the same fixed, seeded sample of DOFs of each (dump_sample, the
+same in every run). Ranks other than 0 write <name>_rank<r>.npy. The workload is
+generated from the arguments alone, so the same arguments give the same inputs in every run.
+
+--full adds, after the timed region and never inside it, the runs of their own: the measured copy
+ceiling, the live C3 rooflines (roofline_hbm, roofline_general), the `general` and `parity` comparators on
+the same workload and a bounded single-thread CPU baseline (the oracle restatement of the reference's
+solve_pcg); the --no-* options drop single ones of them. Without --full those fields are null.
 
 Multi-GPU (python -m torch.distributed.run ... bench.py --gpus N): weak scaling, one process per
 GPU. The global block stacks N copies of the per-GPU workload along z; rank r owns a contiguous range
@@ -32,6 +46,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, "civiwave-fem_amd"))
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md chip table (spec 8.0 TB/s)
+RESTART_PERIOD = 16  # steps after which the benchmarked trajectory starts again from rest (see main)
 
 
 def parse():
@@ -49,6 +64,14 @@ def parse():
                     help="tet4: the Kuhn expansion the reference runs (the headline); hex8: native hexes "
                          "(SURVEY 8f4, FAST only, parity unpinned)")
     ap.add_argument("--max-iterations", type=int, default=2000)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the stepper's state after the last of them (displacement, "
+                         "velocity, acceleration) as DIR/<name>.npy, float32; at most 64 MB in all (a fixed seeded "
+                         "sample of the DOFs above that)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the measurements that take runs of their own: the copy "
+                         "ceiling, the C3 rooflines, the 'general' and 'parity' comparators and the CPU baseline "
+                         "(the --no-* options below drop single ones). Off: those fields are null")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--keff-sample", type=int, default=5,
                     help="hipEvent-time every k-th K_eff launch of the timed steps (1 = all). Coprime with the lazy-x "
@@ -69,7 +92,10 @@ def parse():
                     help="skip the live configs[2] K_eff roofline (N=1 runs of configs other than c3 add it)")
     ap.add_argument("--traffic", default="auto",
                     help="PMC summary json for roofline.traffic; 'auto' = newest profiles/r*_<config>_<mode>_pmc.json")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def cpu_model() -> str:
@@ -287,6 +313,38 @@ def stream_copy_gbs(L, device, nbytes=2 << 30, reps=20):
     return g.value if L.cwf_hip_bandwidth_probe(device, nbytes, reps, C.byref(g)) == 0 else None
 
 
+DUMP_BUDGET_BYTES = 64_000_000  # --dump-outputs writes at most this much in all
+DUMP_SAMPLE_SEED = 20240607
+
+
+def dump_sample(n, k):
+    """The DOFs --dump-outputs keeps of a vector of n when it may keep only k < n: a fixed seeded choice, ascending."""
+    import numpy as np
+
+    return np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=k, replace=False))
+
+
+def dump_outputs(stepper, outdir, rank=0):
+    """The stepper's state after the last timed step (what a caller reads through Stepper.get_state) as float32
+    .npy files under `outdir`. When the three vectors together exceed DUMP_BUDGET_BYTES, the DOFs dump_sample picks,
+    the same ones of each vector and in every run."""
+    import numpy as np
+
+    os.makedirs(outdir, exist_ok=True)
+    fields = (("displacement", stepper.DISPLACEMENT), ("velocity", stepper.VELOCITY),
+              ("acceleration", stepper.ACCELERATION))
+    n = int(stepper.dof_count)
+    keep = None
+    if len(fields) * (4 * n + 128) > DUMP_BUDGET_BYTES:  # 128 B: the .npy header
+        k = DUMP_BUDGET_BYTES // (len(fields) * 4) - 64
+        keep = dump_sample(n, k)
+    suffix = f"_rank{rank}" if rank else ""
+    for name, which in fields:
+        a = stepper.get_state(which)
+        np.save(os.path.join(outdir, f"{name}{suffix}.npy"), np.ascontiguousarray(a if keep is None else a[keep],
+                                                                                  np.float32))
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -418,7 +476,24 @@ def main():
     if load_pattern is not None:  # the harmonic tip load (C4), rewritten on the device before every step
         stepper.set_load_pattern(*load_pattern)
 
+    # The state of these configs grows from step to step (the oracle's Stepper, the bit-exact restatement of the
+    # reference's, on C1: max |a| 3.4 after the first step, 3.5e3 after 11, 4.7e28 after 76, about 2.5x per step; C2
+    # on the GPU 3.7e5 after 12), so an unbroken run leaves fp32 after about 90 steps and times, and would dump,
+    # inf and NaN from there on. Every RESTART_PERIOD-th step, warm-up steps counted, therefore starts again from
+    # rest: u, v, a and the PCG warm start are zeroed on the device (four device-to-device copies on the handle's
+    # stream). Runs of up to RESTART_PERIOD steps in all, the default among them, never restart; a longer one
+    # repeats the first RESTART_PERIOD steps' work, and its state after n steps is that of a fresh run after
+    # (n - 1) % RESTART_PERIOD + 1.
+    rest = torch.zeros(stepper.dof_count, dtype=torch.float32, device=f"cuda:{device}")
+    torch.cuda.synchronize()
+    steps_done = 0
+
     def step(t):
+        nonlocal steps_done
+        if steps_done and steps_done % RESTART_PERIOD == 0:
+            for which in (stepper.DISPLACEMENT, stepper.VELOCITY, stepper.ACCELERATION, stepper.SOLUTION):
+                stepper.set_state(which, rest)
+        steps_done += 1
         if load_pattern is not None:
             stepper.set_load_scale(case.load_scale(t))
         return stepper.step(t).value()
@@ -492,29 +567,32 @@ def main():
         # only a profile of the same kernel built from the same sources counts: the newest such
         traffic, traffic_src = pmc_traffic(cands, kname, src_hash)
     result = None
+    if args.dump_outputs:
+        dump_outputs(stepper, args.dump_outputs, rank)
     stepper.close()
     stepper.system.close()
+    # everything below that takes a run of its own is --full only
     hbm = hbm_general = None
-    if (rank == 0 and world == 1 and not args.no_hbm_roofline and args.mode == "fast" and args.element == "tet4"
-            and args.config != "c3"):
+    if (args.full and rank == 0 and world == 1 and not args.no_hbm_roofline and args.mode == "fast"
+            and args.element == "tet4" and args.config != "c3"):
         hbm = hbm_roofline(L, device)
         if not args.no_general_roofline:
             hbm_general = hbm_roofline(L, device, general=True)
     general = None
-    if (rank == 0 and world == 1 and not args.no_general and args.mode == "fast" and args.element == "tet4"
-            and operator_of(kname).startswith("structured")):
+    if (args.full and rank == 0 and world == 1 and not args.no_general and args.mode == "fast"
+            and args.element == "tet4" and operator_of(kname).startswith("structured")):
         general = side_line(L, device, args.config, min(args.steps, 5))
     parity = None
-    if (rank == 0 and world == 1 and not args.no_parity and args.mode == "fast" and args.element == "tet4"
-            and args.config in ("c1", "c2")):
+    if (args.full and rank == 0 and world == 1 and not args.no_parity and args.mode == "fast"
+            and args.element == "tet4" and args.config in ("c1", "c2")):
         parity = side_line(L, device, args.config, min(args.steps, 3), mode="parity")
-    copy_gbs = stream_copy_gbs(L, device) if rank == 0 else None
+    copy_gbs = stream_copy_gbs(L, device) if args.full and rank == 0 else None
     for rl in (hbm, hbm_general):
         if rl and copy_gbs:
             rl["frac_of_measured_copy"] = rl["achieved"] / copy_gbs
     if rank == 0:
         cpu = None
-        if not args.no_cpu_baseline and world == 1 and args.element == "tet4":  # rank 0 at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1 and args.element == "tet4":  # rank 0 at N=1 only
             cpu = cpu_baseline(case, sK, sM, args.cpu_iterations)
         result = {
             "metric": "PCG DOF-iterations/sec per Newmark step (PCG-it/s x DOFs); DOF-updates/s and "
@@ -524,6 +602,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "restart_period": RESTART_PERIOD,
             "ms_per_step": 1e3 * elapsed / args.steps,
             "higher_is_better": True,
             "scaling": "strong" if (strong and world > 1) or args.scaling == "strong" else "weak",

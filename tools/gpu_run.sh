@@ -8,7 +8,8 @@
 #   tests[:FILE,FILE..[:KEXPR]]  pytest -m gpu -s over tests/ (or the listed test files; KEXPR: a -k expression,
 #                           commas for spaces; no '::' node ids, ':' splits the step)
 #   smoke                   __graft_entry__.smoke()
-#   bench:NAME[:ARGS]       one bench.py line (ARGS: bench.py arguments, commas for spaces) -> <TAG>_bench_NAME.json
+#   bench:NAME[:ARGS]       one bench.py --full line (ARGS: further bench.py arguments, commas for spaces)
+#                           -> <TAG>_bench_NAME.json
 #   ab:NAME:ENV[:ARGS]      the same bench twice per pass, in-tree default vs ENV (commas for spaces: several
 #                           VAR=VALUE), PASSES (default 2) alternating passes -> one summary line per run
 #   ablib:NAME:VARIANT[:ARGS]  the same against civiwave-fem_amd/lib_VARIANT/libcwf_hip.so
@@ -23,7 +24,7 @@
 #   peer                    the PEER communicator's tests with their exchange-latency prints (2 / 3 processes on
 #                           this GPU) -> <TAG>/peer.log
 # e.g. bash tools/gpu_run.sh r04c tests:tests/test_gpu_lattice.py bench:c2 bench:c3:--config,c3,--steps,3 \
-#        ab:c2cg:CWF_LAT_CG=0 prof:c3:--config,c3,--steps,2,--warmup,1,--no-cpu-baseline
+#        ab:c2cg:CWF_LAT_CG=0 prof:c3:--full,--config,c3,--steps,2,--warmup,1,--no-cpu-baseline
 set -o pipefail
 R="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 cd "$R"
@@ -58,7 +59,7 @@ for step in "$@"; do
       timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tail -20 $O/smoke.log; exit 1; }
       tail -1 $O/smoke.log ;;
     bench)
-      bench bench_$a "" $(sp "$b") || exit 2 ;;
+      bench bench_$a "" --full $(sp "$b") || exit 2 ;;
     ab|ablib)
       for pass in $(seq 1 ${PASSES:-2}); do
         bench ${a}_new_p$pass "" --no-cpu-baseline --no-hbm-roofline --no-general-roofline --no-general $(sp "$c") || exit 2
@@ -66,7 +67,7 @@ for step in "$@"; do
         bench ${a}_alt_p$pass "$other" --no-cpu-baseline --no-hbm-roofline --no-general-roofline --no-general $(sp "$c") || exit 2
       done ;;
     prof|sq)
-      args=$(sp "${b:---steps,3,--warmup,1,--no-cpu-baseline}")
+      args=$(sp "${b:---full,--steps,3,--warmup,1,--no-cpu-baseline}")
       if [ $kind = sq ]; then export SQ_PMC=1; fi
       bash tools/profile.sh ${TAG}_$a $args > $O/prof_$a.log 2>&1 || { tail -20 $O/prof_$a.log; exit 3; }
       K=$(grep -h '^{"metric"' gpurun_out/prof_${TAG}_$a/bench_kt.log | python3 -c "import json,sys; print(json.loads(sys.stdin.read())['roofline']['kernel'])")

@@ -4,7 +4,7 @@
 # SCRIPT=tools/spmv_bench.py profiles that script instead of bench.py (args likewise).
 R="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 TAG=${1:-run}; shift
-ARGS=${@:-"--steps 3 --warmup 1 --no-cpu-baseline"}
+ARGS=${@:-"--full --steps 3 --warmup 1 --no-cpu-baseline"}
 SCRIPT=$R/${SCRIPT:-bench.py}
 cd /tmp && export TMPDIR=/tmp
 OUT=$R/gpurun_out/prof_$TAG

@@ -3,7 +3,7 @@
 # their cycles. Usage: tools/sq_profile.sh TAG [bench args]
 R="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 TAG=${1:-run}; shift
-ARGS=${@:-"--steps 2 --warmup 1 --no-cpu-baseline"}
+ARGS=${@:-"--full --steps 2 --warmup 1 --no-cpu-baseline"}
 cd /tmp && export TMPDIR=/tmp
 OUT=$R/gpurun_out/sq_$TAG
 mkdir -p $OUT
