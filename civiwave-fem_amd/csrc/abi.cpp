@@ -1,7 +1,10 @@
-// abi.cpp -- C-ABI (include/cwf_hip.h) over the gfx950 kernels: handle lifetime (validation, HBM layout and
-// upload, the FAST tilings and the structured-block detection), mode / scalar / timing switches and the
-// measurement entry points. One HIP stream per handle. The PCG entry points are in abi_pcg.cpp, the Stepper in
-// abi_stepper.cpp, the communicators in comm.cpp and peer.hip.
+// abi.cpp -- C-ABI (include/cwf_hip.h) over the gfx950 kernels: handle lifetime, mode / scalar / timing switches
+// and the measurement entry points. One HIP stream per handle. The PCG entry points are in abi_pcg.cpp, the
+// Stepper in abi_stepper.cpp, the communicators in comm.cpp and peer.hip.
+// cwf_hip_system_create is a sequence of stages: validate_desc, find_lattice, choose_fast_path (the one place
+// that decides the FAST layout), renumber_desc, open_handle, upload_mesh_arrays, upload_incidence, one of
+// layout_lattice / layout_groups / layout_tiles, upload_hex_jacobi, alloc_scratch. A guard (HandlePtr) holds the
+// handle and one catch takes host allocation failures, so every failing exit frees what was allocated.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -37,18 +40,6 @@ int set_error(cwf_hip_system *h, int code, const std::string &msg, const std::st
 int hip_fail(cwf_hip_system *h, hipError_t e, const char *what)
 {
     return set_error(h, CWF_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e), hipGetErrorName(e));
-}
-
-// hex8 tile lanes: 256 (<= 256 hexes, <= 512 nodes) from 1M hexes up, else 128. The per-workgroup p.Ap shares
-// every update workgroup refolds (and the r.r / r.z shares every hex workgroup refolds) halve with the
-// workgroup count: C3 hex8 +2.5-3.9% on 256 lanes, C2 hex8 -2.0-2.5% (same-box A/B, two passes).
-// CWF_HEX_NT=128|256 overrides
-uint32_t hex_tile_lanes(uint64_t hexes)
-{
-    const char *e = knob("CWF_HEX_NT");
-    if (e)
-        return atoi(e) == 256 ? 256u : 128u;
-    return hexes >= 1000000ull ? 256u : 128u;
 }
 
 }  // namespace cwf
@@ -316,28 +307,22 @@ std::vector<uint32_t> morton_node_order(const double *X, uint64_t N)
     for (int k = 0; k < 3; ++k)
         ext = std::max(ext, hi[k] - lo[k]);
     const double scale = ext > 0 ? (double)((1u << 21) - 1) / ext : 0.0;
-    auto spread = [](uint64_t v) {
-        v &= 0x1fffff;
-        v = (v | v << 32) & 0x1f00000000ffffull;
-        v = (v | v << 16) & 0x1f0000ff0000ffull;
-        v = (v | v << 8) & 0x100f00f00f00f00full;
-        v = (v | v << 4) & 0x10c30c30c30c30c3ull;
-        v = (v | v << 2) & 0x1249249249249249ull;
-        return v;
-    };
     std::vector<uint64_t> key(N);
     for (uint64_t n = 0; n < N; ++n)
     {
         uint64_t q[3];
         for (int k = 0; k < 3; ++k)
             q[k] = (uint64_t)std::llround((X[3 * n + k] - lo[k]) * scale);
-        key[n] = spread(q[0]) | spread(q[1]) << 1 | spread(q[2]) << 2;
+        key[n] = spread21(q[0]) | spread21(q[1]) << 1 | spread21(q[2]) << 2;
     }
     std::vector<uint32_t> perm(N);
     std::iota(perm.begin(), perm.end(), 0u);
     std::stable_sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) { return key[a] < key[b]; });
     return perm;
 }
+
+// ---- cwf_hip_system_create: the path choice, then one function per stage. A stage returns a status; the
+// handle's guard in create (HandlePtr) frees whatever a failing stage had allocated, so HIPTRY is safe in them.
 
 // CWF_GROUPS=0 (diagnostic): the per-tet tiles instead of the fan groups
 bool groups_enabled()
@@ -351,11 +336,571 @@ bool groups_enabled()
 // whose per-workgroup p.Ap shares every update workgroup refolds: with write-through partials C2 runs +2.3%
 // on 256 lanes (same-box A/B, two passes; 128 had been +6% before the partials were written through).
 // CWF_GROUP_NT=128|256 overrides
-uint32_t group_lanes(uint64_t E)
+uint32_t group_lanes()
 {
-    (void)E;
     const char *gn = knob("CWF_GROUP_NT");
     return gn && atoi(gn) == 128 ? 128u : 256u;
+}
+
+// hex8 tile lanes: 256 (<= 256 hexes, <= 512 nodes) from 1M hexes up, else 128. The per-workgroup p.Ap shares
+// every update workgroup refolds (and the r.r / r.z shares every hex workgroup refolds) halve with the
+// workgroup count: C3 hex8 +2.5-3.9% on 256 lanes, C2 hex8 -2.0-2.5% (same-box A/B, two passes).
+// CWF_HEX_NT=128|256 overrides
+uint32_t hex_tile_lanes(uint64_t hexes)
+{
+    const char *e = knob("CWF_HEX_NT");
+    if (e)
+        return atoi(e) == 256 ? 256u : 128u;
+    return hexes >= 1000000ull ? 256u : 128u;
+}
+
+// hex8: all 8 connectivity slots used; tet4 pads slots 4..7 with UINT32_MAX
+static bool desc_hex(const cwf_system_desc *d)
+{
+    return d->element_count && d->element_connectivity[4] != 0xFFFFFFFFu;
+}
+
+// Which FAST layout create builds for the caller's desc (is_lat: detect_lattice's verdict; geo_ok: the
+// coordinates reproduce the gradients). Structured blocks take the lattice stencil, hex8 meshes the hex tiles.
+// Tets take the fan groups when the geometry can be recomputed (the groups kernel has no gradient stream) and
+// there are <= 16 materials (D from kernel arguments or an LDS table), else the pipelined per-tet tiles, else
+// (no usable coordinates) the 48-B records; CWF_GROUPS=0 and CWF_TILE_PIPE=0 each step one kernel down.
+// owner_renumber ignores CWF_TILE_PIPE: under CWF_TILE_PIPE=0 a mesh that would take the fan groups is still
+// renumbered by their owner tiles although it runs k_keff_tiles. The knob has always behaved so; kept as it is.
+PathChoice choose_fast_path(const cwf_system_desc *d, bool is_lat, bool geo_ok)
+{
+    if (!d->element_count)
+        return {FastPath::None, false};
+    if (is_lat)
+        return {FastPath::Lattice, false};
+    if (desc_hex(d))
+        return {FastPath::HexTiles, true};
+    const bool fans = geo_ok && groups_enabled() && d->material_count <= 16;
+    const char *pp = knob("CWF_TILE_PIPE");  // diagnostic: 0 = the one-tile-per-workgroup kernel
+    const bool pipe = geo_ok && !(pp && pp[0] == '0');
+    return {!pipe ? FastPath::Tiles : fans ? FastPath::Groups : FastPath::TilesPipe, fans};
+}
+
+// validate_system (pcg.cpp:82-139)
+static int validate_desc(const cwf_system_desc *d)
+{
+    const uint64_t N = d->node_count, E = d->element_count;
+    if (d->dof_count != N * 3)
+        return set_error(nullptr, CWF_ERR_SIZE, "dof count mismatch (expected node_count * 3)",
+                         "node_count=" + std::to_string(N) + "\ndof_count=" + std::to_string(d->dof_count));
+    if (d->material_count == 0 || !d->material_stiffness)
+        return set_error(nullptr, CWF_ERR_MATERIALS, "materials table is empty");
+    if (d->reduction_block == 0)
+        return set_error(nullptr, CWF_ERR_REDUCTION, "reduction block must be >= 1", "reduction_block=0");
+    if (d->reduction_partials == 0)
+        return set_error(nullptr, CWF_ERR_REDUCTION, "reduction partial count must be >= 1", "reduction_partials=0");
+    if ((E && (!d->element_connectivity || !d->element_gradients || !d->element_volume ||
+               !d->element_material_index)) ||
+        (N && (!d->lumped_mass || !d->bc_mask)))
+        return set_error(nullptr, CWF_ERR_ARGUMENT, "null system array");
+    if (N * 3 >= (1ull << 32) || E >= (1ull << 30))
+        return set_error(nullptr, CWF_ERR_UNSUPPORTED, "mesh too large for one handle (shard it)",
+                         "nodes=" + std::to_string(N) + "\nelements=" + std::to_string(E));
+    const bool hex = desc_hex(d);
+    const int K = hex ? 8 : 4;
+    if (hex && d->mode != CWF_MODE_FAST)
+        return set_error(nullptr, CWF_ERR_UNSUPPORTED, "hex8 elements run in CWF_MODE_FAST only",
+                         "the reference has no hex8 arithmetic to reproduce (preprocess.cpp:326-330)");
+    if (hex && !d->node_coords)
+        return set_error(nullptr, CWF_ERR_ARGUMENT, "hex8 systems need node_coords");
+    for (uint64_t e = 0; e < E; ++e)
+    {
+        if (d->element_material_index[e] >= d->material_count)
+            return set_error(nullptr, CWF_ERR_MATERIAL_RANGE, "element references material out of range",
+                             "element=" + std::to_string(e) +
+                                 "\nmaterial_index=" + std::to_string(d->element_material_index[e]));
+        if ((d->element_connectivity[e * 8 + 4] != 0xFFFFFFFFu) != hex)
+            return set_error(nullptr, CWF_ERR_UNSUPPORTED, "mixed tet4/hex8 meshes are not supported",
+                             "element=" + std::to_string(e));
+        for (int a = 0; a < K; ++a)
+            if (d->element_connectivity[e * 8 + a] >= N)
+                return set_error(nullptr, CWF_ERR_NODE_RANGE, "element connectivity references node out of range",
+                                 "element=" + std::to_string(e) +
+                                     "\nnode=" + std::to_string(d->element_connectivity[e * 8 + a]));
+    }
+    return 0;
+}
+
+// Structured Kuhn block (lattice.cpp): the FAST operator is the node-pair stencil of the one shared cell
+// stiffness (k_keff_lattice). Its nodes stay in the caller's order when that is lexicographic within planes
+// (a shard's local order too); otherwise a handle that may renumber takes the lexicographic order (lat.perm).
+static bool find_lattice(const cwf_system_desc *d, bool may_renumber, Lattice &lat)
+{
+    const char *lv = knob("CWF_LATTICE");
+    if (d->mode != CWF_MODE_FAST || !d->element_count || !d->node_count || d->node_count >= 0x15555555ull ||
+        !d->node_coords || (lv && lv[0] == '0'))
+        return false;
+    std::string why;
+    const bool is_lat = detect_lattice(d, may_renumber, lat, &why);
+    if (knob("CWF_VERBOSE"))
+        fprintf(stderr, "[cwf] lattice: %s (%u x %u x %u nodes%s)\n", is_lat ? "yes" : why.c_str(), lat.nx, lat.ny,
+                lat.nz, is_lat && !lat.perm.empty() ? ", renumbered" : "");
+    return is_lat;
+}
+
+// The caller's desc in the handle's internal node order: perm[i] = caller node of internal node i, the node
+// arrays permuted by it, and `desc`, the caller's desc over them (perm converts at the ABI boundary)
+struct RenumberedDesc
+{
+    std::vector<uint32_t> perm, conn, mask;
+    std::vector<float> mass;
+    std::vector<double> coords;
+    cwf_system_desc desc{};
+
+    void apply(const cwf_system_desc *d)
+    {
+        const uint64_t N = d->node_count, E = d->element_count;
+        std::vector<uint32_t> inv(N);
+        for (uint64_t i = 0; i < N; ++i)
+            inv[perm[i]] = (uint32_t)i;
+        conn.assign(d->element_connectivity, d->element_connectivity + 8 * E);
+        for (auto &c : conn)
+            if (c != 0xFFFFFFFFu)
+                c = inv[c];
+        mass.resize(N);
+        mask.resize(N);
+        coords.resize(3 * N);
+        for (uint64_t i = 0; i < N; ++i)
+        {
+            const uint64_t n = perm[i];
+            mass[i] = d->lumped_mass[n];
+            mask[i] = d->bc_mask[n];
+            for (int k = 0; k < 3; ++k)
+                coords[3 * i + k] = d->node_coords[3 * n + k];
+        }
+        desc = *d;
+        desc.element_connectivity = conn.data();
+        desc.lumped_mass = mass.data();
+        desc.bc_mask = mask.data();
+        desc.node_coords = coords.data();
+        desc.adjacency_offsets = desc.adjacency_elements = nullptr;  // rebuilt in internal order (ascending
+        desc.adjacency_local = nullptr;                               // element per node)
+    }
+};
+
+// owner tile of every node (its record there carries the owner bit); range(tl): the tile's span of tile_nodes
+template <class Range>
+static std::vector<uint32_t> node_owner_tiles(uint64_t N, const std::vector<uint32_t> &tile_nodes, uint32_t ntiles,
+                                              Range range)
+{
+    std::vector<uint32_t> own(N, 0xFFFFFFFFu);
+    for (uint32_t tl = 0; tl < ntiles; ++tl)
+    {
+        const std::pair<uint32_t, uint32_t> r = range(tl);
+        for (uint32_t q = r.first; q < r.second; ++q)
+            if (tile_nodes[q] & 0x80000000u)
+                own[tile_nodes[q] & 0x7fffffffu] = tl;
+    }
+    return own;
+}
+
+// FAST handles renumber their nodes (cwf_hip.h CWF_DESC_KEEP_NODE_ORDER): a lattice into its lexicographic
+// order (lat.perm, taken), everything else along a Morton curve. Fan-group and hex8 meshes (pc.owner_renumber)
+// renumber again by (owner tile, Morton) so every tile's owned nodes are one contiguous id range (whole-line
+// owner p / partial stores, coalesced owned gathers). The groups and tiles are built from coordinates and tet
+// order only, so the rebuild after this renumbering gives the same partition.
+static void renumber_desc(const cwf_system_desc *d, Lattice &lat, PathChoice pc, RenumberedDesc &r)
+{
+    const uint64_t N = d->node_count, E = d->element_count;
+    if (pc.path == FastPath::Lattice)
+        r.perm.swap(lat.perm);
+    else
+        r.perm = morton_node_order(d->node_coords, N);
+    r.apply(d);
+    if (!pc.owner_renumber)
+        return;
+    std::vector<uint32_t> own;
+    if (pc.path == FastPath::HexTiles)  // the hex tiles (tiles.cpp, 8 corners): the same owner = first tile of the node
+    {
+        HostTiles ht;
+        build_tiles(&r.desc, ht, 2u * hex_tile_lanes(E), hex_tile_lanes(E), 8);
+        own = node_owner_tiles(N, ht.tile_nodes, ht.ntiles, [&](uint32_t tl) {
+            return std::make_pair(ht.tile_node_off[tl], ht.tile_node_off[tl + 1]);
+        });
+    }
+    else
+    {
+        GroupTiles gt;
+        const uint32_t gnt = group_lanes();
+        if (!fan_groups_usable(build_group_tiles(&r.desc, gt, gnt, 2 * gnt, kGroupSlotsPerLane * gnt, false), gt))
+            return;
+        own = node_owner_tiles(N, gt.tile_nodes, gt.ntiles,
+                               [&](uint32_t tl) { return std::make_pair(gt.hdr[tl].z, gt.hdr[tl].z + gt.hdr[tl].w); });
+    }
+    std::vector<uint32_t> order(N);
+    std::iota(order.begin(), order.end(), 0u);
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return own[a] < own[b]; });
+    std::vector<uint32_t> p2(N);
+    for (uint64_t i = 0; i < N; ++i)
+        p2[i] = r.perm[order[i]];
+    r.perm.swap(p2);
+    r.apply(d);
+}
+
+// the handle, its stream and pinned control block, and the scalars of DevSys
+static int open_handle(const cwf_system_desc *d, int device, HandlePtr &hp)
+{
+    hipError_t he = hipSetDevice(device);
+    if (he != hipSuccess)
+        return hip_fail(nullptr, he, "hipSetDevice");
+    hp.reset(new (std::nothrow) cwf_hip_system());
+    cwf_hip_system *h = hp.get();
+    if (!h)
+        return set_error(nullptr, CWF_ERR_ALLOC, "host allocation failed");
+    h->device = device;
+    h->mode = d->mode == CWF_MODE_FAST ? CWF_MODE_FAST : CWF_MODE_PARITY;
+    h->reduction_block = d->reduction_block;
+    h->reduction_partials = d->reduction_partials;
+    if ((he = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)) != hipSuccess)
+        return hip_fail(h, he, "hipStreamCreate");
+    if ((he = hipHostMalloc(reinterpret_cast<void **>(&h->ctl_host), sizeof(Ctl), hipHostMallocDefault)) !=
+        hipSuccess)
+        return hip_fail(h, he, "hipHostMalloc");
+    DevSys &s = h->ds;
+    s.N = (uint32_t)d->node_count;
+    s.Nown = s.N;
+    s.E = (uint32_t)d->element_count;
+    s.D = 3 * s.N;
+    s.M = (uint32_t)d->material_count;
+    s.sK = d->stiffness_scale;
+    s.sM = d->mass_factor;
+    s.iso = 1;
+    for (uint64_t m = 0; m < d->material_count; ++m)
+        s.iso &= iso_pattern(d->material_stiffness + 36 * m) ? 1 : 0;
+    if (s.M == 1)  // table order of the FAST kernels (dsrc): iso = 3x3 normal block + 3 shear diagonals
+        for (int t = 0; t < (s.iso ? 12 : 36); ++t)
+            s.d1[t] = (float)d->material_stiffness[s.iso ? (t < 9 ? (t / 3) * 6 + (t % 3) : (t - 6) * 7) : t];
+    s.hex = desc_hex(d) ? 1 : 0;
+    return 0;
+}
+
+// element records (64 B/tet; the PARITY kernels only, so none for hex8) and the per-element / per-node arrays
+static int upload_mesh_arrays(cwf_hip_system *h, const cwf_system_desc *d)
+{
+    DevSys &s = h->ds;
+    const uint64_t N = s.N, E = s.E;
+    Uploader up{h};
+    if (!s.hex)
+    {
+        std::vector<uint32_t> rec(E * 16);
+        for (uint64_t e = 0; e < E; ++e)
+        {
+            uint32_t *r = rec.data() + e * 16;
+            for (int a = 0; a < 4; ++a)
+                r[a] = d->element_connectivity[e * 8 + a];
+            std::memcpy(r + 4, d->element_gradients + e * 24, 12 * sizeof(float));
+        }
+        s.erec = up.put(reinterpret_cast<const uint4 *>(rec.data()), E * 4);
+    }
+    s.vol = up.put(d->element_volume, E);
+    s.mat = up.put(d->element_material_index, E);
+    s.dmat = up.put(d->material_stiffness, 36 * d->material_count);
+    s.mass = up.put(d->lumped_mass, N);
+    s.mask = up.put(d->bc_mask, N);
+    return up.st;
+}
+
+// node -> element CSR, ascending element per node (preprocess.cpp:380-403): the caller's, checked, or built
+static int upload_incidence(cwf_hip_system *h, const cwf_system_desc *d)
+{
+    DevSys &s = h->ds;
+    const uint64_t N = s.N, E = s.E;
+    const int K = s.hex ? 8 : 4;
+    const uint32_t sh = s.hex ? 3u : 2u;  // inc = element << sh | corner
+    std::vector<uint32_t> off(N + 1, 0), inc(E * K);
+    if (d->adjacency_offsets && d->adjacency_elements && d->adjacency_local)
+    {
+        std::memcpy(off.data(), d->adjacency_offsets, (N + 1) * sizeof(uint32_t));
+        if (off[N] != E * K || off[0] != 0)
+            return set_error(h, CWF_ERR_SIZE, "adjacency size mismatch",
+                             "expected=" + std::to_string(E * K) + "\nactual=" + std::to_string(off[N]));
+        // the caller's CSR must be exactly the node -> (element, corner) incidences in ascending element order
+        // (preprocess.cpp:389-400): every later pass indexes through it without bounds checks
+        for (uint64_t n = 0; n < N; ++n)
+        {
+            if (off[n] > off[n + 1])
+                return set_error(h, CWF_ERR_ARGUMENT, "adjacency offsets must be non-decreasing",
+                                 "node=" + std::to_string(n));
+            for (uint32_t j = off[n]; j < off[n + 1]; ++j)
+            {
+                const uint32_t e = d->adjacency_elements[j], a = d->adjacency_local[j];
+                if (e >= E || a >= (uint32_t)K || d->element_connectivity[8ull * e + a] != n ||
+                    (j > off[n] && d->adjacency_elements[j - 1] >= e))
+                    return set_error(h, CWF_ERR_ARGUMENT, "adjacency does not match the connectivity",
+                                     "node=" + std::to_string(n) + "\nentry=" + std::to_string(j));
+                inc[j] = (e << sh) | a;
+            }
+        }
+    }
+    else
+    {
+        std::vector<uint32_t> cnt(N, 0);
+        for (uint64_t e = 0; e < E; ++e)
+            for (int a = 0; a < K; ++a)
+                ++cnt[d->element_connectivity[e * 8 + a]];
+        uint32_t acc = 0;
+        for (uint64_t n = 0; n < N; ++n)
+        {
+            off[n] = acc;
+            acc += cnt[n];
+            cnt[n] = 0;
+        }
+        off[N] = acc;
+        for (uint64_t e = 0; e < E; ++e)
+            for (int a = 0; a < K; ++a)
+            {
+                const uint32_t n = d->element_connectivity[e * 8 + a];
+                inc[off[n] + cnt[n]++] = ((uint32_t)e << sh) | (uint32_t)a;
+            }
+    }
+    Uploader up{h};
+    s.off = up.put(off);
+    s.inc = up.put(inc);
+    return up.st;
+}
+
+// structured Kuhn block: the stencil blocks, the plane table and one row value per node (lattice.inc); the
+// per-class preconditioner tables when the lumped mass is a function of the boundary type
+static int layout_lattice(cwf_hip_system *h, const cwf_system_desc *d, Lattice &lat)
+{
+    DevTiles &t = h->ds.t;
+    const uint64_t N = h->ds.N;
+    std::vector<uint32_t> npo(N + 1);
+    std::iota(npo.begin(), npo.end(), 0u);
+    t.off_mask = pack_off_mask(npo, d->bc_mask, N);  // N < 2^29 (find_lattice): always packs
+    Uploader up{h};
+    t.lplane = up.put(lat.plane);
+    t.lcoef = up.put(lattice_device_coef(lat));
+    t.node_part_off = up.put(npo);
+    t.part = up.alloc<float>(3 * (N + 2));  // + 2 padding slots (update pass)
+    t.lat = 1;
+    t.lnx = lat.nx;
+    t.lny = lat.ny;
+    t.lnz = lat.nz;
+    t.lk1 = lat.nz;
+    t.lpstride = lat.nx * lat.ny;
+    for (uint32_t k = 0; k < lat.nz; ++k)
+        if (lat.plane[k] != k * t.lpstride)
+            t.lpstride = 0;
+    t.lsym = lat.sym ? 1 : 0;
+    t.lhex = lat.hex ? 1 : 0;
+    t.node_major = 1;
+    t.E = h->ds.E;
+    t.geo = 1;
+    t.total_tile_nodes = (uint32_t)N;
+    const LatticeClasses lc = lattice_classes(lat, d->bc_mask, d->lumped_mass);
+    if (lc.uniform && lc.interior)
+    {
+        t.lmu = 1;
+        t.lmass = lc.interior_mass;
+        // z from r in the K_eff pass, no z store in the update pass (attach turns it off, comm.cpp): from
+        // 2M nodes, where the iteration's vectors leave the 256 MB MALL and the 12 B per node the update
+        // pass no longer writes are HBM bytes (C3 +4-5% PCG it/s); on C2 the K_eff pass's class-table fill
+        // and the 3 x 3 products per halo entry sit on its latency-bound critical path (-8%), same box
+        const char *zr = knob("CWF_LAT_ZR");
+        t.lzr = zr ? (zr[0] == '1' ? 1 : 0) : (N >= (1ull << 21) ? 1 : 0);
+    }
+    if (lc.uniform)
+    {
+        t.lcls = up.put(lc.cls.data(), N);
+        t.lrep = up.put(lc.rep);
+        // classes without a node keep zero inverses (k_lat_class_inverse fills only represented ones; halo
+        // lanes of the z-from-r and single-launch passes may read any class)
+        t.lcinv6 = up.zeros<uint4>(kLatClasses);
+        t.lcinv9 = up.zeros<float>(9 * kLatClasses);
+        t.lcz = up.zeros<float4>(2 * kLatClasses);
+    }
+    h->lat_plane.swap(lat.plane);
+    lattice_plan(t);
+    return up.st;
+}
+
+// Fan groups (groups.cpp, k_keff_groups_pipe): the default FAST tet path when the mesh groups into fans
+// (fan_groups_usable). Sets t.grp when it does; otherwise leaves the handle for layout_tiles.
+static int layout_groups(cwf_hip_system *h, const cwf_system_desc *d)
+{
+    DevSys &s = h->ds;
+    DevTiles &t = s.t;
+    const uint64_t N = s.N, E = s.E;
+    GroupTiles gt;
+    const uint32_t gnt = group_lanes();
+    const int gst = build_group_tiles(d, gt, gnt, 2 * gnt, kGroupSlotsPerLane * gnt);
+    if (knob("CWF_VERBOSE"))
+        fprintf(stderr, "[cwf] fan groups: status %d, %u groups (%.2f tets each), %u tiles, %zu tile nodes "
+                        "(%.3f per node), max %u nodes / %u slots per tile\n",
+                gst, gt.ngroups, gt.tets_per_group, gt.ntiles, gt.tile_nodes.size(),
+                N ? (double)gt.tile_nodes.size() / (double)N : 0.0, gt.max_tile_nodes, gt.max_tile_slots);
+    if (!fan_groups_usable(gst, gt))
+        return 0;
+    const size_t T = gt.tile_nodes.size();
+    std::vector<uint2> tnode(T);
+    for (size_t q = 0; q < T; ++q)
+        tnode[q] = uint2{gt.tile_nodes[q], gt.run[q]};
+    t.off_mask = pack_off_mask(gt.node_part_off, d->bc_mask, N);
+    Uploader up{h};
+    t.grec = up.put(gt.grec);
+    t.hdr = up.put(gt.hdr);
+    t.tnode = up.put(tnode);
+    t.node_part_off = up.put(gt.node_part_off);
+    t.tslot = up.put(gt.tile_slot.data(), T);
+    t.tcoord = up.put3(gt.tcoord, T);
+    t.part = up.alloc<float>(3 * (T + 2));  // + 2 padding slots (update pass)
+    t.grp = 1;
+    t.geo = 1;
+    t.node_major = 1;
+    t.push = 1;
+    t.pipe = 1;
+    t.pipe_nt = (int)gnt;
+    t.wt_part = E < 4000000ull ? 1 : 0;  // write-through tile partials below 4M tets
+    t.ntiles = gt.ntiles;
+    t.ngroups = gt.ngroups;
+    t.max_tile_nodes = gt.max_tile_nodes;
+    t.total_tile_nodes = (uint32_t)T;
+    t.E = (uint32_t)E;
+    t.pipe_grid = fast_pipe_grid(s);
+    return up.st;
+}
+
+// FAST-mode element tiles (tiles.cpp): the hex tiles (k_keff_hex_tiles: hex_nt lanes, one hex and two tile
+// nodes per lane, push fold), the pipelined per-tet tiles or one tile per workgroup.
+// GEO (geo_ok): stream 8-B corner ids + tile-node coordinates and recompute gradients/volume on the fly, when
+// the desc carries coordinates that reproduce its gradients (CWF_GEO=0 forces the 48-B records)
+static int layout_tiles(cwf_hip_system *h, const cwf_system_desc *d, FastPath path, bool geo_ok)
+{
+    DevSys &s = h->ds;
+    DevTiles &t = s.t;
+    const uint64_t N = s.N, E = s.E;
+    const bool hex = path == FastPath::HexTiles, pipe = path == FastPath::TilesPipe;
+    t.geo = hex || geo_ok ? 1 : 0;
+    t.pipe = pipe ? 1 : 0;
+    t.push = hex || pipe ? 1 : 0;  // the pipelined kernel folds pushed forces (epos), not local-CSR entries
+    HostTiles ht;
+    if (hex)
+    {
+        t.hex = 1;
+        t.hex_nt = (int)hex_tile_lanes(E);
+        build_tiles(d, ht, 2u * (uint32_t)t.hex_nt, (uint32_t)t.hex_nt, 8);
+    }
+    else if (pipe)
+    {
+        // 256-thread workgroups over 512-element tiles, or 128 over 256 (128 below 4M tets: the meshes whose
+        // 512-element tiles would give each resident workgroup < 8 tiles)
+        t.pipe_nt = E < 4000000ull ? 128 : 256;
+        build_tiles(d, ht, (uint32_t)t.pipe_nt, 2u * (uint32_t)t.pipe_nt);
+    }
+    else
+        build_tiles(d, ht, (uint32_t)kMaxTileNodes, (uint32_t)kTileElems);
+    const size_t T = ht.tile_nodes.size();
+    if (knob("CWF_VERBOSE"))
+        fprintf(stderr, "[cwf] tiles: %u tiles, %zu tile nodes (%.3f per node), max %u nodes/tile, %s records\n",
+                ht.ntiles, T, N ? (double)T / (double)N : 0.0, ht.max_tile_nodes,
+                t.geo ? "8-B geometric" : "48-B gradient");
+    Uploader up{h};
+    if (t.geo)
+    {
+        if (hex)
+            t.eid8 = up.put(ht.eid8.data(), E);
+        else
+            t.eid = up.put(ht.eid.data(), E);
+        t.tcoord = up.put3(ht.tcoord, T);
+    }
+    else
+        t.planes = up.put3(ht.planes, E);
+    if (!ht.mat.empty())
+        t.mat = up.put(ht.mat.data(), E);
+    // only the tet push fold pads its runs, within the pipelined kernel's slot budget (4 te + 2 nt)
+    const TileRecords rec = pack_tile_records(ht, hex ? 8 : 4, pipe, 8u * (uint32_t)t.pipe_nt + 2u * (uint32_t)t.pipe_nt);
+    t.hdr = up.put(rec.hdr);
+    t.tnode = up.put(rec.tnode);
+    if (!t.push)  // PUSH streams the per-element positions (epos) instead
+    {
+        ht.csr_ent.resize(ht.csr_ent.size() + 8, 0);  // the kernel reads a tile's entries as 16-B words
+        t.csr_ent = up.put(ht.csr_ent);
+    }
+    t.off_mask = pack_off_mask(ht.node_part_off, d->bc_mask, N);
+    t.node_part_off = up.put(ht.node_part_off);
+    t.part_slot = up.put(ht.node_part_slot);
+    if (hex)
+        t.epos8 = up.put(ht.epos8);
+    else if (pipe)
+        t.epos = up.put(ht.epos);
+    if (pipe || hex)
+    {
+        t.tslot = up.put(ht.tile_slot);
+        t.node_major = 1;
+    }
+    t.part = up.alloc<float>(3 * (T + 2));  // + 2 padding slots (update pass)
+    t.ntiles = ht.ntiles;
+    t.hex_all_affine = hex && !ht.tile_affine.empty() &&
+                       std::all_of(ht.tile_affine.begin(), ht.tile_affine.end(), [](uint8_t a) { return a != 0; });
+    t.max_tile_nodes = ht.max_tile_nodes;
+    t.total_tile_nodes = (uint32_t)T;
+    t.E = (uint32_t)E;
+    if (pipe || hex)
+        t.pipe_grid = fast_pipe_grid(s);
+    return up.st;
+}
+
+// the hex block-Jacobi setup integrates from the global corners (fp64)
+static int upload_hex_jacobi(cwf_hip_system *h, const cwf_system_desc *d)
+{
+    DevSys &s = h->ds;
+    Uploader up{h};
+    s.hconn = up.put(d->element_connectivity, 8ull * s.E);
+    s.hcoord = up.put(d->node_coords, 3ull * s.N);
+    s.hgrad = up.put(d->element_gradients, 24ull * s.E);
+    return up.st;
+}
+
+// solver vectors, reduction partials and scalars; perm (a renumbered handle's node order) or NULL
+static int alloc_scratch(cwf_hip_system *h, const cwf_system_desc *d, const std::vector<uint32_t> *perm)
+{
+    const DevSys &s = h->ds;
+    const uint64_t N = s.N, D = 3 * N;
+    Uploader up{h};
+    for (float **v : {&h->x, &h->r, &h->p, &h->p2, &h->p3, &h->p4, &h->z, &h->Ap, &h->rhs, &h->tmp})
+        *v = up.alloc<float>(D);
+    if (s.t.lat && s.t.lcls)  // the fused lattice iteration's second r / Ap and its shares (lattice_fused.inc)
+    {
+        h->r2 = up.alloc<float>(D);
+        h->ap2 = up.alloc<float>(D);
+        h->fsh = up.alloc<double>(2ull * 5 * std::max<uint32_t>(s.t.lnwork, 1u));
+        h->g_fsh = up.alloc<double>(8);  // one rank until attach (comm.cpp grows it to [nranks][8])
+    }
+    h->inv = up.alloc<float>(9 * N);
+    h->inv6 = up.alloc<float>(4 * N);
+    const uint64_t chunks = (D + d->reduction_block - 1) / d->reduction_block;
+    h->part_cap = std::max<uint64_t>(
+        {chunks, (uint64_t)fast_block_count(h), (uint64_t)fast_dot_blocks(s.D), (uint64_t)s.t.ntiles,
+         (uint64_t)s.t.pipe_grid, 1});
+    for (double **v : {&h->part0, &h->part1, &h->part2})
+        *v = up.alloc<double>(h->part_cap);
+    h->ctl = up.alloc<Ctl>(1);
+    h->scal = up.alloc<double>(8);
+    // folded per-rank scalars (one rank until cwf_hip_system_attach): p.Ap, {r.r, r.z}, {rhs.rhs, r0.r0}, r0.z0
+    h->g_pap = up.alloc<double>(6);
+    h->g_rrz = h->g_pap + 1;
+    h->g_init = h->g_rrz + 2;
+    h->g_rz0 = h->g_init + 2;
+    if (perm)
+    {
+        h->perm = up.put(*perm);
+        h->pbuf = up.alloc<float>(13 * N);
+    }
+    if (!up.st && h->mode == CWF_MODE_PARITY)
+        up.st = parity_force_buffer(h);
+    if (up.st)
+        return up.st;
+    HIPTRY(h, hipMemset(h->x, 0, D * sizeof(float)));
+    HIPTRY(h, hipMemset(h->ctl, 0, sizeof(Ctl)));
+    HIPTRY(h, hipMemset(h->g_pap, 0, 6 * sizeof(double)));
+    HIPTRY(h, hipDeviceSynchronize());
+    return 0;
 }
 
 }  // namespace cwf
@@ -405,806 +950,69 @@ void cwf_hip_system_destroy(cwf_hip_system *h)
     delete h;
 }
 
+// validate, choose the FAST path, renumber, open the handle, then one stage per group of device arrays (above).
+// Host arrays live and die inside their stage. Every exit after the handle exists goes through hp.
 int cwf_hip_system_create(const cwf_system_desc *d, int device, cwf_hip_system **out)
 {
     if (!d || !out)
         return set_error(nullptr, CWF_ERR_ARGUMENT, "null pointer");
     *out = nullptr;
-    const uint64_t N = d->node_count, E = d->element_count;
-    // validate_system (pcg.cpp:82-139)
-    if (d->dof_count != N * 3)
-        return set_error(nullptr, CWF_ERR_SIZE, "dof count mismatch (expected node_count * 3)",
-                         "node_count=" + std::to_string(N) + "\ndof_count=" + std::to_string(d->dof_count));
-    if (d->material_count == 0 || !d->material_stiffness)
-        return set_error(nullptr, CWF_ERR_MATERIALS, "materials table is empty");
-    if (d->reduction_block == 0)
-        return set_error(nullptr, CWF_ERR_REDUCTION, "reduction block must be >= 1", "reduction_block=0");
-    if (d->reduction_partials == 0)
-        return set_error(nullptr, CWF_ERR_REDUCTION, "reduction partial count must be >= 1", "reduction_partials=0");
-    if ((E && (!d->element_connectivity || !d->element_gradients || !d->element_volume ||
-               !d->element_material_index)) ||
-        (N && (!d->lumped_mass || !d->bc_mask)))
-        return set_error(nullptr, CWF_ERR_ARGUMENT, "null system array");
-    if (N * 3 >= (1ull << 32) || E >= (1ull << 30))
-        return set_error(nullptr, CWF_ERR_UNSUPPORTED, "mesh too large for one handle (shard it)",
-                         "nodes=" + std::to_string(N) + "\nelements=" + std::to_string(E));
-    // hex8: all 8 connectivity slots used; tet4 pads slots 4..7 with UINT32_MAX
-    const bool hex = E && d->element_connectivity[4] != 0xFFFFFFFFu;
-    const int K = hex ? 8 : 4;
-    if (hex && d->mode != CWF_MODE_FAST)
-        return set_error(nullptr, CWF_ERR_UNSUPPORTED, "hex8 elements run in CWF_MODE_FAST only",
-                         "the reference has no hex8 arithmetic to reproduce (preprocess.cpp:326-330)");
-    if (hex && !d->node_coords)
-        return set_error(nullptr, CWF_ERR_ARGUMENT, "hex8 systems need node_coords");
-    for (uint64_t e = 0; e < E; ++e)
-    {
-        if (d->element_material_index[e] >= d->material_count)
-            return set_error(nullptr, CWF_ERR_MATERIAL_RANGE, "element references material out of range",
-                             "element=" + std::to_string(e) +
-                                 "\nmaterial_index=" + std::to_string(d->element_material_index[e]));
-        if ((d->element_connectivity[e * 8 + 4] != 0xFFFFFFFFu) != hex)
-            return set_error(nullptr, CWF_ERR_UNSUPPORTED, "mixed tet4/hex8 meshes are not supported",
-                             "element=" + std::to_string(e));
-        for (int a = 0; a < K; ++a)
-            if (d->element_connectivity[e * 8 + a] >= N)
-                return set_error(nullptr, CWF_ERR_NODE_RANGE, "element connectivity references node out of range",
-                                 "element=" + std::to_string(e) +
-                                     "\nnode=" + std::to_string(d->element_connectivity[e * 8 + a]));
-    }
-    // FAST handles renumber their nodes along a Morton curve (cwf_hip.h CWF_DESC_KEEP_NODE_ORDER): the
-    // rest of create then sees a desc in internal order; perm converts at the boundary
-    cwf_system_desc rd{};
-    std::vector<uint32_t> r_perm, r_conn, r_mask;
-    std::vector<float> r_mass;
-    std::vector<double> r_coords;
-    const char *rn = knob("CWF_RENUMBER");
-    const bool may_renumber = d->mode == CWF_MODE_FAST && E && N && d->node_coords &&
-                              !(d->reserved & CWF_DESC_KEEP_NODE_ORDER) && !(rn && rn[0] == '0');
-    // structured Kuhn block (lattice.cpp): the FAST operator is the node-pair stencil of the one shared cell
-    // stiffness (k_keff_lattice). Its nodes stay in the caller's order when that is lexicographic within planes
-    // (a shard's local order too); otherwise a handle that may renumber takes the lexicographic order.
-    Lattice lat;
-    bool is_lat = false;
-    {
-        const char *lv = knob("CWF_LATTICE");
-        if (d->mode == CWF_MODE_FAST && E && N && N < 0x15555555ull && d->node_coords && !(lv && lv[0] == '0'))
+    HandlePtr hp(nullptr, cwf_hip_system_destroy);
+    // the handle's message and context outlive it in the thread-local error
+    const auto bail = [&hp](int st) {
+        if (hp)
         {
-            std::string why;
-            try
-            {
-                is_lat = detect_lattice(d, may_renumber, lat, &why);
-            }
-            catch (const std::bad_alloc &)
-            {
-                return set_error(nullptr, CWF_ERR_ALLOC, "host allocation failed");
-            }
-            if (knob("CWF_VERBOSE"))
-                fprintf(stderr, "[cwf] lattice: %s (%u x %u x %u nodes%s)\n", is_lat ? "yes" : why.c_str(), lat.nx,
-                        lat.ny, lat.nz, is_lat && !lat.perm.empty() ? ", renumbered" : "");
+            const std::string m = hp->err, c = hp->ctx;
+            hp.reset();
+            set_error(nullptr, st, m, c);
         }
-    }
-    const bool renumber = may_renumber && (!is_lat || !lat.perm.empty());
-    // FAST recomputes tet geometry from node coordinates when they reproduce the desc's gradients (GEO); only
-    // then can the tets group into fans (the groups kernel has no gradient stream). Node renumbering does not
-    // change it, so it is decided once, on the caller's desc.
-    const char *ge = knob("CWF_GEO");
-    const bool geo_ok = E && N && d->node_coords && !(ge && ge[0] == '0') &&
-                        (d->element_connectivity[4] != 0xFFFFFFFFu || geometry_matches(d));
-    if (renumber)
-    {
-        const auto apply_perm = [&]() {
-            std::vector<uint32_t> inv(N);
-            for (uint64_t i = 0; i < N; ++i)
-                inv[r_perm[i]] = (uint32_t)i;
-            r_conn.assign(d->element_connectivity, d->element_connectivity + 8 * E);
-            for (auto &c : r_conn)
-                if (c != 0xFFFFFFFFu)
-                    c = inv[c];
-            r_mass.resize(N);
-            r_mask.resize(N);
-            r_coords.resize(3 * N);
-            for (uint64_t i = 0; i < N; ++i)
-            {
-                const uint64_t n = r_perm[i];
-                r_mass[i] = d->lumped_mass[n];
-                r_mask[i] = d->bc_mask[n];
-                for (int k = 0; k < 3; ++k)
-                    r_coords[3 * i + k] = d->node_coords[3 * n + k];
-            }
-        };
-        try
-        {
-            if (is_lat)  // lexicographic lattice order (lattice.cpp)
-            {
-                r_perm.swap(lat.perm);
-                apply_perm();
-            }
-            else
-            {
-            r_perm = morton_node_order(d->node_coords, N);
-            apply_perm();
-            // fan-group and hex8 meshes: renumber again by (owner tile, Morton) so every tile's owned nodes are one
-            // contiguous id range (whole-line owner p / partial stores, coalesced owned gathers). The groups
-            // and tiles are built from coordinates and tet order only, so the rebuild after this renumbering
-            // gives the same partition.
-            if (hex || (d->material_count <= 16 && groups_enabled() && geo_ok))
-            {
-                cwf_system_desc md = *d;
-                md.element_connectivity = r_conn.data();
-                md.lumped_mass = r_mass.data();
-                md.bc_mask = r_mask.data();
-                md.node_coords = r_coords.data();
-                std::vector<uint32_t> own;
-                if (hex)  // the hex tiles (tiles.cpp, 8 corners): the same owner = first tile of the node
-                {
-                    HostTiles ht;
-                    build_tiles(&md, ht, 2u * hex_tile_lanes(E), hex_tile_lanes(E), 8);
-                    own.assign(N, 0xFFFFFFFFu);
-                    for (uint32_t tl = 0; tl < ht.ntiles; ++tl)
-                        for (uint32_t q = ht.tile_node_off[tl]; q < ht.tile_node_off[tl + 1]; ++q)
-                            if (ht.tile_nodes[q] & 0x80000000u)
-                                own[ht.tile_nodes[q] & 0x7fffffffu] = tl;
-                }
-                else
-                {
-                    GroupTiles gt;
-                    const uint32_t gnt = group_lanes(E);
-                    if (build_group_tiles(&md, gt, gnt, 2 * gnt, kGroupSlotsPerLane * gnt, false) == 0 &&
-                        gt.tets_per_group >= 3.0)
-                    {
-                        own.assign(N, 0xFFFFFFFFu);
-                        for (uint32_t tl = 0; tl < gt.ntiles; ++tl)
-                            for (uint32_t q = gt.hdr[tl].z; q < gt.hdr[tl].z + gt.hdr[tl].w; ++q)
-                                if (gt.tile_nodes[q] & 0x80000000u)
-                                    own[gt.tile_nodes[q] & 0x7fffffffu] = tl;
-                    }
-                }
-                if (!own.empty())
-                {
-                    std::vector<uint32_t> order(N);
-                    std::iota(order.begin(), order.end(), 0u);
-                    std::stable_sort(order.begin(), order.end(),
-                                     [&](uint32_t a, uint32_t b) { return own[a] < own[b]; });
-                    std::vector<uint32_t> p2(N);
-                    for (uint64_t i = 0; i < N; ++i)
-                        p2[i] = r_perm[order[i]];
-                    r_perm.swap(p2);
-                    apply_perm();
-                }
-            }
-            }  // !is_lat
-        }
-        catch (const std::bad_alloc &)
-        {
-            return set_error(nullptr, CWF_ERR_ALLOC, "host allocation failed");
-        }
-        rd = *d;
-        rd.element_connectivity = r_conn.data();
-        rd.lumped_mass = r_mass.data();
-        rd.bc_mask = r_mask.data();
-        rd.node_coords = r_coords.data();
-        rd.adjacency_offsets = nullptr;  // rebuilt in internal order (ascending element per node)
-        rd.adjacency_elements = nullptr;
-        rd.adjacency_local = nullptr;
-        d = &rd;
-    }
-    hipError_t he = hipSetDevice(device);
-    if (he != hipSuccess)
-        return hip_fail(nullptr, he, "hipSetDevice");
-
-    cwf_hip_system *h = new (std::nothrow) cwf_hip_system();
-    if (!h)
-        return set_error(nullptr, CWF_ERR_ALLOC, "host allocation failed");
-    auto bail = [&](int st) {
-        std::string m = h->err, c = h->ctx;
-        cwf_hip_system_destroy(h);
-        set_error(nullptr, st, m, c);
         return st;
     };
-    h->device = device;
-    h->mode = d->mode == CWF_MODE_FAST ? CWF_MODE_FAST : CWF_MODE_PARITY;
-    h->reduction_block = d->reduction_block;
-    h->reduction_partials = d->reduction_partials;
-    if ((he = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)) != hipSuccess)
-        return bail(hip_fail(h, he, "hipStreamCreate"));
-    if ((he = hipHostMalloc(reinterpret_cast<void **>(&h->ctl_host), sizeof(Ctl), hipHostMallocDefault)) !=
-        hipSuccess)
-        return bail(hip_fail(h, he, "hipHostMalloc"));
-
-    DevSys &s = h->ds;
-    s.N = (uint32_t)N;
-    s.Nown = (uint32_t)N;
-    s.E = (uint32_t)E;
-    s.D = (uint32_t)(3 * N);
-    s.M = (uint32_t)d->material_count;
-    s.sK = d->stiffness_scale;
-    s.sM = d->mass_factor;
-    s.iso = 1;
-    for (uint64_t m = 0; m < d->material_count; ++m)
-        s.iso &= iso_pattern(d->material_stiffness + 36 * m) ? 1 : 0;
-    if (s.M == 1)  // table order of the FAST kernels (dsrc): iso = 3x3 normal block + 3 shear diagonals
-        for (int t = 0; t < (s.iso ? 12 : 36); ++t)
-            s.d1[t] = (float)d->material_stiffness[s.iso ? (t < 9 ? (t / 3) * 6 + (t % 3) : (t - 6) * 7) : t];
-    s.hex = hex ? 1 : 0;
-
-    // element records (64 B/tet; the PARITY kernels only, so none for hex8)
-    if (!hex)
+    try
     {
-        std::vector<uint32_t> rec;
-        try
+        if (int st = validate_desc(d))
+            return st;
+        const bool hex = desc_hex(d);
+        const char *rn = knob("CWF_RENUMBER");
+        const bool may_renumber = d->mode == CWF_MODE_FAST && d->element_count && d->node_count && d->node_coords &&
+                                  !(d->reserved & CWF_DESC_KEEP_NODE_ORDER) && !(rn && rn[0] == '0');
+        Lattice lat;
+        const bool is_lat = find_lattice(d, may_renumber, lat);
+        // FAST recomputes tet geometry from node coordinates when they reproduce the desc's gradients (GEO).
+        // Node renumbering does not change it, so it is decided once, on the caller's desc.
+        const char *ge = knob("CWF_GEO");
+        const bool geo_ok = d->element_count && d->node_count && d->node_coords && !(ge && ge[0] == '0') &&
+                            (hex || geometry_matches(d));
+        const PathChoice pc = choose_fast_path(d, is_lat, geo_ok);
+        RenumberedDesc rd;  // the rest of create sees the desc in internal order
+        const bool renumber = may_renumber && (!is_lat || !lat.perm.empty());
+        if (renumber)
         {
-            rec.resize(E * 16);
+            renumber_desc(d, lat, pc, rd);
+            d = &rd.desc;
         }
-        catch (const std::bad_alloc &)
-        {
-            return bail(set_error(h, CWF_ERR_ALLOC, "host allocation failed"));
-        }
-        for (uint64_t e = 0; e < E; ++e)
-        {
-            uint32_t *r = rec.data() + e * 16;
-            for (int a = 0; a < 4; ++a)
-                r[a] = d->element_connectivity[e * 8 + a];
-            std::memcpy(r + 4, d->element_gradients + e * 24, 12 * sizeof(float));
-        }
-        uint4 *erec = nullptr;
-        if (int st = upload(h, &erec, reinterpret_cast<const uint4 *>(rec.data()), E * 4))
-            return bail(st);
-        s.erec = erec;
-    }
-    {
-        float *vol;
-        uint32_t *mat;
-        double *dm;
-        float *mass;
-        uint32_t *mask;
-        if (int st = upload(h, &vol, d->element_volume, E))
-            return bail(st);
-        if (int st = upload(h, &mat, d->element_material_index, E))
-            return bail(st);
-        if (int st = upload(h, &dm, d->material_stiffness, 36 * d->material_count))
-            return bail(st);
-        if (int st = upload(h, &mass, d->lumped_mass, N))
-            return bail(st);
-        if (int st = upload(h, &mask, d->bc_mask, N))
-            return bail(st);
-        s.vol = vol;
-        s.mat = mat;
-        s.dmat = dm;
-        s.mass = mass;
-        s.mask = mask;
-    }
-    // node -> element CSR, ascending element per node (preprocess.cpp:380-403)
-    {
-        std::vector<uint32_t> off(N + 1, 0), inc;
-        const uint32_t sh = hex ? 3u : 2u;  // inc = element << sh | corner
-        try
-        {
-            inc.resize(E * K);
-        }
-        catch (const std::bad_alloc &)
-        {
-            return bail(set_error(h, CWF_ERR_ALLOC, "host allocation failed"));
-        }
-        if (d->adjacency_offsets && d->adjacency_elements && d->adjacency_local)
-        {
-            std::memcpy(off.data(), d->adjacency_offsets, (N + 1) * sizeof(uint32_t));
-            if (off[N] != E * K || off[0] != 0)
-                return bail(set_error(h, CWF_ERR_SIZE, "adjacency size mismatch",
-                                      "expected=" + std::to_string(E * K) + "\nactual=" + std::to_string(off[N])));
-            // the caller's CSR must be exactly the node -> (element, corner) incidences in ascending element order
-            // (preprocess.cpp:389-400): every later pass indexes through it without bounds checks
-            for (uint64_t n = 0; n < N; ++n)
-            {
-                if (off[n] > off[n + 1])
-                    return bail(set_error(h, CWF_ERR_ARGUMENT, "adjacency offsets must be non-decreasing",
-                                          "node=" + std::to_string(n)));
-                for (uint32_t j = off[n]; j < off[n + 1]; ++j)
-                {
-                    const uint32_t e = d->adjacency_elements[j], a = d->adjacency_local[j];
-                    if (e >= E || a >= (uint32_t)K || d->element_connectivity[8ull * e + a] != n ||
-                        (j > off[n] && d->adjacency_elements[j - 1] >= e))
-                        return bail(set_error(h, CWF_ERR_ARGUMENT, "adjacency does not match the connectivity",
-                                              "node=" + std::to_string(n) + "\nentry=" + std::to_string(j)));
-                    inc[j] = (e << sh) | a;
-                }
-            }
-        }
-        else
-        {
-            std::vector<uint32_t> cnt(N, 0);
-            for (uint64_t e = 0; e < E; ++e)
-                for (int a = 0; a < K; ++a)
-                    ++cnt[d->element_connectivity[e * 8 + a]];
-            uint32_t acc = 0;
-            for (uint64_t n = 0; n < N; ++n)
-            {
-                off[n] = acc;
-                acc += cnt[n];
-                cnt[n] = 0;
-            }
-            off[N] = acc;
-            for (uint64_t e = 0; e < E; ++e)
-                for (int a = 0; a < K; ++a)
-                {
-                    const uint32_t n = d->element_connectivity[e * 8 + a];
-                    inc[off[n] + cnt[n]++] = ((uint32_t)e << sh) | (uint32_t)a;
-                }
-        }
-        uint32_t *doff, *dinc;
-        if (int st = upload(h, &doff, off.data(), N + 1))
-            return bail(st);
-        if (int st = upload(h, &dinc, inc.data(), E * K))
-            return bail(st);
-        s.off = doff;
-        s.inc = dinc;
-    }
-    // structured Kuhn block: the stencil blocks, the plane table and one row value per node (lattice.inc)
-    if (E && is_lat)
-    {
-        DevTiles &t = s.t;
-        std::vector<uint32_t> npo(N + 1);
-        for (uint64_t n = 0; n <= N; ++n)
-            npo[n] = (uint32_t)n | (n < N ? (d->bc_mask[n] & 7u) << 29 : 0u);
-        uint32_t *dpl, *dnpo;
-        float *dcf, *part;
-        if (int st = upload(h, &dpl, lat.plane.data(), lat.plane.size()))
-            return bail(st);
-        // the device copy's stencil blocks are stored row-pair interleaved for the packed rows of k_keff_lattice:
-        // per offset {S00 S10 S01 S11 S02 S12 S20 S21 S22}; the cell-pair blocks after them keep row-major order
-        std::vector<float> cdev(lat.coef, lat.coef + (lat.hex ? kLatHexCoef : kLatCoef));
-        for (int o = 0; o < (lat.hex ? kLatHexOffsets : kLatOffsets); ++o)
-            for (int c = 0; c < 3; ++c)
-            {
-                cdev[9 * o + 2 * c] = lat.coef[9 * o + c];
-                cdev[9 * o + 2 * c + 1] = lat.coef[9 * o + 3 + c];
-                cdev[9 * o + 6 + c] = lat.coef[9 * o + 6 + c];
-            }
-        if (int st = upload(h, &dcf, cdev.data(), (uint64_t)cdev.size()))
-            return bail(st);
-        if (int st = upload(h, &dnpo, npo.data(), npo.size()))
-            return bail(st);
-        if (int st = dalloc(h, &part, 3 * (N + 2)))  // + 2 padding slots (update pass)
-            return bail(st);
-        t.lat = 1;
-        t.lnx = lat.nx;
-        t.lny = lat.ny;
-        t.lnz = lat.nz;
-        t.lk0 = 0;
-        t.lk1 = lat.nz;
-        t.lplane = dpl;
-        t.lpstride = lat.nx * lat.ny;
-        for (uint32_t k = 0; k < lat.nz; ++k)
-            if (lat.plane[k] != k * t.lpstride)
-                t.lpstride = 0;
-        t.lcoef = dcf;
-        t.lsym = lat.sym ? 1 : 0;
-        t.lhex = lat.hex ? 1 : 0;
-        t.node_part_off = dnpo;
-        t.off_mask = 1;
-        t.node_major = 1;
-        t.part = part;
-        t.E = (uint32_t)E;
-        t.geo = 1;
-        t.total_tile_nodes = (uint32_t)N;
-        t.wt_part = 0;
-        // per-class preconditioner (the update pass reads one byte per node instead of the 16-B record and the
-        // partial-run bounds) when the lumped mass is a function of the boundary type
-        {
-            std::vector<uint8_t> cls(N);
-            std::vector<uint32_t> rep(kLatClasses, 0xFFFFFFFFu);
-            std::vector<float> tmass(27, 0.f);
-            std::vector<uint8_t> tseen(27, 0);
-            bool uniform = true;
-            for (uint32_t k = 0; k < lat.nz && uniform; ++k)
-                for (uint32_t j = 0; j < lat.ny; ++j)
-                    for (uint32_t i = 0; i < lat.nx; ++i)
-                    {
-                        const uint32_t n = lat.plane[k] + j * lat.nx + i;
-                        const auto side = [](uint32_t a, uint32_t na) { return a == 0 ? 0u : a + 1 == na ? 2u : 1u; };
-                        const uint32_t ty = side(i, lat.nx) + 3 * side(j, lat.ny) + 9 * side(k, lat.nz);
-                        const uint32_t c = ty << 3 | (d->bc_mask[n] & 7u);
-                        cls[n] = (uint8_t)c;
-                        if (rep[c] == 0xFFFFFFFFu || n < rep[c])
-                            rep[c] = n;
-                        if (!tseen[ty])
-                        {
-                            tseen[ty] = 1;
-                            tmass[ty] = d->lumped_mass[n];
-                        }
-                        else if (std::memcmp(&tmass[ty], &d->lumped_mass[n], sizeof(float)) != 0)
-                            uniform = false;
-                    }
-            if (uniform && tseen[13])  // type 13: inside along x, y and z (the bricks' nodes)
-            {
-                t.lmu = 1;
-                t.lmass = tmass[13];
-                // z from r in the K_eff pass, no z store in the update pass (attach turns it off, comm.cpp): from
-                // 2M nodes, where the iteration's vectors leave the 256 MB MALL and the 12 B per node the update
-                // pass no longer writes are HBM bytes (C3 +4-5% PCG it/s); on C2 the K_eff pass's class-table fill
-                // and the 3 x 3 products per halo entry sit on its latency-bound critical path (-8%), same box
-                const char *zr = knob("CWF_LAT_ZR");
-                t.lzr = zr ? (zr[0] == '1' ? 1 : 0) : (N >= (1ull << 21) ? 1 : 0);
-            }
-            if (uniform)
-            {
-                uint8_t *dcls;
-                uint32_t *drep;
-                uint4 *dci6;
-                float *dci9;
-                if (int st = upload(h, &dcls, cls.data(), N))
-                    return bail(st);
-                if (int st = upload(h, &drep, rep.data(), kLatClasses))
-                    return bail(st);
-                if (int st = dalloc(h, &dci6, kLatClasses))
-                    return bail(st);
-                if (int st = dalloc(h, &dci9, 9 * kLatClasses))
-                    return bail(st);
-                float4 *dcz;
-                if (int st = dalloc(h, &dcz, 2 * kLatClasses))
-                    return bail(st);
-                HIPTRY(h, hipMemset(dcz, 0, 2 * kLatClasses * sizeof(float4)));
-                // classes without a node keep zero inverses (k_lat_class_inverse fills only represented ones; halo
-                // lanes of the z-from-r and single-launch passes may read any class)
-                HIPTRY(h, hipMemset(dci6, 0, kLatClasses * sizeof(uint4)));
-                HIPTRY(h, hipMemset(dci9, 0, 9 * kLatClasses * sizeof(float)));
-                t.lcls = dcls;
-                t.lrep = drep;
-                t.lcinv6 = dci6;
-                t.lcinv9 = dci9;
-                t.lcz = dcz;
-            }
-        }
-        h->lat_plane.swap(lat.plane);
-        lattice_plan(t);
-    }
-    // FAST-mode element tiles (tiles.cpp)
-    else if (E)
-    {
-        HostTiles ht;
-        DevTiles &t = s.t;
-        // GEO: stream 8-B corner ids + tile-node coordinates and recompute gradients/volume on the fly,
-        // when the desc carries coordinates that reproduce its gradients (CWF_GEO=0 forces the records)
-        t.geo = hex || geo_ok ? 1 : 0;
-        if (hex)  // k_keff_hex_tiles: hex_nt lanes, one hex and two tile nodes per lane, push fold
-        {
-            t.hex = 1;
-            t.hex_nt = (int)hex_tile_lanes(E);
-            t.wt_part = 0;
-            t.push = 1;
-        }
-        else
-        {
-            const char *pp = knob("CWF_TILE_PIPE");  // diagnostic: 0 = the one-tile-per-workgroup kernel
-            t.pipe = t.geo && !(pp && pp[0] == '0') ? 1 : 0;
-        }
-        // fan groups (groups.cpp, k_keff_groups_pipe): the default FAST tet path when the mesh groups into
-        // fans of >= 3 tets on average and has <= 16 materials (D from kernel arguments or an LDS table);
-        // CWF_GROUPS=0: the per-tet tiles below
-        bool grouped = false;
-        {
-            if (!hex && t.pipe && groups_enabled() && d->material_count <= 16)
-            {
-                GroupTiles gt;
-                int gst = -1;
-                const uint32_t gnt = group_lanes(E);
-                try
-                {
-                    gst = build_group_tiles(d, gt, gnt, 2 * gnt, kGroupSlotsPerLane * gnt);
-                }
-                catch (const std::bad_alloc &)
-                {
-                    return bail(set_error(h, CWF_ERR_ALLOC, "host allocation failed"));
-                }
-                if (knob("CWF_VERBOSE"))
-                    fprintf(stderr, "[cwf] fan groups: status %d, %u groups (%.2f tets each), %u tiles, %zu tile nodes "
-                                    "(%.3f per node), max %u nodes / %u slots per tile\n",
-                            gst, gt.ngroups, gt.tets_per_group, gt.ntiles, gt.tile_nodes.size(),
-                            N ? (double)gt.tile_nodes.size() / (double)N : 0.0, gt.max_tile_nodes, gt.max_tile_slots);
-                if (gst == 0 && gt.tets_per_group >= 3.0)
-                {
-                    const size_t T = gt.tile_nodes.size();
-                    std::vector<uint2> tnode(T);
-                    for (size_t q = 0; q < T; ++q)
-                        tnode[q] = uint2{gt.tile_nodes[q], gt.run[q]};
-                    if (ht_off_mask_ok(gt.node_part_off))
-                    {
-                        for (uint64_t n = 0; n < N; ++n)
-                            gt.node_part_off[n] |= (d->bc_mask[n] & 7u) << 29;
-                        t.off_mask = 1;
-                    }
-                    uint4 *ga, *dh;
-                    uint2 *dtn;
-                    uint32_t *npo, *tsl;
-                    float *tc, *part;
-                    if (int st = upload(h, &ga, gt.grec.data(), gt.grec.size()))
-                        return bail(st);
-                    if (int st = upload(h, &dh, gt.hdr.data(), gt.hdr.size()))
-                        return bail(st);
-                    if (int st = upload(h, &dtn, tnode.data(), T))
-                        return bail(st);
-                    if (int st = upload(h, &npo, gt.node_part_off.data(), gt.node_part_off.size()))
-                        return bail(st);
-                    if (int st = upload(h, &tsl, gt.tile_slot.data(), T))
-                        return bail(st);
-                    if (int st = dalloc(h, &tc, 3 * T))
-                        return bail(st);
-                    for (int q = 0; q < 3; ++q)
-                        HIPTRY(h, hipMemcpy(tc + q * T, gt.tcoord[q].data(), T * sizeof(float), hipMemcpyHostToDevice));
-                    if (int st = dalloc(h, &part, 3 * (T + 2)))  // + 2 padding slots (update pass)
-                        return bail(st);
-                    t.grp = 1;
-                    t.grec = ga;
-                    t.hdr = dh;
-                    t.tnode = dtn;
-                    t.tslot = tsl;
-                    t.tcoord = tc;
-                    t.node_part_off = npo;
-                    t.part = part;
-                    t.node_major = 1;
-                    t.push = 1;
-                    t.pipe = 1;
-                    t.pipe_nt = (int)gnt;
-                    t.wt_part = E < 4000000ull ? 1 : 0;  // write-through tile partials below 4M tets
-                    t.ntiles = gt.ntiles;
-                    t.ngroups = gt.ngroups;
-                    t.max_tile_nodes = gt.max_tile_nodes;
-                    t.total_tile_nodes = (uint32_t)T;
-                    t.E = (uint32_t)E;
-                    t.pipe_grid = fast_pipe_grid(s);
-                    grouped = true;
-                }
-            }
-        }
-        if (!grouped)
-        {
-        try
-        {
-            // pipelined tiles: 256-thread workgroups over 512-element tiles, or 128 over 256 (128 below 4M
-            // tets: the meshes whose 512-element tiles would give each resident workgroup < 8 tiles)
-            if (t.pipe)
-            {
-                t.pipe_nt = E < 4000000ull ? 128 : 256;
-                t.push = 1;  // the pipelined kernel folds pushed forces (epos), not local-CSR entries
-            }
-            if (hex)
-                build_tiles(d, ht, 2u * (uint32_t)t.hex_nt, (uint32_t)t.hex_nt, 8);
-            else
-                build_tiles(d, ht, t.pipe ? (uint32_t)t.pipe_nt : (uint32_t)kMaxTileNodes,
-                            t.pipe ? 2u * (uint32_t)t.pipe_nt : (uint32_t)kTileElems);
-        }
-        catch (const std::bad_alloc &)
-        {
-            return bail(set_error(h, CWF_ERR_ALLOC, "host allocation failed"));
-        }
-        if (knob("CWF_VERBOSE"))
-            fprintf(stderr, "[cwf] tiles: %u tiles, %zu tile nodes (%.3f per node), max %u nodes/tile, %s records\n",
-                    ht.ntiles, ht.tile_nodes.size(), N ? (double)ht.tile_nodes.size() / (double)N : 0.0,
-                    ht.max_tile_nodes, t.geo ? "8-B geometric" : "48-B gradient");
-        if (t.geo)
-        {
-            uint2 *eid = nullptr;
-            float *tc;
-            if (hex)
-            {
-                uint4 *e8;
-                if (int st = upload(h, &e8, ht.eid8.data(), E))
-                    return bail(st);
-                t.eid8 = e8;
-            }
-            else if (int st = upload(h, &eid, ht.eid.data(), E))
-                return bail(st);
-            const size_t T3 = ht.tile_nodes.size();
-            if (int st = dalloc(h, &tc, 3 * T3))
-                return bail(st);
-            for (int q = 0; q < 3; ++q)
-                HIPTRY(h, hipMemcpy(tc + q * T3, ht.tcoord[q].data(), T3 * sizeof(float), hipMemcpyHostToDevice));
-            t.eid = eid;
-            t.tcoord = tc;
-        }
-        else
-        {
-            uint4 *planes;
-            if (int st = dalloc(h, &planes, 3 * E))
-                return bail(st);
-            for (int q = 0; q < 3; ++q)
-                HIPTRY(h, hipMemcpy(planes + q * E, ht.planes[q].data(), E * sizeof(uint4), hipMemcpyHostToDevice));
-            t.planes = planes;
-        }
-        if (!ht.mat.empty())
-        {
-            uint32_t *tm;
-            if (int st = upload(h, &tm, ht.mat.data(), E))
-                return bail(st);
-            t.mat = tm;
-        }
-        // per-tile header (one scalar dwordx4 load) and 8-B tile-node records {node|owner, csr range};
-        // partials are tile-major (a tile's block is one contiguous store) and the update pass gathers a
-        // node's slots through part_slot
-        std::vector<uint4> hdr(ht.ntiles);
-        std::vector<uint2> tnode(ht.tile_nodes.size());
-        // tet push fold: every node's run of pushed forces starts on an even slot (the fold reads two
-        // {f_x, f_y} pairs with one ds_read_b128 and two f_z with one ds_read_b64) and gets 2 (mod 4)
-        // slots, so the half-start offsets of side-by-side fold lanes are odd multiples apart and spread
-        // over the LDS banks (a uniform stride such as the 24 tets of an interior Kuhn node would put all
-        // lanes on a few banks). A tile whose pads would overflow the kernel's slot budget (4 te + 2 nt)
-        // only rounds to even. The element corners' positions (epos) shift with their node's run.
-        const bool pad_runs = t.push && !hex;
-        const uint32_t slot_budget = 8u * (uint32_t)t.pipe_nt + 2u * (uint32_t)t.pipe_nt;
-        std::vector<uint32_t> shift;
-        for (uint32_t k = 0; k < ht.ntiles; ++k)
-        {
-            const uint32_t e0 = ht.tile_elem_off[k], nb = ht.tile_node_off[k], nb1 = ht.tile_node_off[k + 1];
-            hdr[k] = uint4{e0, ht.tile_elem_off[k + 1] - e0, nb, nb1 - nb};
-            if (hex && !ht.tile_affine.empty() && ht.tile_affine[k])
-                hdr[k].x |= 0x80000000u;  // hex8 tile of parallelepipeds (k_keff_hex_tiles: constant J)
-            shift.assign(nb1 - nb, 0);
-            for (int spread = 1; spread >= 0; --spread)
-            {
-                uint32_t padded = 0;
-                for (uint32_t q = nb; q < nb1; ++q)
-                {
-                    const uint32_t a = ht.csr_off[q] - (uint32_t)K * e0, b = ht.csr_off[q + 1] - (uint32_t)K * e0;
-                    const uint32_t start = pad_runs ? padded : a;
-                    tnode[q] = uint2{ht.tile_nodes[q], start | ((start + b - a) << 16)};
-                    shift[q - nb] = start - a;
-                    uint32_t len = (b - a + 1u) & ~1u;  // even
-                    if (spread && (len / 2u) % 2u == 0u)
-                        len += 2u;  // 2 (mod 4)
-                    padded = start + len;
-                }
-                if (!pad_runs || padded <= slot_budget)
-                    break;
-            }
-            if (pad_runs)
-                for (uint32_t j = e0; j < ht.tile_elem_off[k + 1]; ++j)
-                {
-                    const uint2 id = ht.eid[j];
-                    uint2 &ep = ht.epos[j];
-                    const uint32_t li[4] = {id.x & 0xffffu, id.x >> 16, id.y & 0xffffu, id.y >> 16};
-                    const uint32_t p[4] = {(ep.x & 0xffffu) + shift[li[0]], (ep.x >> 16) + shift[li[1]],
-                                           (ep.y & 0xffffu) + shift[li[2]], (ep.y >> 16) + shift[li[3]]};
-                    ep = uint2{p[0] | (p[1] << 16), p[2] | (p[3] << 16)};
-                }
-        }
-        uint4 *dh;
-        uint2 *dtn;
-        uint32_t *npo;
-        uint16_t *ce;
-        float *part;
-        if (int st = upload(h, &dh, hdr.data(), hdr.size()))
-            return bail(st);
-        if (int st = upload(h, &dtn, tnode.data(), tnode.size()))
-            return bail(st);
-        ht.csr_ent.resize(ht.csr_ent.size() + 8, 0);  // the pipelined kernel reads a tile's entries as 16-B words
-        ce = nullptr;
-        if (!t.push)  // PUSH streams the per-element positions (epos) instead
-            if (int st = upload(h, &ce, ht.csr_ent.data(), ht.csr_ent.size()))
-                return bail(st);
-        // the update pass reads each node's partial range anyway: the Dirichlet mask rides in its top bits
-        // (one 4-B stream less per PCG iteration) when the offsets leave them free
-        if (ht.node_part_off.back() <= kPartOffBits)
-        {
-            for (uint64_t n = 0; n < N; ++n)
-                ht.node_part_off[n] |= (d->bc_mask[n] & 7u) << 29;
-            t.off_mask = 1;
-        }
-        if (int st = upload(h, &npo, ht.node_part_off.data(), ht.node_part_off.size()))
-            return bail(st);
-        uint32_t *ps;
-        if (int st = upload(h, &ps, ht.node_part_slot.data(), ht.node_part_slot.size()))
-            return bail(st);
-        t.part_slot = ps;
-        if (t.push && hex)
-        {
-            uint4 *ep;
-            if (int st = upload(h, &ep, ht.epos8.data(), ht.epos8.size()))
-                return bail(st);
-            t.epos8 = ep;
-        }
-        else if (t.push)
-        {
-            uint2 *ep;
-            if (int st = upload(h, &ep, ht.epos.data(), ht.epos.size()))
-                return bail(st);
-            t.epos = ep;
-        }
-        if (t.pipe || t.hex)
-        {
-            uint32_t *tsl;
-            if (int st = upload(h, &tsl, ht.tile_slot.data(), ht.tile_slot.size()))
-                return bail(st);
-            t.tslot = tsl;
-            t.node_major = 1;
-        }
-        if (int st = dalloc(h, &part, 3 * (ht.tile_nodes.size() + 2)))  // + 2 padding slots (update pass)
-            return bail(st);
-        t.ntiles = ht.ntiles;
-        t.hex_all_affine = hex && !ht.tile_affine.empty() &&
-                           std::all_of(ht.tile_affine.begin(), ht.tile_affine.end(), [](uint8_t a) { return a != 0; });
-        t.max_tile_nodes = ht.max_tile_nodes;
-        t.total_tile_nodes = (uint32_t)ht.tile_nodes.size();
-        t.E = (uint32_t)E;
-        t.hdr = dh;
-        t.tnode = dtn;
-        t.csr_ent = ce;
-        t.node_part_off = npo;
-        t.part = part;
-        if (t.pipe || t.hex)
-            t.pipe_grid = fast_pipe_grid(s);
-        }  // !grouped
-    }
-    if (hex)  // the hex block-Jacobi setup integrates from the global corners (fp64)
-    {
-        uint32_t *hc;
-        double *hx;
-        std::vector<uint32_t> conn(E * 8);
-        std::memcpy(conn.data(), d->element_connectivity, E * 8 * sizeof(uint32_t));
-        if (int st = upload(h, &hc, conn.data(), E * 8))
-            return bail(st);
-        if (int st = upload(h, &hx, d->node_coords, 3 * N))
-            return bail(st);
-        float *hg;
-        if (int st = upload(h, &hg, d->element_gradients, 24 * E))
-            return bail(st);
-        s.hconn = hc;
-        s.hcoord = hx;
-        s.hgrad = hg;
-    }
-    // solver scratch
-    const uint64_t D = 3 * N;
-    for (float **v : {&h->x, &h->r, &h->p, &h->p2, &h->p3, &h->p4, &h->z, &h->Ap, &h->rhs, &h->tmp})
-        if (int st = dalloc(h, v, D))
-            return bail(st);
-    if (s.t.lat && s.t.lcls)  // the fused lattice iteration's second r / Ap and its shares (lattice_fused.inc)
-    {
-        if (int st = dalloc(h, &h->r2, D))
-            return bail(st);
-        if (int st = dalloc(h, &h->ap2, D))
-            return bail(st);
-        if (int st = dalloc(h, &h->fsh, 2ull * 5 * std::max<uint32_t>(s.t.lnwork, 1u)))
-            return bail(st);
-        if (int st = dalloc(h, &h->g_fsh, 8))  // one rank until attach (comm.cpp grows it to [nranks][8])
+        int st = open_handle(d, device, hp);
+        cwf_hip_system *h = hp.get();
+        st = st ? st : upload_mesh_arrays(h, d);
+        st = st ? st : upload_incidence(h, d);
+        if (!st && pc.path == FastPath::Lattice)
+            st = layout_lattice(h, d, lat);
+        if (!st && pc.path == FastPath::Groups)
+            st = layout_groups(h, d);
+        // a mesh that was to group into fans and does not takes the pipelined per-tet tiles
+        if (!st && pc.path != FastPath::None && pc.path != FastPath::Lattice && !h->ds.t.grp)
+            st = layout_tiles(h, d, pc.path == FastPath::Groups ? FastPath::TilesPipe : pc.path, geo_ok);
+        if (!st && hex)
+            st = upload_hex_jacobi(h, d);
+        st = st ? st : alloc_scratch(h, d, renumber ? &rd.perm : nullptr);
+        if (st)
             return bail(st);
     }
-    if (int st = dalloc(h, &h->inv, 9 * N))
-        return bail(st);
-    if (int st = dalloc(h, &h->inv6, 4 * N))
-        return bail(st);
-    const uint64_t chunks = (D + d->reduction_block - 1) / d->reduction_block;
-    h->part_cap = std::max<uint64_t>(
-        {chunks, (uint64_t)fast_block_count(h), (uint64_t)fast_dot_blocks(s.D), (uint64_t)s.t.ntiles,
-         (uint64_t)s.t.pipe_grid, 1});
-    if (int st = dalloc(h, &h->part0, h->part_cap))
-        return bail(st);
-    if (int st = dalloc(h, &h->part1, h->part_cap))
-        return bail(st);
-    if (int st = dalloc(h, &h->part2, h->part_cap))
-        return bail(st);
-    if (int st = dalloc(h, &h->ctl, 1))
-        return bail(st);
-    if (int st = dalloc(h, &h->scal, 8))
-        return bail(st);
-    // folded per-rank scalars (one rank until cwf_hip_system_attach): p.Ap, {r.r, r.z}, {rhs.rhs, r0.r0}, r0.z0
-    if (int st = dalloc(h, &h->g_pap, 6))
-        return bail(st);
-    h->g_rrz = h->g_pap + 1;
-    h->g_init = h->g_rrz + 2;
-    h->g_rz0 = h->g_init + 2;
-    if (renumber)
+    catch (const std::bad_alloc &)
     {
-        if (int st = upload(h, &h->perm, r_perm.data(), N))
-            return bail(st);
-        if (int st = dalloc(h, &h->pbuf, 13 * N))
-            return bail(st);
+        return bail(set_error(hp.get(), CWF_ERR_ALLOC, "host allocation failed"));
     }
-    if (h->mode == CWF_MODE_PARITY)
-        if (int st = parity_force_buffer(h))
-            return bail(st);
-    HIPTRY(h, hipMemset(h->x, 0, D * sizeof(float)));
-    HIPTRY(h, hipMemset(h->ctl, 0, sizeof(Ctl)));
-    HIPTRY(h, hipMemset(h->g_pap, 0, 6 * sizeof(double)));
-    HIPTRY(h, hipDeviceSynchronize());
-    *out = h;
+    *out = hp.release();
     return 0;
 }
 

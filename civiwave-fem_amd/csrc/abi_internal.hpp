@@ -1,11 +1,13 @@
 // abi_internal.hpp -- what the C-ABI translation units (abi.cpp: handles, abi_pcg.cpp: apply_keff / block
 // Jacobi / dot / solve_pcg, abi_stepper.cpp: the Stepper) share: the HIP error macro, device allocation and
-// upload, vector staging between the caller's layout and the handle's, and the PCG driver.
+// upload, vector staging between the caller's layout and the handle's, the PCG driver, and the host-only pieces
+// of cwf_hip_system_create (abi.cpp, tiles.cpp, lattice.cpp; tests/cpp/create_host_test.cpp calls them).
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -39,6 +41,15 @@ template <class T> inline int dalloc(cwf_hip_system *h, T **p, size_t count)
 
 // the Dirichlet mask can ride in node_part_off's top bits when the offsets leave them free
 inline bool ht_off_mask_ok(const std::vector<uint32_t> &npo) { return npo.back() <= cwf::kPartOffBits; }
+// ... and then does (the update pass reads the offsets anyway: one 4-B stream less). Returns DevTiles::off_mask
+inline int pack_off_mask(std::vector<uint32_t> &npo, const uint32_t *bc_mask, uint64_t N)
+{
+    if (!ht_off_mask_ok(npo))
+        return 0;
+    for (uint64_t n = 0; n < N; ++n)
+        npo[n] |= (bc_mask[n] & 7u) << 29;
+    return 1;
+}
 
 template <class T> inline int upload(cwf_hip_system *h, T **dst, const T *src, size_t count)
 {
@@ -49,6 +60,87 @@ template <class T> inline int upload(cwf_hip_system *h, T **dst, const T *src, s
     return 0;
 }
 
+// A create stage's device allocations and uploads: the first failure is kept in st (the message is on the
+// handle) and every later call does nothing, so a stage checks st once, before it uses the pointers.
+struct Uploader
+{
+    cwf_hip_system *h;
+    int st = 0;
+    int check(hipError_t e, const char *what) { return !st && e != hipSuccess ? st = hip_fail(h, e, what) : st; }
+    template <class T> T *alloc(size_t count)
+    {
+        T *p = nullptr;
+        st = st ? st : dalloc(h, &p, count);
+        return p;
+    }
+    template <class T> T *zeros(size_t count)
+    {
+        T *p = alloc<T>(count);
+        check(st ? hipSuccess : hipMemset(p, 0, count * sizeof(T)), "hipMemset");
+        return p;
+    }
+    template <class T> T *put(const T *src, size_t count)
+    {
+        T *p = nullptr;
+        st = st ? st : upload(h, &p, src, count);
+        return p;
+    }
+    template <class T> T *put(const std::vector<T> &v) { return put(v.data(), v.size()); }
+    // three host planes of n entries each into one device array [3][n]
+    template <class T> T *put3(const std::vector<T> (&v)[3], size_t n)
+    {
+        T *p = alloc<T>(3 * n);
+        for (int q = 0; q < 3 && !st; ++q)
+            check(hipMemcpy(p + q * n, v[q].data(), n * sizeof(T), hipMemcpyHostToDevice), "hipMemcpy");
+        return p;
+    }
+};
+
+// cwf_hip_system_create holds the handle in one of these from allocation to *out = h: every failing exit
+// destroys the stream, the pinned block and the device buffers uploaded so far
+using HandlePtr = std::unique_ptr<cwf_hip_system, decltype(&cwf_hip_system_destroy)>;
+
+// The FAST K_eff path of a desc with elements (choose_fast_path, abi.cpp). Groups is a wish: a mesh that does not
+// group into fans (fan_groups_usable) takes TilesPipe instead.
+enum class FastPath
+{
+    None,       // no elements
+    Lattice,    // k_keff_lattice / k_pcg_lattice / k_pcg_resident: structured blocks (lattice.cpp)
+    Groups,     // k_keff_groups_pipe: tet fan groups (groups.cpp)
+    TilesPipe,  // k_keff_tiles_pipe: per-tet 8-B geometric records, pipelined
+    Tiles,      // k_keff_tiles: one tile per workgroup (48-B records, or 8-B ones under CWF_TILE_PIPE=0)
+    HexTiles,   // k_keff_hex_tiles
+};
+struct PathChoice
+{
+    FastPath path;
+    bool owner_renumber;  // a handle that renumbers orders its nodes by (owner tile, Morton), not Morton alone
+};
+PathChoice choose_fast_path(const cwf_system_desc *d, bool is_lat, bool geo_ok);
+bool groups_enabled();
+uint32_t group_lanes();
+inline bool fan_groups_usable(int status, const GroupTiles &gt) { return status == 0 && gt.tets_per_group >= 3.0; }
+
+// tiles.cpp: the device records of the per-tet / hex tiles. pad_runs (the tet push fold) moves ht.epos with the runs
+struct TileRecords
+{
+    std::vector<uint4> hdr;    // [ntiles] {first element | affine bit 31, #elements, first tile node, #nodes}
+    std::vector<uint2> tnode;  // [total] {node | owner bit 31, run begin | run end << 16}
+};
+TileRecords pack_tile_records(HostTiles &ht, int corners, bool pad_runs, uint32_t slot_budget);
+
+// lattice.cpp: what the lattice layout uploads besides the Lattice itself
+std::vector<float> lattice_device_coef(const Lattice &lat);
+struct LatticeClasses
+{
+    std::vector<uint8_t> cls;   // [N] boundary type << 3 | Dirichlet mask
+    std::vector<uint32_t> rep;  // [kLatClasses] lowest node of the class, 0xFFFFFFFF: none
+    bool uniform = true;        // the lumped mass is a function of the boundary type (else cls / rep are partial)
+    bool interior = false;      // a node inside along x, y and z exists; interior_mass is its lumped mass
+    float interior_mass = 0.f;
+};
+LatticeClasses lattice_classes(const Lattice &lat, const uint32_t *bc_mask, const float *lumped_mass);
+
 bool iso_pattern(const double *D);
 int parity_incidence_slots(cwf_hip_system *h);
 int parity_force_buffer(cwf_hip_system *h);
@@ -58,8 +150,6 @@ int stage_vec(cwf_hip_system *h, const float *src, float *scratch, int kind, int
 int vec_in(cwf_hip_system *h, const float *src, float *dst, int kind, int w);
 int vec_out(cwf_hip_system *h, const float *src, float *dst, int kind, int w);
 std::vector<uint32_t> morton_node_order(const double *X, uint64_t N);
-bool groups_enabled();
-uint32_t group_lanes(uint64_t E);
 std::string pcg_error_message(int code, int iter, std::string *ctx);
 // solve_pcg on device buffers for a group (one handle, or every rank of a LOCAL sharded system)
 int run_pcg_group(const std::vector<cwf_hip_system *> &g, const std::vector<const float *> &rhs,

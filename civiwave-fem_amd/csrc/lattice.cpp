@@ -24,7 +24,7 @@
 #include <cmath>
 #include <cstring>
 
-#include "cwf_internal.hpp"
+#include "abi_internal.hpp"
 
 namespace cwf
 {
@@ -480,6 +480,54 @@ void lattice_plan(DevTiles &t)
                               (nhi + kLatThreads - 1) / kLatThreads);
     }
     t.ntiles = t.lnwork;
+}
+
+// The device copy's stencil blocks are stored row-pair interleaved for the packed rows of k_keff_lattice: per
+// offset {S00 S10 S01 S11 S02 S12 S20 S21 S22}; the cell-pair blocks after them keep row-major order
+std::vector<float> lattice_device_coef(const Lattice &lat)
+{
+    std::vector<float> cdev(lat.coef, lat.coef + (lat.hex ? kLatHexCoef : kLatCoef));
+    for (int o = 0; o < (lat.hex ? kLatHexOffsets : kLatOffsets); ++o)
+        for (int c = 0; c < 3; ++c)
+        {
+            cdev[9 * o + 2 * c] = lat.coef[9 * o + c];
+            cdev[9 * o + 2 * c + 1] = lat.coef[9 * o + 3 + c];
+            cdev[9 * o + 6 + c] = lat.coef[9 * o + 6 + c];
+        }
+    return cdev;
+}
+
+// Per-class preconditioner (the update pass reads one byte per node instead of the 16-B record and the
+// partial-run bounds) when the lumped mass is a function of the boundary type
+LatticeClasses lattice_classes(const Lattice &lat, const uint32_t *bc_mask, const float *lumped_mass)
+{
+    LatticeClasses lc;
+    lc.cls.resize((size_t)lat.nx * lat.ny * lat.nz);
+    lc.rep.assign(kLatClasses, 0xFFFFFFFFu);
+    float tmass[27] = {};
+    bool tseen[27] = {};
+    for (uint32_t k = 0; k < lat.nz && lc.uniform; ++k)
+        for (uint32_t j = 0; j < lat.ny; ++j)
+            for (uint32_t i = 0; i < lat.nx; ++i)
+            {
+                const uint32_t n = lat.plane[k] + j * lat.nx + i;
+                const auto side = [](uint32_t a, uint32_t na) { return a == 0 ? 0u : a + 1 == na ? 2u : 1u; };
+                const uint32_t ty = side(i, lat.nx) + 3 * side(j, lat.ny) + 9 * side(k, lat.nz);
+                const uint32_t c = ty << 3 | (bc_mask[n] & 7u);
+                lc.cls[n] = (uint8_t)c;
+                if (lc.rep[c] == 0xFFFFFFFFu || n < lc.rep[c])
+                    lc.rep[c] = n;
+                if (!tseen[ty])
+                {
+                    tseen[ty] = true;
+                    tmass[ty] = lumped_mass[n];
+                }
+                else if (std::memcmp(&tmass[ty], &lumped_mass[n], sizeof(float)) != 0)
+                    lc.uniform = false;
+            }
+    lc.interior = tseen[13];  // type 13: inside along x, y and z (the bricks' nodes)
+    lc.interior_mass = tmass[13];
+    return lc;
 }
 
 }  // namespace cwf

@@ -22,7 +22,7 @@
 #include <string>
 #include <vector>
 
-#include "cwf_internal.hpp"
+#include "abi_internal.hpp"
 
 namespace cwf
 {
@@ -364,6 +364,59 @@ int build_tiles(const cwf_system_desc *d, HostTiles &out, uint32_t max_nodes, ui
         if (out.node_part_off[n + 1] > out.node_part_off[n])
             out.tile_nodes[out.node_part_slot[out.node_part_off[n]]] |= 0x80000000u;
     return 0;
+}
+
+// Per-tile header (one scalar dwordx4 load) and 8-B tile-node records {node|owner, csr range}; partials are
+// tile-major (one contiguous store per tile) and the update pass gathers a node's slots through part_slot.
+// pad_runs, the tet push fold: every node's run of pushed forces starts on an even slot (the fold reads two
+// {f_x, f_y} pairs with one ds_read_b128 and two f_z with one ds_read_b64) and gets 2 (mod 4) slots, so the
+// half-start offsets of side-by-side fold lanes are odd multiples apart and spread over the LDS banks (a uniform
+// stride such as the 24 tets of an interior Kuhn node would put all lanes on a few banks). A tile whose pads
+// would overflow the kernel's slot budget (4 te + 2 nt) only rounds to even. The element corners' positions
+// (epos) shift with their node's run.
+TileRecords pack_tile_records(HostTiles &ht, int corners, bool pad_runs, uint32_t slot_budget)
+{
+    const uint32_t K = (uint32_t)corners;
+    TileRecords r;
+    r.hdr.resize(ht.ntiles);
+    r.tnode.resize(ht.tile_nodes.size());
+    std::vector<uint32_t> shift;
+    for (uint32_t k = 0; k < ht.ntiles; ++k)
+    {
+        const uint32_t e0 = ht.tile_elem_off[k], nb = ht.tile_node_off[k], nb1 = ht.tile_node_off[k + 1];
+        r.hdr[k] = uint4{e0, ht.tile_elem_off[k + 1] - e0, nb, nb1 - nb};
+        if (K == 8 && !ht.tile_affine.empty() && ht.tile_affine[k])
+            r.hdr[k].x |= 0x80000000u;  // hex8 tile of parallelepipeds (k_keff_hex_tiles: constant J)
+        shift.assign(nb1 - nb, 0);
+        for (int spread = 1; spread >= 0; --spread)
+        {
+            uint32_t padded = 0;
+            for (uint32_t q = nb; q < nb1; ++q)
+            {
+                const uint32_t a = ht.csr_off[q] - K * e0, b = ht.csr_off[q + 1] - K * e0;
+                const uint32_t start = pad_runs ? padded : a;
+                r.tnode[q] = uint2{ht.tile_nodes[q], start | ((start + b - a) << 16)};
+                shift[q - nb] = start - a;
+                uint32_t len = (b - a + 1u) & ~1u;  // even
+                if (spread && (len / 2u) % 2u == 0u)
+                    len += 2u;  // 2 (mod 4)
+                padded = start + len;
+            }
+            if (!pad_runs || padded <= slot_budget)
+                break;
+        }
+        if (pad_runs)
+            for (uint32_t j = e0; j < ht.tile_elem_off[k + 1]; ++j)
+            {
+                const uint2 id = ht.eid[j];
+                uint2 &ep = ht.epos[j];
+                const uint32_t li[4] = {id.x & 0xffffu, id.x >> 16, id.y & 0xffffu, id.y >> 16};
+                const uint32_t p[4] = {(ep.x & 0xffffu) + shift[li[0]], (ep.x >> 16) + shift[li[1]],
+                                       (ep.y & 0xffffu) + shift[li[2]], (ep.y >> 16) + shift[li[3]]};
+                ep = uint2{p[0] | (p[1] << 16), p[2] | (p[3] << 16)};
+            }
+    }
+    return r;
 }
 
 bool geometry_matches(const cwf_system_desc *d)

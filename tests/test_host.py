@@ -90,6 +90,25 @@ def _build_cpp_test(tmp_path):
     return exe
 
 
+def test_create_host_pieces(tmp_path):
+    """tests/cpp/create_host_test.cpp: the FAST path choice, the push-run padding and the lattice class table of
+    cwf_hip_system_create, called through abi_internal.hpp on descs the program builds (no GPU call). Host g++
+    compiles the internal headers with -D__HIP_PLATFORM_AMD__; every knob is unset for the run."""
+    import subprocess
+    import os
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    libdir = os.path.join(root, "civiwave-fem_amd", "lib")
+    exe = str(tmp_path / "create_host_test")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
+                    "-I" + os.path.join(root, "civiwave-fem_amd", "csrc"),
+                    os.path.join(root, "tests", "cpp", "create_host_test.cpp"), "-o", exe, f"-L{libdir}", "-lcwf_hip",
+                    f"-Wl,-rpath,{libdir}"], check=True)
+    env = {k: v for k, v in os.environ.items() if not k.startswith("CWF_")}
+    out = subprocess.run([exe], env=env, check=True, capture_output=True, text=True)
+    assert out.stdout.strip() == "ok"
+
+
 def test_cpp_mirror_header_compiles_and_links(tmp_path):
     """include/cwf_hip.hpp (C++ mirror of cwf::gpu::pcg / Stepper) builds with the image's g++."""
     assert _build_cpp_test(tmp_path)
