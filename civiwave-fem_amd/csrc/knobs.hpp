@@ -42,6 +42,8 @@ inline constexpr Knob kKnobs[] = {
     {"CWF_FUSED_TRACE", "path (ablation build only): per-workgroup phase stamps of one fused launch per solve, appended"},
     {"CWF_RESIDENT_TRACE", "path: per-workgroup phase stamps of one phase (CWF_FUSED_TRACE_IT) of every resident solve, "
                            "appended (tools/resident_trace.py)"},
+    {"CWF_RESIDENT_REREAD", "1: every phase of the resident solve takes its first ring vote as failed once, so every ring "
+                            "granule is requested and formed twice (tests/test_gpu_resident_handoff.py: same bits)"},
     {"CWF_FUSED_TRACE_IT", "n: the iteration whose launch CWF_FUSED_TRACE records (default 50)"},
     {"CWF_FUSED_MAXWG", "n: cap on the fused launch's grid (default 1024 workgroups; a grid below the work items walks them persistently)"},
     {"CWF_XLAG", "1..4: iterations per lazy x update (tests/test_gpu_parity.py compares 4 with 1)"},

@@ -1,14 +1,16 @@
 // resident.cpp -- the plan of the resident solve (resident.hip): the structured block cut into one box per workgroup
 // (at most one per CU, so the persistent grid is co-resident), each box's node list (the thread -> node map its
 // registers keep for the whole solve), its halo list (the one-node ring its rows read, each entry pointing at the
-// owner's published record) and the publication index of every node some other box reads.
+// owner's published Ap granule) and the publication index of every node some other box reads.
 //
 // Box choice: every factorisation gx * gy * gz <= CUs of the node lattice, boxes of ceil(n / g) nodes per axis at most,
-// scored by the per-workgroup work of a phase (own nodes + 1.5 x halo entries, each halo entry being three 16-B
-// loads and a formed p) plus a barrier term growing with the grid (2 per workgroup); the image (box + ring, float4)
+// scored by the per-workgroup work of a phase (own nodes + 1.5 x halo entries, each halo entry being one 16-B
+// load and a formed r and p; the weight dates from three loads and is kept: the plan is not re-tuned) plus a barrier
+// term growing with the grid (2 per workgroup); the image (box + ring, float4)
 // must fit the LDS beside the static tables and the lists the kernel's 4 + 3 entries per thread. C2 (70^3 nodes): 5 x 7 x 7 boxes of
 // 14 x 10 x 10 nodes, 245 workgroups.
 #include <algorithm>
+#include <cstdio>
 #include <cstring>
 
 #include "abi_internal.hpp"
@@ -22,7 +24,8 @@ constexpr unsigned kResThreads = 512, kResOwn = 4 * kResThreads, kResHalo = 3 * 
 // entries' r, Ap, x in the 4-node instantiation: 72 KB; the class table; the box's boundary types' stencils, at
 // most kResTypesHost of the 27: 8.6 KB with the 15-offset Kuhn stencil, 15.6 KB with the 27-offset hex8 one)
 constexpr unsigned kResTypesHost = 12;  // resident.hip kResTypes
-constexpr unsigned kResGhostHost = 512;  // resident.hip kResGhostMax: a shard box's ghost halo entries (their r, p in LDS)
+constexpr unsigned kResGhostHost = 512;  // a shard box's ghost halo entries, at most (the kernel kept their r, p in LDS
+                                         // once; it no longer needs the cap, the accepted plans stay what they were)
 constexpr uint32_t kNone = 0xFFFFFFFFu;
 constexpr uint32_t kResGhost = 0x80000000u;  // a halo entry's source: a ghost record (resident.hip)
 constexpr unsigned kFusedSharesHost = 5;  // kFusedShares (lattice_common.hpp): one 16-B granule each
@@ -226,7 +229,7 @@ bool plan_resident(cwf_hip_system *h, bool shard)
         std::sort(halol[b].begin(), halol[b].end(), [](const uint4 &a, const uint4 &c) { return a.z < c.z; });
         max_halo = std::max<unsigned>(max_halo, (unsigned)halol[b].size());
         halo_total += halol[b].size();
-        // the ghost entries are the list's tail: the first one's position (the kernel's index into its ghost state)
+        // the ghost entries are the list's tail: the first one's position
         const auto g0 = std::find_if(halol[b].begin(), halol[b].end(), [](const uint4 &e) { return (e.z & kResGhost) != 0; });
         const uint64_t ng = (uint64_t)(halol[b].end() - g0);
         if (ng > kResGhostHost)
@@ -325,6 +328,9 @@ bool plan_resident(cwf_hip_system *h, bool shard)
     uint4 *dh, *dow, *dha;
     float *dpub;
     double *dsh;
+    // pub: the kernel uses [2][npub][4] floats (one {Ap, tag} granule per published node and parity), the front third of
+    // this allocation. Its size, and resident_offchip_bytes below, stay those of the three-granule record: both are
+    // handle counters that tests/golden/create_layout.json pins (tests/test_gpu_create_paths.py)
     if (upload(h, &dh, hdr.data(), hdr.size()) || upload(h, &dow, own.data(), own.size()) ||
         upload(h, &dha, halo.data(), halo.size()) || dalloc(h, &dpub, 2ull * 12 * std::max<uint32_t>(npub, 1u)) ||
         dalloc(h, &dsh, 2ull * 2 * kFusedSharesHost * G))
@@ -358,6 +364,9 @@ bool plan_resident(cwf_hip_system *h, bool shard)
     rp.remote_sends = remote_sends;
     rp.ghost_total = ghost_total;
     rp.state = 1;
+    if (knob("CWF_VERBOSE"))
+        fprintf(stderr, "[cwf] resident plan: %u boxes (%u x %u x %u), max_own %u, max_halo %u, %u published nodes\n", G,
+                bg[0], bg[1], bg[2], max_own, max_halo, npub);
     return true;
 }
 
@@ -403,8 +412,12 @@ bool resident_on(const cwf_hip_system *h)
 uint64_t resident_offchip_bytes(const cwf_hip_system *h)
 {
     const ResidentPlan &rp = h->res;
-    // 48-B records on chip (read by the ring entries, written by the published nodes); a shard's ghost entries read,
-    // and its send-plane nodes write, one 16-B Ap granule
+    // The pinned model (tests/golden/create_layout.json): 48-B records read by the on-chip ring entries and written by
+    // the published nodes, one 16-B Ap granule per ghost entry and per send-plane node. The kernel now moves 16 B per
+    // ring entry and per published node, so on one handle this OVERSTATES the bytes moved by
+    // 32 * (halo_total + npub) per iteration (C2: 19.38 MB reported, 9.67 MB moved), and with
+    // them bench.py's algorithmic_bytes_per_launch, achieved GB/s and frac. The measured traffic (PMC) is the figure
+    // to read until the golden is regenerated by a change that may touch it
     uint64_t b = 48ull * (rp.halo_total - rp.ghost_total + rp.npub) + 16ull * (rp.ghost_total + rp.remote_sends) +
                  80ull * rp.G * (1ull + rp.G);
     if (rp.shard)  // the rank totals: one rank's stores to every rank, every workgroup's poll of all of them

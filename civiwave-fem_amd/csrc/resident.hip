@@ -7,20 +7,36 @@
 // 0.23 of HBM; VERDICT r5 items 2 and the C3 / 8 strong-scaling bound). A block of up to ~0.5M nodes fits on chip:
 // 256 CUs x 160 KB of LDS and 512 KB of VGPRs hold C2's 16.5 MB of r, Ap, p, x many times over. So the solve becomes
 // one persistent launch of one 512-thread workgroup per CU, each owning a box of the lattice:
-//   - its nodes' r, Ap, p, x, z, class and mass live in registers (NPT nodes per thread) for the whole solve;
+//   - its nodes' r, Ap, p, x, class and mass live on chip (registers, or LDS in the 4-node instantiation) for the
+//     whole solve;
 //   - per iteration (phase j) it forms r_j, z_j, p_j, x_j exactly as lattice_fused.inc's launch j does (fused_form),
-//     writes p_j into an LDS image of the box plus its one-node halo, applies the stencil rows (interior nodes: the
-//     brick rows' difference form; block-surface nodes: the shell's cell form), and leaves the five fp64 dots;
-//   - the halo's p_j is formed locally from the owners' published (r_(j-1), Ap_(j-1), p_(j-1)) -- the same bits the
-//     owner forms -- so ONE synchronisation per iteration carries both the halo and the scalars: each workgroup stores
-//     its box-surface records and its five shares write-through (sc1), waits for its stores, and adds one to an
-//     arrival counter; the next phase polls the counter (sc1) until every workgroup arrived, reads the G x 5 shares
-//     and its halo records (sc1: served past the non-coherent L1 / per-XCD L2), folds the shares in a fixed order
-//     (so every workgroup takes the same alpha, beta and stop decision, fused_decide) and goes on.
-// The hand-off is MI355X_MICROARCH.md's validated form (sc1 16-B stores, every storing wave's vmcnt(0) before one
-// lane's agent-scope add after a workgroup barrier; one lane's sc1 poll, a workgroup barrier, then sc1 16-B loads).
-// Every wait is bounded (kResTimeoutTicks): a workgroup that is never scheduled (the grid must be co-resident, one per
-// CU; resident_capacity checks the occupancy) ends the solve with CWF_ERR_HIP instead of hanging the GPU.
+//     writes p_j into an LDS image of the box plus its one-node ring, applies the stencil rows (interior nodes: the
+//     brick rows' difference form; block-surface nodes: the shell's cell form), and leaves the five fp64 dots.
+// The hand-off between boxes is tagged 16-B granules, one synchronisation per iteration, no counter:
+//   - published: per box-surface node that another box reads, ONE granule {Ap_j.xyz, tag} per phase (pub, by phase
+//     parity), and per workgroup five share granules {dot lo, hi, tag, -} (sh). The tag is tag0 + j + 1: a granule of
+//     another phase or of an earlier solve never matches. Every granule is one write-through (sc1) 16-B store; the
+//     node granules are stored in the rows, the shares last;
+//   - kept by the consumer: r_(j-1) and p_(j-1) of each ring entry, in the registers of the thread that has the entry
+//     (hr, hp), for the whole solve. Phase 0 takes r_0 from fast_fused_init's r vector and p = Ap = 0, as the owner
+//     does; phase j forms r_j = r_(j-1) - alpha Ap_(j-1), z_j, p_j = z_j + beta p_(j-1) with fused_form from the kept
+//     values, the loaded Ap_(j-1) and the node's class. The owner runs the same function on the same bits with the same
+//     alpha and beta (every workgroup folds the same shares in the same order, fused_decide), so both sides hold the
+//     same r_j and p_j bit for bit and neither ever has to be sent. A shard's ghost entries are ring entries like any
+//     other: only the source of their Ap granule differs (the PEER mailbox, system scope);
+//   - a phase polls (sc1 loads, served past the non-coherent L1 / per-XCD L2) the G x 5 shares until all carry phase
+//     j - 1's tag, requests its ring's Ap granules, folds the shares, forms its own nodes, then checks each ring
+//     granule's tag under a workgroup vote; granules that had not landed are requested again. The vote can fail, so
+//     the ring check can run more than once per phase: every pass forms from the OLD kept values into temporaries
+//     (hrn, hpn), and they replace the kept ones only after the vote has passed. Updating in place would apply alpha
+//     twice to the entries that had landed on a pass another entry failed (CWF_RESIDENT_REREAD forces a second pass:
+//     tests/test_gpu_resident_handoff.py);
+//   - this rests on a 16-B store being seen whole or not at all by a 16-B load of the same aligned address (value and
+//     tag travel in one granule, so no ordering between granules is needed): observed on gfx950 for the dwordx4
+//     buffer accesses used here, not an architectural guarantee (DESIGN.md section 7 states the same for the mailboxes).
+// Every wait is bounded (kResMaxRounds poll rounds, then give_up): a workgroup that is never scheduled (the grid must be
+// co-resident, one per CU; resident_blocks_per_cu checks the occupancy) ends the solve with CWF_ERR_HIP instead of
+// hanging the GPU.
 //
 // Results: the per-node arithmetic is lattice_fused.inc's; only the grouping of the fp64 dot sums differs (boxes
 // instead of bricks), so alpha / beta differ in their last bits and the solve is tolerance-equal, not bit-equal, to the
@@ -44,22 +60,21 @@ constexpr uint32_t kResNone = 0xFFFFFFFFu;
 constexpr uint32_t kResOob = 0xFFFFFF00u;  // a byte offset past every range-checked buffer here, +32 included (no wrap)
 constexpr uint32_t kResGhost = 0x80000000u;  // a halo entry's source: a shard's ghost record (resident.cpp)
 constexpr int kResTypes = 12;  // boundary types one box's own nodes touch, at most (resident.cpp kResTypesHost)
-constexpr int kResGhostMax = 512;  // a shard box's ghost halo entries, at most (resident.cpp kResGhostHost)
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 struct ResArgs
 {
     Ctl *ctl;
     double *hist;
-    const uint4 *hdr;   // [G] {LDS slots, first ghost halo entry (a shard), PX, PXY}: the box's (sx + 2)(sy + 2)(sz + 2)
-                        // image and its strides
+    const uint4 *hdr;   // [G] {LDS slots, - (the plan's first ghost halo entry: unused here), PX, PXY}: the box's
+                        // (sx + 2)(sy + 2)(sz + 2) image and its strides
     const uint4 *own;   // [G][own_stride] {node, image slot, publication index or kResNone, -}
     const uint4 *halo;  // [G][halo_stride] {node, slot, publication index of its owner's record, -}
     const float4 *tcoef;  // the stencil of each boundary type (the block-surface rows), padded blocks: [27][nOff][3]
                           // for the register-state instantiation; for the LDS-state one [G][kResTypes][nOff][3], per
                           // box only the types its nodes have (the own entry's y >> 24 is the node's index there)
     uint32_t own_stride, halo_stride;
-    float *pub;         // [2][npub][12] by phase parity: granules {r.xyz, tag} {Ap.xyz, tag} {p.xyz, tag}
+    float *pub;         // [2][npub][4] by phase parity: one granule {Ap.xyz, tag} per published node
     uint32_t npub;
     double *sh;         // [2][G][5] granules {share lo, hi, tag, -} by phase parity
     uint32_t tag0;      // this solve's tag base: phase j's granules carry tag0 + j + 1 (a previous solve's never match)
@@ -67,8 +82,9 @@ struct ResArgs
     uint32_t max_it;
     uint64_t *trace;    // diagnostic (CWF_RESIDENT_TRACE): per workgroup 8 s_memrealtime stamps of phase trace_j
     uint32_t trace_j;
-    // a PEER slab shard (nranks > 1): the send planes' Ap_(j-1) granules stored into the neighbours' mailboxes (a ghost's
-    // r and p the receiving box forms itself and keeps, exactly as the owner does), the ghosts' granules read from this
+    uint32_t reread;    // test (CWF_RESIDENT_REREAD): every phase j > 0 takes its first ring vote as failed once
+    // a PEER slab shard (nranks > 1): the send planes' Ap_(j-1) granules stored into the neighbours' mailboxes too (a
+    // ghost is a ring entry like any other, only its granule's source differs), the ghosts' granules read from this
     // rank's, the rank totals stored to every rank and polled from this rank's
     ResPeerArgs pa;
 };
@@ -140,7 +156,6 @@ __global__ __launch_bounds__(kResNT) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     __shared__ float4 tcf[kTT * E::nOff * 3];  // the boundary types' stencils (not the interior's)
     __shared__ int vote[3];  // the poll rounds' workgroup vote, by round mod 3
     __shared__ double rt[MR ? kFusedShares * kMaxPeers : 1];  // a shard: the ranks' totals, folded in rank order
-    __shared__ float4 gst[MR ? 2 * kResGhostMax : 1];  // a shard: each ghost entry's r_j, p_j ({r, -} {p, -})
     // the own entries' r, Ap, x and p: in registers for boxes of <= 3 nodes per thread (C2's 14 x 10 x 10), else
     // (LST) r, Ap, x in LDS (lane-linear: conflict-free) and p in the image (each slot formed by one thread), so 4
     // nodes per thread fit without spilling (the C3 / 8 slab's 19 x 19 x 5; LDS state cost C2 0.9 us per phase)
@@ -177,7 +192,7 @@ __global__ __launch_bounds__(kResNT) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     constexpr bool multi = MR;  // a PEER slab shard (its own instantiation: the one-block kernel stays as it was)
     const __amdgpu_buffer_rsrc_t rx = sized_rsrc(ra.x, vbytes), rr = sized_rsrc(ra.r, vbytes),
                                  rcls = sized_rsrc(T.lcls, s.N), rmass = sized_rsrc(s.mass, 4u * s.N),
-                                 rpub = sized_rsrc(ra.pub, 96u * ra.npub), rsh = sized_rsrc(ra.sh, 160u * G);
+                                 rpub = sized_rsrc(ra.pub, 32u * ra.npub), rsh = sized_rsrc(ra.sh, 160u * G);
     // own nodes: their r, Ap, x in LDS (st), p in the image, for the whole solve; in registers only the node, its
     // image slot and class, publication index and mass (4 per node: 4 nodes per thread fit without spilling)
     uint32_t on[NPT], osc[NPT], opub[NPT];  // node; image slot | class << 16; publication index
@@ -203,8 +218,10 @@ __global__ __launch_bounds__(kResNT) __attribute__((amdgpu_waves_per_eu(2, 2))) 
                  (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rcls, v ? e.x : kResNone, 0, 0) << 16;
         m[u] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rmass, v ? 4u * e.x : 4u * kLatOob1, 0, 0));
     }
-    // halo entries: their owners' records
+    // halo (ring) entries: their owners' records; r_(j-1) and p_(j-1) of each as this thread formed them in phase
+    // j - 1, kept for the whole solve (fused_form on the owner's inputs: the owner's bits)
     uint32_t hn[NPH], hsc[NPH], hpub[NPH];  // node; image slot | class << 16; the owner's publication index
+    float hr[NPH][3], hp[NPH][3];
 #pragma unroll
     for (int h = 0; h < NPH; ++h)
     {
@@ -213,6 +230,9 @@ __global__ __launch_bounds__(kResNT) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         hpub[h] = e.z;
         hsc[h] = e.y | (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rcls, e.x != kResNone ? e.x : kResNone, 0, 0)
                            << 16;
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            hr[h][c] = hp[h][c] = 0.f;
     }
     const CtlPre pre = ctl_prefetch(ra.ctl, 1u);  // tol and active (set by fast_fused_init)
     // the node's neighbours in the image (workgroup-uniform)
@@ -220,15 +240,12 @@ __global__ __launch_bounds__(kResNT) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 #pragma unroll
     for (int o = 0; o < E::nOff; ++o)
         soff[o] = E::off[o][0] + E::off[o][1] * PX + E::off[o][2] * PXY;
-    // halo entry h's record of the phase of parity par: another box's (pub), or a ghost's in the mailbox (a shard;
-    // the out-of-range load of the other source returns 0, so the two combine by OR)
-    const auto request = [&](int h, uint32_t par, u32x4 &a, u32x4 &c, u32x4 &e) {
+    // halo entry h's Ap granule of the phase of parity par: another box's (pub), or a ghost's in the mailbox (a
+    // shard; the out-of-range load of the other source returns 0, so the two combine by OR)
+    const auto request = [&](int h, uint32_t par, u32x4 &c) {
         const bool gh = (hpub[h] & kResGhost) != 0u, v = hn[h] != kResNone;
-        const uint32_t po = v && !gh ? 48u * (par * ra.npub + hpub[h]) : kResOob;
-        a = ld4_sc1(rpub, po);
-        c = ld4_sc1(rpub, po + 16u);
-        e = ld4_sc1(rpub, po + 32u);
-        if constexpr (multi)  // a ghost: its owner's Ap_(j-1) granule only
+        c = ld4_sc1(rpub, v && !gh ? 16u * (par * ra.npub + hpub[h]) : kResOob);
+        if constexpr (multi)
         {
             const __amdgpu_buffer_rsrc_t rg = sized_rsrc(par ? ra.pa.grecv[1] : ra.pa.grecv[0], ra.pa.grecv_bytes);
             c |= ld4_sys(rg, v && gh ? 16u * (hpub[h] & ~kResGhost) : kResOob);
@@ -241,8 +258,8 @@ __global__ __launch_bounds__(kResNT) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     for (; go; ++j)
     {
         float alpha = 0.f, beta = 0.f;
-        float hr[NPH][3], ha[NPH][3], hp[NPH][3];
-        u32x4 w0[NPH], w1[NPH], w2[NPH];  // phase j - 1's halo records (granules {r, tag} {Ap, tag} {p, tag})
+        float ha[NPH][3], hrn[NPH][3], hpn[NPH][3];  // Ap_(j-1); r_j, p_j as formed (kept once the vote has passed)
+        u32x4 w1[NPH];  // phase j - 1's halo granules {Ap, tag}
         const uint32_t par = (j - 1u) & 1u, want = ra.tag0 + j;
         // the workgroup's vote on `ok` (slot round mod 3; the next round's slot is reset before this round's
         // barrier: its last readers passed a barrier since). Every thread counts the same rounds: uniform
@@ -263,7 +280,8 @@ __global__ __launch_bounds__(kResNT) __attribute__((amdgpu_waves_per_eu(2, 2))) 
                 ra.ctl->active = 0;
             }
         };
-        if (j == 0)  // phase 0 (alpha = beta = 0; Ap_(-1) = p_(-1) = 0): the halo's r_0 from fast_fused_init's r
+        if (j == 0)  // phase 0 (alpha = beta = 0; Ap_(-1) = p_(-1) = 0, hp as initialised): the halo's r_0 from
+                     // fast_fused_init's r
         {
 #pragma unroll
             for (int h = 0; h < NPH; ++h)
@@ -273,20 +291,20 @@ __global__ __launch_bounds__(kResNT) __attribute__((amdgpu_waves_per_eu(2, 2))) 
                 hr[h][0] = __uint_as_float(w.x), hr[h][1] = __uint_as_float(w.y), hr[h][2] = __uint_as_float(w.z);
 #pragma unroll
                 for (int c = 0; c < 3; ++c)
-                    ha[h][c] = hp[h][c] = 0.f;
+                    ha[h][c] = 0.f;
             }
         }
         else
         {
             stamp(j, 0);
-            // phase j - 1's five shares of every workgroup and this box's halo records, polled until every granule
+            // phase j - 1's five shares of every workgroup and this box's halo granules, polled until every granule
             // carries phase j - 1's tag (each 16-B granule is one write-through store with its own tag: no counter,
             // no ordering between granules needed). Bounded: a workgroup that never publishes ends the solve
             u32x4 g[kFusedShares];
             // the five share granules of every workgroup (thread t < G: workgroup t's), polled until all carry
-            // phase j - 1's tag; then this box's halo records are requested and arrive while the shares are folded
-            // and the own nodes formed (a producer stores its halo records before its shares, so they have nearly
-            // always landed by then; a record with another tag is read again below)
+            // phase j - 1's tag; then this box's halo granules are requested and arrive while the shares are folded
+            // and the own nodes formed (a producer stores its Ap granules before its shares, so they have nearly
+            // always landed by then; a granule with another tag is read again below)
             for (;; ++round)
             {
 #pragma unroll
@@ -307,7 +325,7 @@ __global__ __launch_bounds__(kResNT) __attribute__((amdgpu_waves_per_eu(2, 2))) 
             }
 #pragma unroll
             for (int h = 0; h < NPH; ++h)
-                request(h, par, w0[h], w1[h], w2[h]);
+                request(h, par, w1[h]);
             stamp(j, 1);
             double v[kFusedShares];
 #pragma unroll
@@ -397,22 +415,11 @@ __global__ __launch_bounds__(kResNT) __attribute__((amdgpu_waves_per_eu(2, 2))) 
             pl[slot] = float4{pn[0], pn[1], pn[2], 0.f};
             fused_entry_dots(rn, zz, d);
         }
-        // a shard's ghost entries: their r_(j-1), p_(j-1) as this box formed them last phase (the registers stay as
-        // loaded through the re-reads below, so a ghost formed twice stores the same r_j, p_j)
-        const auto ghost = [&](int h) { return multi && (hpub[h] & kResGhost) != 0u; };
-        const auto gslot = [&](int h) { return 2u * (tid + (uint32_t)h * kResNT - hd.y); };
-        if constexpr (multi)
-            if (j > 0)
-#pragma unroll
-                for (int h = 0; h < NPH; ++h)
-                    if (hn[h] != kResNone && ghost(h))
-                    {
-                        const float4 gr = gst[gslot(h)], gp = gst[gslot(h) + 1u];
-                        hr[h][0] = gr.x, hr[h][1] = gr.y, hr[h][2] = gr.z;
-                        hp[h][0] = gp.x, hp[h][1] = gp.y, hp[h][2] = gp.z;
-                    }
-        // the halo's p_j: phase 0 from fast_fused_init's r; later phases from the records requested above, each
-        // granule checked for its tag (a record that had not landed is read again: a bounded, voted re-read)
+        // the halo's r_j, p_j from the kept r_(j-1), p_(j-1) (phase 0: fast_fused_init's r and 0) and the Ap_(j-1)
+        // granules requested above, each checked for its tag (one that had not landed is read again: a bounded, voted
+        // re-read). Every pass forms from the kept values into hrn / hpn; they replace the kept ones only once the vote
+        // has passed, so an entry formed on two passes takes alpha once
+        bool again = ra.reread != 0u && j > 0;  // (the test knob: the first vote of the phase counts as failed)
         for (;; ++round)
         {
             bool hok = true;
@@ -423,38 +430,27 @@ __global__ __launch_bounds__(kResNT) __attribute__((amdgpu_waves_per_eu(2, 2))) 
                     continue;
                 if (j > 0)
                 {
-                    const bool gh = ghost(h);
-                    if (w1[h].w != want || (!gh && (w0[h].w != want || w2[h].w != want)))
+                    if (w1[h].w != want)
                     {
                         hok = false;
                         continue;
                     }
-                    if (!gh)
-                    {
-                        hr[h][0] = __uint_as_float(w0[h].x), hr[h][1] = __uint_as_float(w0[h].y);
-                        hr[h][2] = __uint_as_float(w0[h].z);
-                        hp[h][0] = __uint_as_float(w2[h].x), hp[h][1] = __uint_as_float(w2[h].y);
-                        hp[h][2] = __uint_as_float(w2[h].z);
-                    }
                     ha[h][0] = __uint_as_float(w1[h].x), ha[h][1] = __uint_as_float(w1[h].y);
                     ha[h][2] = __uint_as_float(w1[h].z);
                 }
-                float rn[3], zz[3], pn[3];
-                fused_form(czA, czB, hsc[h] >> 16, alpha, beta, hr[h], ha[h], hp[h], rn, zz, pn);
-                pl[hsc[h] & 0xFFFFu] = float4{pn[0], pn[1], pn[2], 0.f};
-                if (ghost(h))
-                {
-                    gst[gslot(h)] = float4{rn[0], rn[1], rn[2], 0.f};
-                    gst[gslot(h) + 1u] = float4{pn[0], pn[1], pn[2], 0.f};
-                }
+                float zz[3];
+                fused_form(czA, czB, hsc[h] >> 16, alpha, beta, hr[h], ha[h], hp[h], hrn[h], zz, hpn[h]);
+                pl[hsc[h] & 0xFFFFu] = float4{hpn[h][0], hpn[h][1], hpn[h][2], 0.f};
             }
             if (j == 0)
             {
                 lds_sync();  // the image complete before the rows
                 break;
             }
-            if (all_ok(hok))  // (its barrier also completes the image: the own entries were written before it)
+            const bool pass = all_ok(hok);  // (its barrier also completes the image: the own entries were written before it)
+            if (pass && !again)
                 break;
+            again = false;
             if (round >= kResMaxRounds)
             {
                 give_up();
@@ -462,10 +458,16 @@ __global__ __launch_bounds__(kResNT) __attribute__((amdgpu_waves_per_eu(2, 2))) 
             }
 #pragma unroll
             for (int h = 0; h < NPH; ++h)
-                request(h, par, w0[h], w1[h], w2[h]);
+                request(h, par, w1[h]);
         }
+#pragma unroll
+        for (int h = 0; h < NPH; ++h)
+            if (hn[h] != kResNone)
+#pragma unroll
+                for (int c = 0; c < 3; ++c)
+                    hr[h][c] = hrn[h][c], hp[h][c] = hpn[h][c];
         stamp(j, 3);
-        // rows: Ap_j = K_eff p_j, the dots of the row, the box-surface records for the neighbours' next phase
+        // rows: Ap_j = K_eff p_j, the dots of the row, the box-surface nodes' Ap_j granules for the neighbours' next phase
 #pragma unroll
         for (int u = 0; u < NPT; ++u)
         {
@@ -553,14 +555,10 @@ __global__ __launch_bounds__(kResNT) __attribute__((amdgpu_waves_per_eu(2, 2))) 
             float zz[3];  // z_j again from r_j (the form's arithmetic: the same bits)
             lat_z(czA[cls], czB[cls], cls, rj, zz);
             fused_row_dots(czA, czB, cls, u0, zz, an, d);
-            const uint32_t po = opub[u] != kResNone ? 48u * ((j & 1u) * ra.npub + opub[u]) : kResOob;
-            const uint32_t tag = ra.tag0 + j + 1u;
-            const u32x4 g0 = {__float_as_uint(rj[0]), __float_as_uint(rj[1]), __float_as_uint(rj[2]), tag},
-                        g1 = {__float_as_uint(an[0]), __float_as_uint(an[1]), __float_as_uint(an[2]), tag},
-                        g2 = {__float_as_uint(u0[0]), __float_as_uint(u0[1]), __float_as_uint(u0[2]), tag};
-            st4_sc1(rpub, po, g0);
-            st4_sc1(rpub, po + 16u, g1);
-            st4_sc1(rpub, po + 32u, g2);
+            // (r_j and p_j are not published: every reader formed them itself, from the same inputs)
+            const uint32_t po = opub[u] != kResNone ? 16u * ((j & 1u) * ra.npub + opub[u]) : kResOob;
+            const u32x4 g1 = {__float_as_uint(an[0]), __float_as_uint(an[1]), __float_as_uint(an[2]), ra.tag0 + j + 1u};
+            st4_sc1(rpub, po, g1);
             if constexpr (multi)  // a send-plane node: its Ap_j granule into the neighbour's mailbox, at its ghost position
             {
                 const uint32_t jp = j & 1u, e = rw >> 24, pos = 16u * (rw & 0xFFFFFFu);
@@ -709,6 +707,8 @@ void launch_pcg_resident(cwf_hip_system *h, uint32_t max_it, hipStream_t st, hip
         ra.trace_j = at ? (uint32_t)atoi(at) : 50u;
         (void)hipMemsetAsync(trace, 0, 64ull * rp.G, st);
     }
+    const char *rk = knob("CWF_RESIDENT_REREAD");  // tests/test_gpu_resident_handoff.py
+    ra.reread = rk && rk[0] == '1' ? 1u : 0u;
     if (rp.npt <= 3 && rp.nph <= 2)
         rp.shard ? launch_resident_n<3, 2, true>(h->ds, ra, rp.G, rp.lds, st, e0, e1)
                  : launch_resident_n<3, 2, false>(h->ds, ra, rp.G, rp.lds, st, e0, e1);
