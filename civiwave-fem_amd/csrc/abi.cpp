@@ -693,7 +693,17 @@ static int layout_lattice(cwf_hip_system *h, const cwf_system_desc *d, Lattice &
     t.E = h->ds.E;
     t.geo = 1;
     t.total_tile_nodes = (uint32_t)N;
-    const LatticeClasses lc = lattice_classes(lat, d->bc_mask, d->lumped_mass);
+    if (lat.layered)  // k_keff_lattice_layered: a stencil table per plane class, a cell-pair table per material
+        t.llayers = (uint32_t)(lat.cls_pair.size() / 2) | (uint32_t)lat.mat_id.size() << 16;
+    // A layered block carries no class preconditioner, even where every density is equal: a node's block inverse
+    // depends on the material pair of its plane, which the 27 boundary types x mask classes do not tell apart. So
+    // lcls, lcz, lmu and lzr stay off, and with lcls off the resident solve (resident.cpp), the fused one-launch
+    // iteration (fast_fused) and z-from-r all decline the handle: it runs the two-kernel loop on the per-node inverse.
+    LatticeClasses lc;
+    if (lat.layered)
+        lc.uniform = false;
+    else
+        lc = lattice_classes(lat, d->bc_mask, d->lumped_mass);
     if (lc.uniform && lc.interior)
     {
         t.lmu = 1;
@@ -1178,6 +1188,11 @@ int cwf_hip_system_keff_traffic(const cwf_hip_system *h, uint64_t *layout_bytes,
             *layout_bytes = (uint64_t)s.Nown * (4 * 12 + 1 + 4 * 12) + 4ull * (s.t.lmu ? s.t.lnshell : s.Nown);
             return 0;
         }
+        if (s.t.lat && s.t.llayers)  // layered: the same streams with the per-node mass, plus the plane-class and
+        {                            // material tables and the per-plane word
+            *layout_bytes = (uint64_t)s.Nown * (12 + 12 + 12 + 12 + 4) + 4ull * lattice_table_floats(s.t) + 4ull * s.t.lnz;
+            return 0;
+        }
         if (s.t.lat)  // per owned node: z and p_old read, the new p and the row value written; the mass read
         {             // (only the shell's when the strict interior's is one value, lmu)
             *layout_bytes = (uint64_t)s.Nown * (12 + 12 + 12 + 12 + (s.t.lmu && s.t.lzr ? 1 : 0)) +
@@ -1248,6 +1263,13 @@ const char *cwf_hip_system_keff_kernel(const cwf_hip_system *h)
                  t.lhex ? "LatHex" : "LatKuhn", t.lmu ? "true" : "false", t.lpstride ? "true" : "false",
                  !t.lpstride && h->ds.Nown < h->ds.N ? "true" : "false",
                  h->fused_grid < t.lnwork ? "true" : "false");
+        return name;
+    }
+    if (t.lat && t.llayers)
+    {
+        static thread_local char name[96];
+        snprintf(name, sizeof name, "k_keff_lattice_layered<1, false, %s, %s>", t.lhex ? "LatHex" : "LatKuhn",
+                 t.lpstride ? "true" : "false");
         return name;
     }
     if (t.lat)  // as rocprofv3 names it, less the namespaces

@@ -108,6 +108,12 @@ struct DevTiles
     const uint32_t *lplane = nullptr;    // [lnz] storage index of node (0, 0, k)
     uint32_t lpstride = 0;               // plane[k] == k lpstride for every k (the kernels then skip the plane[] load
                                          // in front of every plane's first gather); 0: read plane[]
+    // Layered block (one material per k-layer of cells; k_keff_lattice_layered): plane classes | material slots << 16,
+    // 0 on a one-material block. lcoef then holds a stencil table per plane class (9 nOff floats each), a cell-pair
+    // table per material slot (9 nPairs floats each) and, after them, one word per node plane (lattice_layers()):
+    // the plane's class | the material slot of the cell layer above it << 16 (the last plane: the layer below).
+    // The field sits in the padding in front of lcoef, so the kernels' argument layout is what it was without it.
+    uint32_t llayers = 0;
     const float *lcoef = nullptr;        // [kLatCoef] stencil, cell-pair and face blocks (unscaled by s_K)
     int lsym = 0;                        // S_(-d) == S_d: the paired-direction instantiation
     int lhex = 0;                        // native hex8 cells: the 27-point instantiation
@@ -121,6 +127,7 @@ struct DevTiles
     float4 *lcz = nullptr;           // [2 kLatClasses] the same inverse unpacked, {a00 a01 a02 a11} {a12 a22 0 0}:
                                      // loaded unconditionally in the K_eff prologue (lattice.inc, ZR)
 };
+static_assert(sizeof(DevTiles) == 352, "llayers fills padding: the K_eff kernels' argument layout is unchanged");
 // lattice work items for planes [lk0, lk1) (lattice.cpp): sets lnbx, lnby, lL, lnwork, ntiles
 void lattice_plan(DevTiles &t);
 
@@ -227,7 +234,31 @@ struct Lattice
     float coef[kLatHexCoef] = {};  // Kuhn: the first kLatCoef
     bool sym = false;  // S_(-d) == S_d for every direction (k_keff_lattice's paired form)
     bool hex = false;  // native hex8 cells (27-point stencil)
+    // Materials by k-layer of cells (cell layer kc: the cells between node planes kc and kc + 1). One material:
+    // layered is false and the tables below repeat coef. Several (layered): coef is unused; a strict-interior node
+    // of plane k takes the stencil table of its plane class, the (material below, material above) pair of its plane,
+    // and a surface node takes each existing cell's pair blocks from the table of that cell's material.
+    bool layered = false;
+    std::vector<uint32_t> layer_mat;  // [nz - 1] material slot of each cell layer (slots by first appearance along k)
+    std::vector<uint32_t> mat_id;     // [slots] the desc's material index of each slot
+    std::vector<uint32_t> plane_cls;  // [nz] plane class of each node plane (the end planes: their one layer twice)
+    std::vector<uint32_t> cls_pair;   // [2 classes] (slot below, slot above) of each class, by first appearance
+    std::vector<float> cls_coef;      // [classes][9 nOff] stencil blocks, row-major 3 x 3
+    std::vector<float> mat_coef;      // [slots][9 nPairs] cell-pair blocks, row-major 3 x 3
 };
+// caps of a layered block: the per-plane tables are workgroup-uniform scalar loads, so all of them should stay in
+// the 16-KB scalar data cache: 16 classes of the larger (hex8, 972-B) table are 15.2 KB
+constexpr uint32_t kLatMaxMaterials = 8, kLatMaxPlaneClasses = 16;
+// layered DevTiles: the floats of lcoef's tables (the per-plane words follow them) and those words
+__host__ __device__ inline uint32_t lattice_table_floats(const DevTiles &t)
+{
+    return 9u * ((t.llayers & 0xFFFFu) * (uint32_t)(t.lhex ? kLatHexOffsets : kLatOffsets) +
+                 (t.llayers >> 16) * (uint32_t)(t.lhex ? kLatHexPairs : kLatPairs));
+}
+inline const uint32_t *lattice_layers(const DevTiles &t)
+{
+    return reinterpret_cast<const uint32_t *>(t.lcoef + lattice_table_floats(t));
+}
 // true when the desc is a Kuhn-split box lattice with one gradient / volume set per Kuhn type (lattice.cpp);
 // allow_perm: the handle may renumber (otherwise the nodes must already be lexicographic within planes)
 bool detect_lattice(const cwf_system_desc *d, bool allow_perm, Lattice &L, std::string *why = nullptr);

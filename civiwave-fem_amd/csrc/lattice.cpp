@@ -17,8 +17,11 @@
 //
 // detect_lattice() decides it for a desc: integer lattice coordinates of every node (from the first tet's cell
 // size), a bijection onto an nx * ny * nz lattice, every tet one Kuhn tet of one cell (each of a cell's 6 types
-// exactly once), one material, and every tet's gradients / volume within 1e-6 (relative) of the first tet of its
-// Kuhn type. Storage order: lexicographic (i fastest) inside each k plane, planes anywhere (a shard's local order:
+// exactly once), one material per k-layer of cells, and every tet's gradients / volume within 1e-6 (relative) of the
+// first tet of its Kuhn type. With one material in all: the tables above. With several (a layered block, strata): one
+// cell stiffness per material, a stencil table per plane class -- the (material below, material above) pair of a node
+// plane -- and a cell-pair table per material (layered_tables; at most kLatMaxMaterials materials and
+// kLatMaxPlaneClasses classes, else no lattice). Storage order: lexicographic (i fastest) inside each k plane, planes anywhere (a shard's local order:
 // owned planes, then its ghost planes; shard.cpp), or, when the handle may renumber, any order (perm).
 #include <algorithm>
 #include <cmath>
@@ -163,49 +166,104 @@ constexpr int kHexPair[kLatHexPairs][2] = {
 #undef P8
 };
 
-// native hex8 cells (Gmsh / VTK corner order; slot s sits at corner bits kHexSlotBits[s]): one hex per cell, the
-// cell stiffness from the first hex's corner coordinates (the lattice's, to 1e-6 of the cell: every cell is a
-// translate), 2 x 2 x 2 Gauss in fp64 (the textbook element of oracle/hex8_oracle.c and k_keff_hex_tiles)
-bool detect_hex_cells(const cwf_system_desc *d, const std::vector<uint32_t> &q, const uint32_t nn[3],
-                      const std::vector<uint32_t> &at, bool allow_perm, Lattice &L, std::string *why)
+// Material slots of the cell layers (by first appearance along k) and the plane classes of the node planes: one
+// class per (slot below, slot above) pair that occurs; the end planes, which have one layer, take it twice (all
+// their nodes are shell nodes: the class only has to exist). lay[kc]: the desc's material of cell layer kc.
+bool layer_classes(const std::vector<uint32_t> &lay, Lattice &L, const char **why)
 {
-    const auto fail = [&](const char *m) {
-        if (why)
-            *why = m;
-        return false;
-    };
-    constexpr int kHexSlotBits[8] = {0, 1, 3, 2, 4, 5, 7, 6};
-    const uint64_t N = d->node_count, E = d->element_count, nx = nn[0], ny = nn[1], nz = nn[2];
-    if (E != (nx - 1) * (ny - 1) * (nz - 1))
-        return fail("element count is not one hex per cell");
-    const uint32_t *conn = d->element_connectivity;
-    std::vector<uint8_t> seen(E, 0);
-    for (uint64_t e = 0; e < E; ++e)
+    const uint32_t nl = (uint32_t)lay.size();
+    L.layer_mat.assign(nl, 0);
+    L.mat_id.clear();
+    for (uint32_t kc = 0; kc < nl; ++kc)
     {
-        const uint32_t *c = &q[3ull * conn[8 * e]];  // slot 0 is the cell's corner (0, 0, 0)
-        if (c[0] >= nx - 1 || c[1] >= ny - 1 || c[2] >= nz - 1)
-            return fail("a hex is not a cell");
-        for (int s = 1; s < 8; ++s)
-        {
-            const uint32_t *qs = &q[3ull * conn[8 * e + s]];
-            const uint32_t ox = qs[0] - c[0], oy = qs[1] - c[1], oz = qs[2] - c[2];
-            if (ox > 1 || oy > 1 || oz > 1 || (int)(ox | oy << 1 | oz << 2) != kHexSlotBits[s])
-                return fail("a hex is not a cell in Gmsh corner order");
-        }
-        const uint64_t cell = ((uint64_t)c[2] * (ny - 1) + c[1]) * (nx - 1) + c[0];
-        if (seen[cell])
-            return fail("two hexes on one cell");
-        seen[cell] = 1;
+        uint32_t s = 0;
+        while (s < L.mat_id.size() && L.mat_id[s] != lay[kc])
+            ++s;
+        if (s == L.mat_id.size())
+            L.mat_id.push_back(lay[kc]);
+        L.layer_mat[kc] = s;
     }
-    if (!storage_order(N, nn, at, allow_perm, L))
-        return fail("node order is not lexicographic within planes");
-    double Xc[8][3];  // corner coordinates of the first hex by corner bits
-    for (int s = 0; s < 8; ++s)
-        for (int k = 0; k < 3; ++k)
-            Xc[kHexSlotBits[s]][k] = d->node_coords[3ull * conn[s] + k];
-    const double *D = d->material_stiffness + 36ull * d->element_material_index[0];
-    double Kc[8][8][3][3];
-    std::memset(Kc, 0, sizeof Kc);
+    if (L.mat_id.size() > kLatMaxMaterials)
+    {
+        *why = "layered block with more than 8 materials";
+        return false;
+    }
+    L.plane_cls.assign(nl + 1, 0);
+    L.cls_pair.clear();
+    for (uint32_t k = 0; k <= nl; ++k)
+    {
+        const uint32_t below = L.layer_mat[k ? k - 1 : 0], above = L.layer_mat[k < nl ? k : nl - 1];
+        uint32_t c = 0;
+        while (2 * c < L.cls_pair.size() && (L.cls_pair[2 * c] != below || L.cls_pair[2 * c + 1] != above))
+            ++c;
+        if (2 * c == L.cls_pair.size())
+        {
+            L.cls_pair.push_back(below);
+            L.cls_pair.push_back(above);
+        }
+        L.plane_cls[k] = c;
+    }
+    if (L.cls_pair.size() / 2 > kLatMaxPlaneClasses)
+    {
+        *why = "layered block with more than 16 plane classes";
+        return false;
+    }
+    L.layered = L.mat_id.size() > 1;
+    return true;
+}
+
+// one material: the layered description repeats the block's own tables (one slot, one class)
+template <int NOFF, int NPAIR>
+void single_material_tables(Lattice &L)
+{
+    L.cls_coef.assign(L.coef, L.coef + 9 * NOFF);
+    L.mat_coef.assign(L.coef + 9 * NOFF, L.coef + 9 * (NOFF + NPAIR));
+}
+
+// Layered block: per plane class (below, above) the stencil blocks S_d = sum over the node's corner positions c
+// with c + d a corner of Kc^m[c][c + d], m the material of the cell the node sits in at corner c: the cell below
+// the node's plane when c's z-bit is 1, the cell above when it is 0. fp64 over both halves, rounded to f32 once.
+// S_(-d) = S_d holds only between equal layers (on an interface plane the two differ by 57-88% of the largest
+// entry for the strata of tests/test_lattice_layered.py), so no class is paired (sym off).
+// Per material slot, the cell-pair blocks for the surface shell.
+template <int NOFF, int NPAIR>
+void layered_tables(const std::vector<double> &Kc, const int (&off)[NOFF][3], const int (&pair)[NPAIR][2], Lattice &L)
+{
+    const auto kc = [&](uint32_t m, int a, int b, int r, int k) { return Kc[(((size_t)m * 8 + a) * 8 + b) * 9 + 3 * r + k]; };
+    const size_t ncls = L.cls_pair.size() / 2, nmat = L.mat_id.size();
+    L.cls_coef.assign(ncls * 9 * NOFF, 0.f);
+    for (size_t cl = 0; cl < ncls; ++cl)
+        for (int o = 0; o < NOFF; ++o)
+        {
+            double S[9] = {};
+            for (int c = 0; c < 8; ++c)
+            {
+                const int cx = (c & 1) + off[o][0], cy = ((c >> 1) & 1) + off[o][1], cz = ((c >> 2) & 1) + off[o][2];
+                if (cx < 0 || cx > 1 || cy < 0 || cy > 1 || cz < 0 || cz > 1)
+                    continue;
+                const int c2 = cx | cy << 1 | cz << 2;
+                const uint32_t m = L.cls_pair[2 * cl + ((c >> 2) & 1 ? 0 : 1)];
+                for (int r = 0; r < 3; ++r)
+                    for (int k = 0; k < 3; ++k)
+                        S[3 * r + k] += kc(m, c, c2, r, k);
+            }
+            for (int j = 0; j < 9; ++j)
+                L.cls_coef[(cl * NOFF + o) * 9 + j] = (float)S[j];
+        }
+    L.mat_coef.assign(nmat * 9 * NPAIR, 0.f);
+    for (size_t m = 0; m < nmat; ++m)
+        for (int p = 0; p < NPAIR; ++p)
+            for (int r = 0; r < 3; ++r)
+                for (int k = 0; k < 3; ++k)
+                    L.mat_coef[(m * NPAIR + p) * 9 + 3 * r + k] = (float)kc((uint32_t)m, pair[p][0], pair[p][1], r, k);
+    L.sym = false;
+    std::memset(L.coef, 0, sizeof L.coef);
+}
+
+// trilinear hex cell stiffness, 2 x 2 x 2 Gauss in fp64, from the cell's corner coordinates by corner bits
+bool hex_cell_stiffness(const double Xc[8][3], const double *D, double Kc[8][8][3][3])
+{
+    std::memset(Kc, 0, sizeof(double) * 8 * 8 * 9);
     const double gq = 1.0 / std::sqrt(3.0);
     for (int gp = 0; gp < 8; ++gp)
     {
@@ -234,7 +292,7 @@ bool detect_hex_cells(const cwf_system_desc *d, const std::vector<uint32_t> &q, 
         A[2][2] = J[0][0] * J[1][1] - J[0][1] * J[1][0];
         const double det = J[0][0] * A[0][0] + J[0][1] * A[1][0] + J[0][2] * A[2][0];
         if (!(std::fabs(det) > 0.0))
-            return fail("degenerate hex");
+            return false;
         double g[8][3];
         for (int a = 0; a < 8; ++a)
             for (int m = 0; m < 3; ++m)
@@ -261,8 +319,109 @@ bool detect_hex_cells(const cwf_system_desc *d, const std::vector<uint32_t> &q, 
                     }
             }
     }
-    stencil_tables(Kc, kLatHexOff, kHexPair, L);
+    return true;
+}
+
+// Kuhn cell stiffness Kc[c][c'] = sum over the cell's tets of vol B_c^T D B_c' (fp64, pcg.cpp:622-651 products)
+void kuhn_cell_stiffness(const double G[6][8][3], const double V[6], const double *D, double Kc[8][8][3][3])
+{
+    std::memset(Kc, 0, sizeof(double) * 8 * 8 * 9);
+    for (int t = 0; t < 6; ++t)
+        for (int sa = 0; sa < 4; ++sa)
+            for (int sb = 0; sb < 4; ++sb)
+            {
+                const int a = kKuhn[t][sa], b = kKuhn[t][sb];
+                double Ba[6][3], Bb[6][3];
+                b_block(G[t][a], Ba);
+                b_block(G[t][b], Bb);
+                for (int r = 0; r < 3; ++r)
+                    for (int k = 0; k < 3; ++k)
+                    {
+                        double sum = 0.0;
+                        for (int i = 0; i < 6; ++i)
+                            for (int j = 0; j < 6; ++j)
+                                sum += Ba[i][r] * D[6 * i + j] * Bb[j][k];
+                        Kc[a][b][r][k] += V[t] * sum;
+                    }
+            }
+}
+
+// the material of each cell layer from the elements' (cell layer, material) pairs; false when a layer holds two
+struct LayerMaterials
+{
+    std::vector<uint32_t> lay;
+    explicit LayerMaterials(uint64_t layers) : lay(layers, 0xFFFFFFFFu) {}
+    bool add(uint32_t kc, uint32_t m)
+    {
+        if (lay[kc] == 0xFFFFFFFFu)
+            lay[kc] = m;
+        return lay[kc] == m;
+    }
+};
+
+// native hex8 cells (Gmsh / VTK corner order; slot s sits at corner bits kHexSlotBits[s]): one hex per cell, the
+// cell stiffness from the first hex's corner coordinates (the lattice's, to 1e-6 of the cell: every cell is a
+// translate), 2 x 2 x 2 Gauss in fp64 (the textbook element of oracle/hex8_oracle.c and k_keff_hex_tiles)
+bool detect_hex_cells(const cwf_system_desc *d, const std::vector<uint32_t> &q, const uint32_t nn[3],
+                      const std::vector<uint32_t> &at, bool allow_perm, Lattice &L, std::string *why)
+{
+    const auto fail = [&](const char *m) {
+        if (why)
+            *why = m;
+        return false;
+    };
+    constexpr int kHexSlotBits[8] = {0, 1, 3, 2, 4, 5, 7, 6};
+    const uint64_t N = d->node_count, E = d->element_count, nx = nn[0], ny = nn[1], nz = nn[2];
+    if (E != (nx - 1) * (ny - 1) * (nz - 1))
+        return fail("element count is not one hex per cell");
+    const uint32_t *conn = d->element_connectivity;
+    std::vector<uint8_t> seen(E, 0);
+    LayerMaterials lm(nz - 1);
+    for (uint64_t e = 0; e < E; ++e)
+    {
+        const uint32_t *c = &q[3ull * conn[8 * e]];  // slot 0 is the cell's corner (0, 0, 0)
+        if (c[0] >= nx - 1 || c[1] >= ny - 1 || c[2] >= nz - 1)
+            return fail("a hex is not a cell");
+        if (!lm.add(c[2], d->element_material_index[e]))
+            return fail("materials vary inside a cell layer");
+        for (int s = 1; s < 8; ++s)
+        {
+            const uint32_t *qs = &q[3ull * conn[8 * e + s]];
+            const uint32_t ox = qs[0] - c[0], oy = qs[1] - c[1], oz = qs[2] - c[2];
+            if (ox > 1 || oy > 1 || oz > 1 || (int)(ox | oy << 1 | oz << 2) != kHexSlotBits[s])
+                return fail("a hex is not a cell in Gmsh corner order");
+        }
+        const uint64_t cell = ((uint64_t)c[2] * (ny - 1) + c[1]) * (nx - 1) + c[0];
+        if (seen[cell])
+            return fail("two hexes on one cell");
+        seen[cell] = 1;
+    }
+    if (!storage_order(N, nn, at, allow_perm, L))
+        return fail("node order is not lexicographic within planes");
+    double Xc[8][3];  // corner coordinates of the first hex by corner bits
+    for (int s = 0; s < 8; ++s)
+        for (int k = 0; k < 3; ++k)
+            Xc[kHexSlotBits[s]][k] = d->node_coords[3ull * conn[s] + k];
     L.hex = true;
+    const char *cwhy = nullptr;
+    if (!layer_classes(lm.lay, L, &cwhy))
+        return fail(cwhy);
+    if (!L.layered)  // one material: today's tables
+    {
+        const double *D = d->material_stiffness + 36ull * d->element_material_index[0];
+        double Kc[8][8][3][3];
+        if (!hex_cell_stiffness(Xc, D, Kc))
+            return fail("degenerate hex");
+        stencil_tables(Kc, kLatHexOff, kHexPair, L);
+        single_material_tables<kLatHexOffsets, kLatHexPairs>(L);
+        return true;
+    }
+    std::vector<double> Km(L.mat_id.size() * 576);
+    for (size_t m = 0; m < L.mat_id.size(); ++m)
+        if (!hex_cell_stiffness(Xc, d->material_stiffness + 36ull * L.mat_id[m],
+                                *reinterpret_cast<double(*)[8][8][3][3]>(&Km[576 * m])))
+            return fail("degenerate hex");
+    layered_tables(Km, kLatHexOff, kHexPair, L);
     return true;
 }
 
@@ -283,10 +442,6 @@ bool detect_lattice(const cwf_system_desc *d, bool allow_perm, Lattice &L, std::
     const int K = hex ? 8 : 4;
     const uint32_t *conn = d->element_connectivity;
     const double *X = d->node_coords;
-    const uint32_t m0 = d->element_material_index[0];
-    for (uint64_t e = 0; e < E; ++e)
-        if (d->element_material_index[e] != m0)
-            return fail("more than one material");
     // cell size from the first element (a Kuhn tet spans its whole cell: it holds corners 0 and 7)
     double h[3], lo[3];
     for (int k = 0; k < 3; ++k)
@@ -346,6 +501,7 @@ bool detect_lattice(const cwf_system_desc *d, bool allow_perm, Lattice &L, std::
         type_of[m] = t;
     }
     std::vector<uint8_t> seen(C, 0);
+    LayerMaterials lm(nz - 1);
     double G[6][8][3];
     double V[6], gmax[6];
     bool have[6] = {false, false, false, false, false, false};
@@ -369,6 +525,8 @@ bool detect_lattice(const cwf_system_desc *d, bool allow_perm, Lattice &L, std::
         const int t = type_of[m];
         if (t < 0 || c[0] >= nx - 1 || c[1] >= ny - 1 || c[2] >= nz - 1)
             return fail("an element is not a Kuhn tet of a cell");
+        if (!lm.add(c[2], d->element_material_index[e]))
+            return fail("materials vary inside a cell layer");
         const uint64_t cell = ((uint64_t)c[2] * (ny - 1) + c[1]) * (nx - 1) + c[0];
         if (seen[cell] & (1u << t))
             return fail("a cell holds one Kuhn type twice");
@@ -400,30 +558,23 @@ bool detect_lattice(const cwf_system_desc *d, bool allow_perm, Lattice &L, std::
     if (!storage_order(N, nn, at, allow_perm, L))
         return fail("node order is not lexicographic within planes");
     L.hex = false;
-    // cell stiffness Kc[c][c'] = sum over the cell's tets of vol B_c^T D B_c' (fp64, pcg.cpp:622-651 products)
-    const double *D = d->material_stiffness + 36ull * m0;
-    double Kc[8][8][3][3];
-    std::memset(Kc, 0, sizeof Kc);
-    for (int t = 0; t < 6; ++t)
-        for (int sa = 0; sa < 4; ++sa)
-            for (int sb = 0; sb < 4; ++sb)
-            {
-                const int a = kKuhn[t][sa], b = kKuhn[t][sb];
-                double Ba[6][3], Bb[6][3];
-                b_block(G[t][a], Ba);
-                b_block(G[t][b], Bb);
-                for (int r = 0; r < 3; ++r)
-                    for (int k = 0; k < 3; ++k)
-                    {
-                        double sum = 0.0;
-                        for (int i = 0; i < 6; ++i)
-                            for (int j = 0; j < 6; ++j)
-                                sum += Ba[i][r] * D[6 * i + j] * Bb[j][k];
-                        Kc[a][b][r][k] += V[t] * sum;
-                    }
-            }
+    const char *cwhy = nullptr;
+    if (!layer_classes(lm.lay, L, &cwhy))
+        return fail(cwhy);
     // every block outside the Kuhn pattern is structurally zero (never accumulated): nothing to check
-    stencil_tables(Kc, kLatOff, kLatPair, L);
+    if (!L.layered)  // one material: today's tables
+    {
+        double Kc[8][8][3][3];
+        kuhn_cell_stiffness(G, V, d->material_stiffness + 36ull * d->element_material_index[0], Kc);
+        stencil_tables(Kc, kLatOff, kLatPair, L);
+        single_material_tables<kLatOffsets, kLatPairs>(L);
+        return true;
+    }
+    std::vector<double> Km(L.mat_id.size() * 576);
+    for (size_t m = 0; m < L.mat_id.size(); ++m)
+        kuhn_cell_stiffness(G, V, d->material_stiffness + 36ull * L.mat_id[m],
+                            *reinterpret_cast<double(*)[8][8][3][3]>(&Km[576 * m]));
+    layered_tables(Km, kLatOff, kLatPair, L);
     return true;
 }
 
@@ -484,16 +635,35 @@ void lattice_plan(DevTiles &t)
 
 // The device copy's stencil blocks are stored row-pair interleaved for the packed rows of k_keff_lattice: per
 // offset {S00 S10 S01 S11 S02 S12 S20 S21 S22}; the cell-pair blocks after them keep row-major order
+// A layered block's copy: one such slice of stencil blocks per plane class, then the cell-pair blocks of every
+// material slot, then one word per node plane (its bits in a float): the plane's class | the material slot of the
+// cell layer above it << 16 (k_keff_lattice_layered; DevTiles::llayers)
 std::vector<float> lattice_device_coef(const Lattice &lat)
 {
-    std::vector<float> cdev(lat.coef, lat.coef + (lat.hex ? kLatHexCoef : kLatCoef));
-    for (int o = 0; o < (lat.hex ? kLatHexOffsets : kLatOffsets); ++o)
+    const int noff = lat.hex ? kLatHexOffsets : kLatOffsets;
+    std::vector<float> cdev;
+    if (lat.layered)
+    {
+        cdev = lat.cls_coef;
+        cdev.insert(cdev.end(), lat.mat_coef.begin(), lat.mat_coef.end());
+    }
+    else
+        cdev.assign(lat.coef, lat.coef + (lat.hex ? kLatHexCoef : kLatCoef));
+    const std::vector<float> src = cdev;
+    for (size_t o = 0; o < (lat.layered ? lat.cls_pair.size() / 2 : 1) * noff; ++o)
         for (int c = 0; c < 3; ++c)
         {
-            cdev[9 * o + 2 * c] = lat.coef[9 * o + c];
-            cdev[9 * o + 2 * c + 1] = lat.coef[9 * o + 3 + c];
-            cdev[9 * o + 6 + c] = lat.coef[9 * o + 6 + c];
+            cdev[9 * o + 2 * c] = src[9 * o + c];
+            cdev[9 * o + 2 * c + 1] = src[9 * o + 3 + c];
+            cdev[9 * o + 6 + c] = src[9 * o + 6 + c];
         }
+    for (uint32_t k = 0; lat.layered && k < lat.nz; ++k)
+    {
+        const uint32_t w = lat.plane_cls[k] | lat.layer_mat[std::min(k, lat.nz - 2)] << 16;
+        float f;
+        std::memcpy(&f, &w, sizeof f);
+        cdev.push_back(f);
+    }
     return cdev;
 }
 
@@ -552,7 +722,7 @@ extern "C" int cwf_lattice_describe(const cwf_system_desc *desc, int renumber, u
                 return CWF_ERR_NODE_RANGE;
     }
     cwf::Lattice L;
-    if (!cwf::detect_lattice(desc, renumber != 0, L))
+    if (!cwf::detect_lattice(desc, renumber != 0, L) || L.layered)  // layered: cwf_lattice_describe_layers
         return 0;
     dims[0] = L.nx;
     dims[1] = L.ny;
@@ -561,5 +731,63 @@ extern "C" int cwf_lattice_describe(const cwf_system_desc *desc, int renumber, u
     dims[0] |= L.sym ? 0x80000000u : 0u;
     if (plane)
         std::memcpy(plane, L.plane.data(), L.plane.size() * sizeof(uint32_t));
+    return 1;
+}
+
+extern "C" int cwf_lattice_describe_layers(const cwf_system_desc *desc, int renumber, uint32_t dims[3], uint32_t info[4],
+                                           uint32_t plane_capacity, uint32_t *plane, uint32_t *plane_class,
+                                           uint32_t *layer_material, uint32_t class_capacity, uint32_t *class_pair,
+                                           float *class_coef, uint32_t material_capacity, uint32_t *material_ids,
+                                           float *pair_coef)
+{
+    static_assert(cwf::kLatMaxMaterials == CWF_LATTICE_MAX_MATERIALS, "cwf_hip.h CWF_LATTICE_MAX_MATERIALS");
+    static_assert(cwf::kLatMaxPlaneClasses == CWF_LATTICE_MAX_PLANE_CLASSES, "cwf_hip.h CWF_LATTICE_MAX_PLANE_CLASSES");
+    if (!desc || !dims || !info || !desc->element_connectivity || !desc->element_gradients || !desc->element_volume ||
+        !desc->element_material_index || !desc->material_stiffness)
+        return CWF_ERR_ARGUMENT;
+    if (desc->mode != CWF_MODE_FAST || desc->node_count >= 0x15555555ull || !desc->element_count)
+        return 0;
+    const bool hex = desc->element_connectivity[4] != 0xFFFFFFFFu;
+    for (uint64_t e = 0; e < desc->element_count; ++e)
+    {
+        if (desc->element_material_index[e] >= desc->material_count)
+            return CWF_ERR_MATERIAL_RANGE;
+        if ((desc->element_connectivity[8 * e + 4] != 0xFFFFFFFFu) != hex)
+            return 0;
+        for (int a = 0; a < (hex ? 8 : 4); ++a)
+            if (desc->element_connectivity[8 * e + a] >= desc->node_count)
+                return CWF_ERR_NODE_RANGE;
+    }
+    cwf::Lattice L;
+    if (!cwf::detect_lattice(desc, renumber != 0, L))
+        return 0;
+    const uint32_t nmat = (uint32_t)L.mat_id.size(), ncls = (uint32_t)(L.cls_pair.size() / 2);
+    const size_t noff = L.hex ? cwf::kLatHexOffsets : cwf::kLatOffsets, npair = L.hex ? cwf::kLatHexPairs : cwf::kLatPairs;
+    dims[0] = L.nx;
+    dims[1] = L.ny;
+    dims[2] = L.nz;
+    info[0] = nmat;
+    info[1] = ncls;
+    info[2] = L.hex ? 1u : 0u;
+    info[3] = L.sym ? 1u : 0u;
+    if (((plane || plane_class || layer_material) && plane_capacity < L.nz) ||
+        ((class_pair || class_coef) && class_capacity < ncls) || ((material_ids || pair_coef) && material_capacity < nmat))
+        return CWF_ERR_SIZE;
+    if (plane)
+        std::memcpy(plane, L.plane.data(), L.nz * sizeof(uint32_t));
+    if (plane_class)
+        std::memcpy(plane_class, L.plane_cls.data(), L.nz * sizeof(uint32_t));
+    if (layer_material)
+        for (uint32_t kc = 0; kc + 1 < L.nz; ++kc)
+            layer_material[kc] = L.mat_id[L.layer_mat[kc]];
+    if (class_pair)
+        for (uint32_t i = 0; i < 2 * ncls; ++i)
+            class_pair[i] = L.mat_id[L.cls_pair[i]];
+    if (class_coef)
+        std::memcpy(class_coef, L.cls_coef.data(), ncls * 9 * noff * sizeof(float));
+    if (material_ids)
+        std::memcpy(material_ids, L.mat_id.data(), nmat * sizeof(uint32_t));
+    if (pair_coef)
+        std::memcpy(pair_coef, L.mat_coef.data(), nmat * 9 * npair * sizeof(float));
     return 1;
 }

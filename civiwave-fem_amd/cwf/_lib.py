@@ -139,6 +139,7 @@ def load() -> C.CDLL:
         "cwf_hip_system_exchange_schedule": ([P], i32),
         "cwf_hip_system_keff_source_hash": ([P], C.c_char_p),
         "cwf_lattice_describe": ([P, i32, P, P, P], i32),
+        "cwf_lattice_describe_layers": ([P, i32, P, P, C.c_uint32, P, P, P, C.c_uint32, P, P, C.c_uint32, P, P], i32),
         "cwf_hip_system_set_timing": ([P, i32], i32),
         "cwf_hip_system_timing": ([P, P, P], i32),
         "cwf_hip_keff_timed": ([P, P, P, i32, P], i32),

@@ -96,6 +96,26 @@ def kuhn_slab(nx: int, ny: int, nz: int, kc0: int, kc1: int, h: float = 1.0, ele
     return TetMesh(sub.coords, sub.tets, groups, (nx, ny, kc1 - kc0)), node_global
 
 
+def layered_block(nx: int, ny: int, nz: int, layers, h: float = 1.0, element: str = "tet4"):
+    """The structured block with a material per cell layer along k (strata): layers[kc] is the material slot of the
+    cells between node planes kc and kc + 1 -> (TetMesh, element_material u32 [E], the slot of every element)."""
+    layers = np.asarray(layers, np.int64)
+    assert layers.shape == (nz,), (layers.shape, nz)
+    tm = (hex_block if element == "hex8" else kuhn_block)(nx, ny, nz, h)
+    per_cell = 1 if element == "hex8" else 6  # elements are numbered cell after cell, cells k slowest
+    return tm, np.repeat(np.repeat(layers, nx * ny), per_cell).astype(np.uint32)
+
+
+def layered_slab(nx: int, ny: int, nz: int, layers, kc0: int, kc1: int, h: float = 1.0, element: str = "tet4"):
+    """kuhn_slab of a layered block: cells k in [kc0, kc1) with their materials -> (TetMesh, global node id per
+    sub-mesh node, element_material u32 [E])."""
+    layers = np.asarray(layers, np.int64)
+    assert layers.shape == (nz,), (layers.shape, nz)
+    tm, node_global = kuhn_slab(nx, ny, nz, kc0, kc1, h, element)
+    per_cell = 1 if element == "hex8" else 6
+    return tm, node_global, np.repeat(np.repeat(layers[kc0:kc1], nx * ny), per_cell).astype(np.uint32)
+
+
 def jitter_and_permute(mesh: TetMesh, h: float, jitter: float = 0.15, seed_jitter: int = 12345,
                        seed_perm: int = 42) -> TetMesh:
     """C4: jitter interior nodes by +-jitter*h and randomly permute node/element order.
@@ -187,16 +207,24 @@ def boundary_faces(tets: np.ndarray, nodes) -> np.ndarray:
 
 
 def write_gmsh(tm: TetMesh, path: str, solid: str = "SOLID", surface_groups=("FIXED", "TIP"),
-               node_groups=None) -> None:
+               node_groups=None, volumes=None) -> None:
     """Gmsh MSH 4.1 ASCII of a TetMesh that cwf.mesh.load_gmsh_file reads back in the same node and
     element order: physical volume `solid` (id 1) holds the tets; every name in `surface_groups` becomes
     a physical surface of its boundary triangles; every name in `node_groups` (default: all of
     tm.node_groups) tags its nodes through $Entities (Mesh::node_groups). Node blocks follow the node
-    order (one block per run of nodes of the same entity), so node i of the mesh is node i of the file."""
+    order (one block per run of nodes of the same entity), so node i of the mesh is node i of the file.
+    volumes=(names, element_volume): several physical volumes instead of `solid`, one per name (a material each);
+    element_volume [E] is the index into names of every element. Element blocks follow the element order (one block
+    per run of elements of the same volume), so element e of the mesh is element e of the file."""
     names = list(tm.node_groups) if node_groups is None else list(node_groups)
-    phys = {solid: (3, 1)}
+    vnames, evol = ([solid], np.zeros(tm.element_count, np.int64)) if volumes is None else \
+        (list(volumes[0]), np.asarray(volumes[1], np.int64))
+    assert evol.shape == (tm.element_count,) and (not evol.size or (evol.min() >= 0 and evol.max() < len(vnames)))
+    phys = {vnames[0]: (3, 1)}
     for i, n in enumerate(names):
         phys[n] = (2, i + 2)
+    for v, n in enumerate(vnames[1:], start=1):  # ids unique across dimensions (the loader keys groups by id)
+        phys[n] = (3, len(names) + 1 + v)
     N = tm.node_count
     owner = np.zeros(N, np.int64)  # entity per node: 0 = volume entity, k = surface entity of names[k-1]
     for k, n in enumerate(names, start=1):
@@ -205,9 +233,10 @@ def write_gmsh(tm: TetMesh, path: str, solid: str = "SOLID", surface_groups=("FI
         owner[free] = k
     lines = ["$MeshFormat", "4.1 0 8", "$EndMeshFormat", "$PhysicalNames", str(len(phys))]
     lines += [f'{d} {i} "{n}"' for n, (d, i) in phys.items()]
-    lines += ["$EndPhysicalNames", "$Entities", f"0 0 {len(names)} 1"]
+    lines += ["$EndPhysicalNames", "$Entities", f"0 0 {len(names)} {len(vnames)}"]
     lines += [f"{k} 0 0 0 1 1 1 1 {phys[n][1]} 0" for k, n in enumerate(names, start=1)]
-    lines += [f"1 0 0 0 1 1 1 1 {phys[solid][1]} 0", "$EndEntities"]
+    lines += [f"{v} 0 0 0 1 1 1 1 {phys[n][1]} 0" for v, n in enumerate(vnames, start=1)]
+    lines.append("$EndEntities")
     # node blocks: runs of equal owner
     runs = []
     start = 0
@@ -227,7 +256,13 @@ def write_gmsh(tm: TetMesh, path: str, solid: str = "SOLID", surface_groups=("FI
     surf = [(k, f) for k, f in surf if len(f)]
     E = tm.element_count
     total = E + sum(len(f) for _, f in surf)
-    lines += ["$Elements", f"{1 + len(surf)} {total} 1 {total}"]
+    vruns = []  # runs of elements of the same volume
+    start = 0
+    for i in range(1, E + 1):
+        if i == E or evol[i] != evol[start]:
+            vruns.append((start, i))
+            start = i
+    lines += ["$Elements", f"{len(vruns) + len(surf)} {total} 1 {total}"]
     tag = 1
     hexes = tm.tets.shape[1] == 8  # Gmsh type 5 volumes with type 3 (quad) faces, else type 4 / type 2
     for k, f in surf:
@@ -235,10 +270,11 @@ def write_gmsh(tm: TetMesh, path: str, solid: str = "SOLID", surface_groups=("FI
         for face in f.tolist():
             lines.append(f"{tag} " + " ".join(str(v + 1) for v in face))
             tag += 1
-    lines.append(f"3 1 {5 if hexes else 4} {E}")
-    for t in tm.tets.tolist():
-        lines.append(f"{tag} " + " ".join(str(v + 1) for v in t))
-        tag += 1
+    for a, b in vruns:
+        lines.append(f"3 {int(evol[a]) + 1} {5 if hexes else 4} {b - a}")
+        for t in tm.tets[a:b].tolist():
+            lines.append(f"{tag} " + " ".join(str(v + 1) for v in t))
+            tag += 1
     lines.append("$EndElements")
     with open(path, "w") as fh:
         fh.write("\n".join(lines) + "\n")

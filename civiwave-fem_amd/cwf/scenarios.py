@@ -176,6 +176,62 @@ def rcb_case(key: str, nranks: int, max_iterations: int = 2000):
     return case, gid, begin
 
 
+# the strata materials of the layered cases: concrete, a soft soil, a stiffer soil
+LAYER_MATERIALS = (Material("m0", 30.0e9, 0.2, 2500.0), Material("m1", 3.0e9, 0.3, 1800.0),
+                   Material("m2", 12.0e9, 0.25, 2200.0))
+
+
+def layered_mesh(tm, element_material, materials=LAYER_MATERIALS):
+    """pack.Mesh of a TetMesh with one element group per material slot (group "SOLID<slot>", ids after the node
+    groups') and the matching (materials, assignments) of a Config."""
+    mesh = pack.from_tetmesh(tm)
+    first = max(mesh.group_names.values()) + 1
+    mesh.group_names.pop("SOLID")
+    for s in range(len(materials)):
+        mesh.group_names[f"SOLID{s}"] = first + s
+    mesh.element_group = (np.asarray(element_material, np.uint32) + np.uint32(first)).astype(np.uint32)
+    return mesh, list(materials), [Assignment(f"SOLID{s}", m.name) for s, m in enumerate(materials)]
+
+
+def layered_config(materials, assignments, **cfg_kw) -> Config:
+    from dataclasses import replace
+
+    return replace(make_config(**cfg_kw), materials=materials, assignments=assignments)
+
+
+def layered_case(nx, ny, nz, layers, h=0.1, element="tet4", materials=LAYER_MATERIALS, permute=False,
+                 **cfg_kw) -> Case:
+    """block_case with a material per cell layer along k: layers[kc] indexes `materials` (horizontal strata)."""
+    tm, emat = meshgen.layered_block(nx, ny, nz, layers, h, element)
+    if permute:  # node and element order permuted, no jitter: still a lattice for a handle that may renumber
+        prng = np.random.Generator(np.random.PCG64(42))  # jitter_and_permute's stream (seed_perm): the node
+        prng.permutation(tm.node_count)                  # permutation first, then the element permutation
+        emat = emat[prng.permutation(tm.element_count)]
+        tm = meshgen.jitter_and_permute(tm, h, jitter=0.0)
+    mesh, mats, asg = layered_mesh(tm, emat, materials)
+    cfg = layered_config(mats, asg, **cfg_kw)
+    tag = "hex" if element == "hex8" else "kuhn"
+    return Case(f"{tag}{nx}x{ny}x{nz}-layered", mesh, cfg, pack.build_packed_buffers(mesh, cfg))
+
+
+def layered_slab_case(shape, layers, planes, rank: int, h: float = 0.1, element: str = "tet4",
+                      materials=LAYER_MATERIALS, **cfg_kw):
+    """Slab shard `rank` of the layered block `shape` (cells) cut at the node planes `planes` ([nranks + 1], from 0
+    to nz + 1: rank r owns node planes [planes[r], planes[r + 1])), as slab_case_shape(stack=False) -> (case over the
+    sub-mesh, global node id per sub-mesh node, rank_node_begin)."""
+    nx, ny, nz = shape
+    A, B = nx + 1, ny + 1
+    assert planes[0] == 0 and planes[-1] == nz + 1
+    kc0, kc1 = max(planes[rank] - 1, 0), min(planes[rank + 1], nz)
+    tm, node_global, emat = meshgen.layered_slab(nx, ny, nz, layers, kc0, kc1, h, element)
+    mesh, mats, asg = layered_mesh(tm, emat, materials)
+    cfg = layered_config(mats, asg, **cfg_kw)
+    tag = "hex" if element == "hex8" else "kuhn"
+    case = Case(f"{tag}{nx}x{ny}x{nz}-layered/slab{rank}of{len(planes) - 1}", mesh, cfg,
+                pack.build_packed_buffers(mesh, cfg))
+    return case, node_global, np.asarray([p * A * B for p in planes], np.uint64)
+
+
 def roller_case(nx, ny, nz, h=0.1, element="tet4", **cfg_kw) -> Case:
     """Partial Dirichlet masks (config.hpp:208 constrain_axis): rollers on three faces -- x=0 fixed in x
     only (FIXED), y=0 in y only (SIDE), z=0 in z only (BOTTOM) -- which remove the rigid modes while most

@@ -166,6 +166,30 @@ const char *cwf_hip_system_keff_source_hash(const cwf_hip_system *h);
  * without CWF_DESC_KEEP_NODE_ORDER may apply. */
 #define CWF_LATTICE_COEFS 549
 int cwf_lattice_describe(const cwf_system_desc *desc, int renumber, uint32_t dims[3], float *coef, uint32_t *plane);
+/* The same for layered blocks (host only, no device): a structured tet4 or hex8 block whose material is constant
+ * within every k-layer of cells (cell layer kc: the cells between node planes kc and kc + 1) runs the per-plane
+ * stencil tables of k_keff_lattice_layered; cwf_lattice_describe returns 0 for it. Returns 1 for a layered or a
+ * one-material lattice and fills dims (nodes per axis, no flag bits) and info = {materials, plane classes, 1 when
+ * hex8, 1 when the stencil pairs S_(-d) = S_d (one material only)}; 0 when the desc is no lattice (materials varying
+ * inside a cell layer, more than CWF_LATTICE_MAX_MATERIALS materials or CWF_LATTICE_MAX_PLANE_CLASSES classes among
+ * the reasons); CWF_ERR_SIZE when a wanted array's capacity is too small (dims and info are filled, so a caller can
+ * size and call again); another negative cwf_status on bad arguments. Every array may be NULL (not wanted):
+ *   plane [dims[2]] storage index of node (0, 0, k), plane_class [dims[2]], layer_material [dims[2] - 1] the desc's
+ *   material index of each cell layer (capacity plane_capacity entries each);
+ *   class_pair [2 classes] (material below, material above) of each class -- the end planes take their one layer
+ *   twice --, class_coef [classes][offsets][3][3] row-major stencil blocks unscaled by stiffness_scale, offsets = 15
+ *   (tet4) or 27 (hex8): S_d = sum over the node's corner positions c of Kc^m[c][c + d], m the material below for
+ *   corners with z-bit 1 and above for z-bit 0, fp64 rounded to f32 once (capacity class_capacity classes);
+ *   material_ids [materials] the desc's material index of each material slot, pair_coef [materials][pairs][3][3] the
+ *   cell-pair blocks of each slot, pairs = 46 (tet4) or 64 (hex8) (capacity material_capacity slots).
+ * A one-material block has one class whose tables are cwf_lattice_describe's, bit for bit. */
+#define CWF_LATTICE_MAX_MATERIALS 8
+#define CWF_LATTICE_MAX_PLANE_CLASSES 16
+int cwf_lattice_describe_layers(const cwf_system_desc *desc, int renumber, uint32_t dims[3], uint32_t info[4],
+                                uint32_t plane_capacity, uint32_t *plane, uint32_t *plane_class,
+                                uint32_t *layer_material, uint32_t class_capacity, uint32_t *class_pair,
+                                float *class_coef, uint32_t material_capacity, uint32_t *material_ids,
+                                float *pair_coef);
 
 /* Live kernel timing (measurement support, not a reference interface): when enabled, every
  * K_eff launch inside solve_pcg / stepper_step is bracketed by hipEvents on the handle's stream;
