@@ -410,6 +410,15 @@ struct cwf_hip_system
     std::vector<uint32_t> lat_plane;  // structured block: host copy of ds.t.lplane (attach derives the owned planes)
     uint64_t last_iters = 0, prev_iters = 0;  // iterations of the last two solves on this handle (first batch size)
     std::string err, ctx;
+    // modal analysis workspace (modal.cpp), allocated at the first block call and kept in `owned`: three blocks of
+    // mo_cols columns [3][mo_cols][D], the Gram chunk partials followed by two q x q results and one rotation (fp64),
+    // and, on a renumbered handle, the lumped mass and mask in the caller's node order (the public block calls weight
+    // caller-order vectors in place)
+    float *mo_blk = nullptr;
+    uint32_t mo_cols = 0;
+    double *mo_f64 = nullptr;
+    float *mo_mass = nullptr;
+    uint32_t *mo_mask = nullptr;
     // live K_eff timing (cwf_hip_system_set_timing)
     int timing = 0;
     std::vector<hipEvent_t> ev;  // 2 per enqueued iteration of one batch

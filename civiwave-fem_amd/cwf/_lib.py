@@ -54,6 +54,17 @@ class PcgTelemetryC(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class ModalSettingsC(C.Structure):
+    _fields_ = [("modes", C.c_uint32), ("block", C.c_uint32), ("max_outer", C.c_uint32), ("reserved", C.c_uint32),
+                ("tolerance", C.c_double), ("shift", C.c_double), ("pcg", PcgSettingsC)]
+
+
+class ModalTelemetryC(C.Structure):
+    _fields_ = [("outer_iterations", C.c_uint32), ("converged", C.c_uint32), ("block", C.c_uint32),
+                ("reserved", C.c_uint32), ("pcg_iterations", C.c_uint64), ("max_change", C.c_double),
+                ("solve_ms", C.c_double), ("block_ms", C.c_double)]
+
+
 class StepperDescC(C.Structure):
     _fields_ = [
         ("rayleigh_alpha", C.c_double), ("rayleigh_beta", C.c_double), ("runtime_tolerance", C.c_double),
@@ -150,6 +161,9 @@ def load() -> C.CDLL:
         "cwf_hip_dot": ([P, P, P, u64, i32, P, P], i32),
         "cwf_hip_solve_pcg": ([P, P, P, P, P, u64, i32, P], i32),
         "cwf_hip_residual_history": ([P, P, u64, P], i32),
+        "cwf_hip_modal_solve": ([P, P, P, P, i32, P], i32),
+        "cwf_hip_block_gram": ([P, P, C.c_uint32, P, C.c_uint32, i32, P, i32], i32),
+        "cwf_hip_block_rotate": ([P, P, C.c_uint32, P, C.c_uint32, P, P, i32], i32),
         "cwf_hip_stepper_create": ([P, P, P], i32),
         "cwf_hip_stepper_destroy": ([P], None),
         "cwf_hip_stepper_step": ([P, f64, i32, P], i32),

@@ -240,6 +240,58 @@ int cwf_hip_solve_pcg(cwf_hip_system *h, const float *rhs, const cwf_pcg_setting
 int cwf_hip_residual_history(cwf_hip_system *h, double *out, uint64_t capacity, uint64_t *count);
 
 /* ---------------------------------------------------------------------------------------
+ * Modal analysis (no reference counterpart): the `modes` lowest eigenpairs of K phi = lambda M phi, K the
+ * handle's stiffness, M its lumped mass, Dirichlet DOFs held at zero. Subspace iteration with Rayleigh-Ritz
+ * (Bathe) over a block of `block` vectors: each outer iteration solves (K + shift M) xbar_j = M x_j with the
+ * handle's own PCG, in whatever schedule the handle's solves take, projects K and M onto the block on the device
+ * (fp64 Gram matrices), solves the small problem on the host and rotates the block. A FAST tet4 handle ends with one
+ * more Rayleigh-Ritz step in the PARITY operator's fp64 element math, so the eigenvalues returned are K's, not those
+ * of FAST's f32 approximation of it (its PARITY node tiles are built at the first such call). For the duration of the call the
+ * handle runs with scalars (1, shift); the caller's scalars are back on every return, errors included.
+ * shift > 0 moves the spectrum, (K + shift M) phi = (lambda + shift) M phi, and makes a structure without enough
+ * supports solvable; shift = 0 needs K definite on the free DOFs. A sharded handle (one attached to a communicator)
+ * is refused with CWF_ERR_UNSUPPORTED: modal analysis across shards is not built.
+ * ------------------------------------------------------------------------------------- */
+#define CWF_MODAL_MAX_BLOCK 32
+typedef struct cwf_modal_settings
+{
+    uint32_t modes, block, max_outer, reserved; /* block 0 = min(2 modes, modes + 8); max_outer 0 = 40; reserved
+                                                   0 (bit 0, evaluation only: project K with `block` extra operator
+                                                   applies per outer iteration instead of reusing the solves'
+                                                   right-hand sides) */
+    double tolerance, shift;                    /* tolerance 0 = 1e-6: largest relative change of the `modes`
+                                                   lowest Ritz values lambda + shift between outer iterations */
+    cwf_pcg_settings pcg; /* inner solves; relative_tolerance 0 = 1e-6, max_iterations 0 = 20000; warm_start is
+                             the solver's own business (Ritz-scaled starts) and is ignored */
+} cwf_modal_settings;
+typedef struct cwf_modal_telemetry
+{
+    uint32_t outer_iterations, converged, block, reserved; /* converged 0 at max_outer is not an error */
+    uint64_t pcg_iterations;                               /* over every inner solve */
+    double max_change, solve_ms, block_ms; /* hipEvent time in the solves / in gram + fold + rotate */
+} cwf_modal_telemetry;
+/* eigenvalues [modes] ascending, fp64 (lambda_i = Ritz value - shift). modes_out (nullable) [modes * 3N], mode i at
+ * [i * 3N], in the caller's node order, host or device by ptr_kind: M-orthonormal, constrained DOFs exactly 0, each
+ * signed so that its component of largest magnitude (ties: the lowest DOF) is positive. The same handle and
+ * settings give the same bits on every call. Errors: CWF_ERR_ARGUMENT naming the field for modes == 0, block <
+ * modes, block > CWF_MODAL_MAX_BLOCK, shift < 0, tolerance < 0, 3N < block or a NULL pointer; CWF_ERR_UNSUPPORTED
+ * for a sharded handle; a PCG failure keeps its code and text, its context extended by "outer=<i>" and
+ * "column=<j>"; CWF_ERR_DENOM_ZERO "Ritz mass matrix is not positive definite" when the block lost rank. */
+int cwf_hip_modal_solve(cwf_hip_system *h, const cwf_modal_settings *s, double *eigenvalues, float *modes_out,
+                        int ptr_kind, cwf_modal_telemetry *tel);
+/* G [qa x qb] row-major (host, fp64) = A^T W B for two blocks of contiguous f32 [3N] columns (column j at A + j 3N;
+ * host or device by ptr_kind, caller's node order), 1 <= qa, qb <= CWF_MODAL_MAX_BLOCK. W = I, or with
+ * mass_weighted the lumped mass on free DOFs and 0 on constrained ones. Products and sums are fp64; the rows are cut
+ * into fixed chunks folded in ascending order, so the bits depend on the inputs alone. */
+int cwf_hip_block_gram(cwf_hip_system *h, const float *A, uint32_t qa, const float *B, uint32_t qb,
+                       int mass_weighted, double *G, int ptr_kind);
+/* X_out [q_out columns] = X [q_in columns] Q, Q [q_in x q_out] row-major host fp64: fp64 accumulation rounded to f32
+ * once; MX_out (nullable) = W X_out with the mass weight above (constrained rows 0). Out of place: X_out and MX_out
+ * must not overlap X. */
+int cwf_hip_block_rotate(cwf_hip_system *h, const float *X, uint32_t q_in, const double *Q, uint32_t q_out,
+                         float *X_out, float *MX_out, int ptr_kind);
+
+/* ---------------------------------------------------------------------------------------
  * Newmark stepper: cwf::gpu::newmark::Stepper (newmark_stepper.hpp:92-190). Device-resident
  * node state (u, v, a, predictor, external force, bc values); one step = predictor -> RHS
  * (+ beta_R * K * d when beta_R != 0) -> Dirichlet clamp -> PCG -> corrector -> adaptive dt.

@@ -257,6 +257,62 @@ inline expected<cwf_hip_system *, PcgError> bind(const MatrixFreeSystem &s, Matr
 
 }  // namespace pcg
 
+// Modal analysis (cwf_hip_modal_solve; no reference counterpart): the lowest eigenpairs of K phi = lambda M phi.
+namespace modal
+{
+
+struct ModalSettings
+{
+    std::uint32_t modes{6};
+    std::uint32_t block{0};       // 0: min(2 modes, modes + 8)
+    std::uint32_t max_outer{40};
+    double tolerance{1.0e-6};
+    double shift{0.0};
+    pcg::PcgSettings pcg{20000, 1.0e-6, false};  // inner solves
+};
+
+struct ModalTelemetry
+{
+    std::uint32_t outer_iterations{0};
+    bool converged{false};
+    std::uint32_t block{0};
+    std::uint64_t pcg_iterations{0};
+    double max_change{0.0}, solve_ms{0.0}, block_ms{0.0};
+};
+
+struct ModalResult
+{
+    std::vector<double> eigenvalues;  // lambda, ascending
+    std::vector<float> modes;         // [modes * dof_count], M-orthonormal, mode i at [i * dof_count]
+    ModalTelemetry telemetry;
+};
+
+[[nodiscard]] inline auto solve(const pcg::MatrixFreeSystem &system, const ModalSettings &settings,
+                                pcg::MatrixFreeWorkspace &workspace) -> expected<ModalResult, pcg::PcgError>
+{
+    auto h = pcg::detail::bind(system, workspace);
+    if (!h)
+        return unexpected<pcg::PcgError>{h.error()};
+    cwf_modal_settings cs{};
+    cs.modes = settings.modes;
+    cs.block = settings.block;
+    cs.max_outer = settings.max_outer;
+    cs.tolerance = settings.tolerance;
+    cs.shift = settings.shift;
+    cs.pcg = cwf_pcg_settings{settings.pcg.max_iterations, settings.pcg.relative_tolerance, 0, 0};
+    ModalResult r;
+    r.eigenvalues.resize(settings.modes);
+    r.modes.resize(static_cast<std::size_t>(settings.modes) * system.dof_count);
+    cwf_modal_telemetry t{};
+    if (cwf_hip_modal_solve(*h, &cs, r.eigenvalues.data(), r.modes.data(), CWF_PTR_HOST, &t) != 0)
+        return unexpected<pcg::PcgError>{pcg::detail::last(*h)};
+    r.telemetry = ModalTelemetry{t.outer_iterations, t.converged != 0, t.block, t.pcg_iterations,
+                                 t.max_change,       t.solve_ms,       t.block_ms};
+    return r;
+}
+
+}  // namespace modal
+
 namespace newmark
 {
 
