@@ -698,7 +698,7 @@ static int layout_lattice(cwf_hip_system *h, const cwf_system_desc *d, Lattice &
     // A layered block carries no class preconditioner, even where every density is equal: a node's block inverse
     // depends on the material pair of its plane, which the 27 boundary types x mask classes do not tell apart. So
     // lcls, lcz, lmu and lzr stay off, and with lcls off the resident solve (resident.cpp), the fused one-launch
-    // iteration (fast_fused) and z-from-r all decline the handle: it runs the two-kernel loop on the per-node inverse.
+    // iteration (schedule.cpp) and z-from-r all decline the handle: it runs the two-kernel loop on the per-node inverse.
     LatticeClasses lc;
     if (lat.layered)
         lc.uniform = false;
@@ -1176,15 +1176,16 @@ int cwf_hip_system_keff_traffic(const cwf_hip_system *h, uint64_t *layout_bytes,
         // hex8: 16-B corner ids + 16-B positions per hex (no material stream for one material)
         // fan groups: 16-B group record (ids, push ranks, tet count, material) instead of the per-tet records
         const uint64_t rec = s.t.hex ? 32 : s.t.geo ? 16 : 56;
-        if (s.t.lat && fast_fused(h) && resident_on(h))
+        const PcgSchedule sch = schedule_of(h);
+        if (sch == PcgSchedule::Resident)
         {  // the resident solve (resident.hip), per iteration: only what crosses a CU -- the halo records read, the
            // box-surface records and the shares written, the G x 5 shares read -- the vectors stay on chip
             *layout_bytes = resident_offchip_bytes(h);
             return 0;
         }
-        if (s.t.lat && fast_fused(h) && h->fused_agreed != 0)  // the fused iteration (lattice_fused.inc): per owned node r_(j-1), Ap_(j-1),
-        {                              // p_(j-1), the class byte and x read, r_j, p_j, Ap_j and x written; the mass
-                                       // of the shell's nodes (the strict interior's is one value when lmu)
+        if (sch == PcgSchedule::Fused || sch == PcgSchedule::FusedPeer)
+        {  // the fused iteration (lattice_fused.inc): per owned node r_(j-1), Ap_(j-1), p_(j-1), the class byte and x
+           // read, r_j, p_j, Ap_j and x written; the mass of the shell's nodes (the strict interior's is one value when lmu)
             *layout_bytes = (uint64_t)s.Nown * (4 * 12 + 1 + 4 * 12) + 4ull * (s.t.lmu ? s.t.lnshell : s.Nown);
             return 0;
         }
@@ -1229,9 +1230,7 @@ const char *cwf_hip_system_keff_source_hash(const cwf_hip_system *h)
 
 int cwf_hip_system_exchange_schedule(const cwf_hip_system *h)
 {
-    if (!h || !h->sharded() || h->fused_agreed < 0)
-        return -1;
-    return h->fused_agreed == 0 ? 0 : h->res_agreed == 1 ? 3 : h->px_agreed == 1 ? 2 : 1;
+    return h && h->sharded() ? exchange_schedule_code(h->sched) : -1;
 }
 
 const char *cwf_hip_system_keff_kernel(const cwf_hip_system *h)
@@ -1249,20 +1248,21 @@ const char *cwf_hip_system_keff_kernel(const cwf_hip_system *h)
             return h->ds.iso ? "k_keff_parity_tile<true, false, false, true>" : "k_keff_parity_tile<false, false, false, true>";
         return h->ds.iso ? "k_keff_parity_tile<true, false, true, false>" : "k_keff_parity_tile<false, false, true, false>";
     }
-    if (t.lat && fast_fused(h) && resident_on(h))
+    const PcgSchedule sch = schedule_of(h);
+    if (sch == PcgSchedule::Resident)
     {  // the resident solve's one launch per solve (resident.hip)
         static thread_local char name[96];
         snprintf(name, sizeof name, "k_pcg_resident<%s, %s, %u, %u, %s>", t.lsym ? "true" : "false",
                  t.lhex ? "LatHex" : "LatKuhn", h->res.npt, h->res.nph, h->res.shard ? "true" : "false");
         return name;
     }
-    if (t.lat && fast_fused(h) && h->fused_agreed != 0)  // the fused iteration's one launch (lattice_fused.inc)
+    if (sch == PcgSchedule::Fused || sch == PcgSchedule::FusedPeer)  // the fused iteration's one launch (lattice_fused.inc)
     {
         static thread_local char name[112];
         snprintf(name, sizeof name, "k_pcg_lattice<%s, %s, %s, %s, %s, %s>", t.lsym ? "true" : "false",
                  t.lhex ? "LatHex" : "LatKuhn", t.lmu ? "true" : "false", t.lpstride ? "true" : "false",
                  !t.lpstride && h->ds.Nown < h->ds.N ? "true" : "false",
-                 h->fused_grid < t.lnwork ? "true" : "false");
+                 h->sched.grid < t.lnwork ? "true" : "false");
         return name;
     }
     if (t.lat && t.llayers)

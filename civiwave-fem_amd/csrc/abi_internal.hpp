@@ -150,7 +150,36 @@ int stage_vec(cwf_hip_system *h, const float *src, float *scratch, int kind, int
 int vec_in(cwf_hip_system *h, const float *src, float *dst, int kind, int w);
 int vec_out(cwf_hip_system *h, const float *src, float *dst, int kind, int w);
 std::vector<uint32_t> morton_node_order(const double *X, uint64_t N);
-std::string pcg_error_message(int code, int iter, std::string *ctx);
+// schedule.cpp: the facts a handle's PCG schedule is chosen from (a shard's: with every rank's vote gathered in `all`)
+struct ScheduleVote
+{
+    bool fuse = false, peer = false, resident = false;  // the fused iteration; its in-kernel PEER exchange; the resident solve
+};
+struct ScheduleFacts
+{
+    int mode = CWF_MODE_PARITY;
+    bool fusable = false;        // a structured block with the fused launch's tables and buffers
+    bool grid_covers = false;    // the fused grid runs every work item in one round
+    int fused_knob = -1;         // CWF_FUSED: -1 unset, else 0 / 1 / 2
+    bool resident_off = false;   // CWF_RESIDENT=0
+    bool resident_plan = false;  // a resident plan could be made
+    bool sharded = false;
+    bool thick_slab = false;     // a shard: it owns at least two node planes
+    int group = 1;               // members driven from this process (a LOCAL communicator: every rank)
+    bool peer_eligible = false;  // a shard: peer_fused_eligible
+    ScheduleVote all;            // a shard: what every rank voted for
+};
+ScheduleVote own_vote(const ScheduleFacts &f);        // pure: what the handle could run were it alone
+SchedulePlan choose_schedule(const ScheduleFacts &f);  // pure: the handle's plan (state, launch, resident)
+PcgSchedule solve_schedule(const SchedulePlan &p, uint64_t max_iterations);  // pure: one solve's schedule
+int exchange_schedule_code(const SchedulePlan &p);  // cwf_hip_system_exchange_schedule's value for a shard's plan
+// plans every member of a group at its first FAST solve (the knobs, the fused grid, the resident plan; shards: the
+// collective vote, whose failure is an error); later calls return at once
+int plan_schedule(const std::vector<cwf_hip_system *> &g);
+// what the handle's solves run (Resident where the plan has it); plans an unplanned handle as its first solve would
+PcgSchedule schedule_of(const cwf_hip_system *h);
+// sch: the schedule that ran
+std::string pcg_error_message(int code, int iter, PcgSchedule sch, std::string *ctx);
 // solve_pcg on device buffers for a group (one handle, or every rank of a LOCAL sharded system)
 int run_pcg_group(const std::vector<cwf_hip_system *> &g, const std::vector<const float *> &rhs,
                   const cwf_pcg_settings &set, cwf_pcg_telemetry *tel);

@@ -11,19 +11,14 @@
 namespace cwf
 {
 
-std::string pcg_error_message(int code, int iter, std::string *ctx)
+std::string pcg_error_message(int code, int iter, PcgSchedule sch, std::string *ctx)
 {
-    if (code == CWF_ERR_DENOM_ZERO)
-    {
-        *ctx = "iteration=" + std::to_string(iter);
-        return "CG denominator approached zero";  // pcg.cpp:846-849
-    }
     if (code == CWF_ERR_COMM)  // a PEER exchange step's bounded wait (peer.hip): a peer never arrived
     {
         *ctx = "step=" + std::to_string(iter);
         return "peer exchange timed out";
     }
-    if (code == CWF_ERR_HIP)  // resident.hip: a workgroup did not reach a phase within its bounded wait
+    if (code == CWF_ERR_HIP && sch == PcgSchedule::Resident)  // resident.hip: a phase's bounded wait ran out
     {
         *ctx = "phase=" + std::to_string(iter);
         return "resident solve: a workgroup missed the phase barrier";
@@ -34,11 +29,17 @@ std::string pcg_error_message(int code, int iter, std::string *ctx)
         return "preconditioner produced near-zero rho";  // pcg.cpp:810-813
     }
     *ctx = "iteration=" + std::to_string(iter);
+    if (code == CWF_ERR_DENOM_ZERO)
+        return "CG denominator approached zero";  // pcg.cpp:846-849
+    if (code == CWF_ERR_HIP)  // kernels_parity.hip stream_fail: the chunk partials of a streamed fold never all arrived
+        return "PARITY streamed scalar fold timed out";
     return "CG rho approached zero";  // pcg.cpp:889-892
 }
 
+namespace
+{
 // the solve's telemetry and error from the control block read back last (every member's is identical)
-int pcg_finish(const std::vector<cwf_hip_system *> &g, cwf_pcg_telemetry *tel)
+int pcg_finish(const std::vector<cwf_hip_system *> &g, PcgSchedule sch, cwf_pcg_telemetry *tel)
 {
     cwf_hip_system *h = g[0];
     const Ctl &c = *h->ctl_host;
@@ -61,7 +62,7 @@ int pcg_finish(const std::vector<cwf_hip_system *> &g, cwf_pcg_telemetry *tel)
     if (c.error)
     {
         std::string ctx;
-        std::string msg = pcg_error_message(c.error, c.error_iter, &ctx);
+        std::string msg = pcg_error_message(c.error, c.error_iter, sch, &ctx);
         for (size_t i = 1; i < g.size(); ++i)
             set_error(g[i], c.error, msg, ctx);
         return set_error(h, c.error, msg, ctx);
@@ -69,42 +70,118 @@ int pcg_finish(const std::vector<cwf_hip_system *> &g, cwf_pcg_telemetry *tel)
     return 0;
 }
 
-// the resident solve: fast_fused_init (block inverse, r_0, norms, tolerance), then ONE launch that runs every
-// iteration on chip (resident.hip) and leaves x, r and the control block; hipEvent-timed as a whole when timing is on
-// (the handle's K_eff timing then counts its iterations: avg = the time per iteration). A PEER slab shard (one member
-// per process): the sharded prologue instead of fast_fused_init, ghost x from the owners after the solve
-int run_pcg_resident(cwf_hip_system *h, const float *rhs, const cwf_pcg_settings &set, cwf_pcg_telemetry *tel)
+// a timed handle's events, two per launch of the largest batch (no L2 write-back per timed launch)
+int timing_events(cwf_hip_system *h, size_t n)
+{
+    const size_t had = h->ev.size();
+    if (!h->timing || had >= n)
+        return 0;
+    h->ev.resize(n);
+    for (size_t i = had; i < n; ++i)
+        HIPTRY(h, hipEventCreateWithFlags(&h->ev[i], hipEventDisableSystemFence));
+    return 0;
+}
+
+// ---- the four steps of a solve, by schedule (a shard's group g: every member driven here; else g = {h}) -----------
+// r_0, the norms, the tolerance and what the schedule's first launch reads. Resident: the fused init without its
+// launch 0 (the one launch runs phase 0 itself)
+int pcg_init(PcgSchedule sch, const std::vector<cwf_hip_system *> &g, const std::vector<const float *> &rhs, double tol)
+{
+    cwf_hip_system *h = g[0];
+    const bool sharded = h->sharded();
+    switch (sch)
+    {
+    case PcgSchedule::Resident:
+        return sharded ? sharded_resident_init(g, rhs, tol) : (fast_fused_init(h, rhs[0], tol, h->stream, false), 0);
+    case PcgSchedule::Fused:
+    case PcgSchedule::FusedPeer:
+        return sharded ? sharded_fused_init(g, rhs, tol, sch) : (fast_fused_init(h, rhs[0], tol, h->stream), 0);
+    case PcgSchedule::TwoKernel:
+        return sharded ? sharded_pcg_init(g, rhs, tol) : (fast_pcg_init(h, rhs[0], tol, h->stream), 0);
+    case PcgSchedule::Parity:
+        return sharded ? sharded_parity_init(g, rhs, tol) : (parity_pcg_init(h, rhs[0], tol, h->stream), 0);
+    }
+    return 0;
+}
+
+// iteration `it` of a launch-per-iteration schedule (member 0's launch carries the timing events)
+int pcg_iteration(PcgSchedule sch, const std::vector<cwf_hip_system *> &g, const std::vector<const float *> &rhs,
+                  unsigned it, hipEvent_t e0, hipEvent_t e1)
+{
+    cwf_hip_system *h = g[0];
+    const bool sharded = h->sharded();
+    switch (sch)
+    {
+    case PcgSchedule::Fused:
+    case PcgSchedule::FusedPeer:
+        return sharded ? sharded_fused_iteration(g, it, e0, e1, sch) : (fast_fused_iteration(h, it, h->stream, e0, e1), 0);
+    case PcgSchedule::TwoKernel:
+        return fast_pcg_iteration_group(g, rhs, it, e0, e1);
+    case PcgSchedule::Parity:
+        return sharded ? sharded_parity_iteration(g, rhs, e0, e1) : (parity_pcg_iteration(h, rhs[0], h->stream, e0, e1), 0);
+    case PcgSchedule::Resident:  // (no launch per iteration)
+        break;
+    }
+    return 0;
+}
+
+// after a batch (`it` iterations enqueued in all): the convergence of its last launch (Fused) or last update
+// (TwoKernel), repeated idempotently by the next launch's start. PARITY decides in its own kernels
+void pcg_batch_check(PcgSchedule sch, const std::vector<cwf_hip_system *> &g, unsigned it)
+{
+    switch (sch)
+    {
+    case PcgSchedule::Fused:
+    case PcgSchedule::FusedPeer:
+        for (cwf_hip_system *m : g)
+            fast_fused_check(m, it, m->stream);
+        break;
+    case PcgSchedule::TwoKernel:
+        for (cwf_hip_system *m : g)
+            fast_check_pcg(m, it, m->stream);
+        break;
+    default:
+        break;
+    }
+}
+
+// after the last batch: the solve's x and r where the schedule left them pending
+int pcg_flush(PcgSchedule sch, const std::vector<cwf_hip_system *> &g, const std::vector<const float *> &rhs)
+{
+    switch (sch)
+    {
+    case PcgSchedule::Fused:  // x is updated in every launch; the solve's r output is the last launch's
+    case PcgSchedule::FusedPeer:
+        for (cwf_hip_system *m : g)
+            fast_fused_finish(m, m->stream);
+        return g[0]->sharded() ? sharded_fused_end(g, sch) : 0;
+    case PcgSchedule::TwoKernel:  // x += alpha_j p_j of the iterations since the last lazy x update
+        for (size_t i = 0; i < g.size(); ++i)
+            fast_flush_x(g[i], rhs[i], g[i]->stream);
+        return 0;
+    default:
+        return 0;
+    }
+}
+
+// the resident solve after its init: ONE launch that runs every iteration on chip (resident.hip) and leaves x, r and
+// the control block; hipEvent-timed as a whole when timing is on (the handle's K_eff timing then counts its
+// iterations: avg = the time per iteration). A PEER slab shard (one member per process): ghost x from the owners
+// after the solve
+int run_pcg_resident(cwf_hip_system *h, const cwf_pcg_settings &set, cwf_pcg_telemetry *tel)
 {
     hipStream_t st = h->stream;
-    const bool shard = h->sharded();
-    if (shard)
-    {
-        if (int e = sharded_resident_init({h}, {rhs}, set.relative_tolerance))
-            return e;
-    }
-    else
-        fast_fused_init(h, rhs, set.relative_tolerance, st, false);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (h->timing)
-    {
-        if (h->ev.size() < 2)
-        {
-            const size_t had = h->ev.size();
-            h->ev.resize(2);
-            for (size_t i = had; i < 2; ++i)
-                HIPTRY(h, hipEventCreateWithFlags(&h->ev[i], hipEventDisableSystemFence));
-        }
-        e0 = h->ev[0];
-        e1 = h->ev[1];
-    }
-    const uint32_t max_it = (uint32_t)std::min<uint64_t>(set.max_iterations, 1u << 24);
+    if (int e = timing_events(h, 2))
+        return e;
+    hipEvent_t e0 = h->timing ? h->ev[0] : nullptr, e1 = h->timing ? h->ev[1] : nullptr;
+    const uint32_t max_it = (uint32_t)set.max_iterations;  // (<= 2^24: solve_schedule)
     launch_pcg_resident(h, max_it, st, e0, e1);
     // the next solve's tags start past every tag this one can publish (phases 0 .. max_it + 1)
     h->res.tag += max_it + 3u;
     HIPTRY(h, hipGetLastError());
     HIPTRY(h, hipMemcpyAsync(h->ctl_host, h->ctl, sizeof(Ctl), hipMemcpyDeviceToHost, st));
     HIPTRY(h, hipStreamSynchronize(st));
-    if (shard && !h->ctl_host->error)  // ghost x <- owners (the stepper's node-wise updates read the ghost rows too)
+    if (h->sharded() && !h->ctl_host->error)  // ghost x <- owners (the stepper's node-wise updates read the ghost rows too)
     {
         if (int e = comm_halo({h}, &cwf_hip_system::x))
             return e;
@@ -119,8 +196,9 @@ int run_pcg_resident(cwf_hip_system *h, const float *rhs, const cwf_pcg_settings
             h->keff_count += h->ctl_host->iterations;
         }
     }
-    return pcg_finish({h}, tel);
+    return pcg_finish({h}, PcgSchedule::Resident, tel);
 }
+}  // namespace
 
 // run solve_pcg on device buffers: rhs[i] and g[i]->x (holding the warm start) for every member of a
 // group -- one handle, or every rank of a sharded system driven from this process (LOCAL comm).
@@ -153,34 +231,15 @@ int run_pcg_group(const std::vector<cwf_hip_system *> &g, const std::vector<cons
     if (!set.warm_start)
         for (cwf_hip_system *m : g)
             HIPTRY(m, hipMemsetAsync(m->x, 0, m->ds.D * sizeof(float), m->stream));
-    const bool fast = h->mode == CWF_MODE_FAST;
-    // one launch per iteration (lattice_fused.inc); shards: one exchange per iteration, agreed by every rank
-    int gf = 0;
-    if (fast && sharded && (gf = group_fused(g)) < 0)
-        return gf;
-    const bool fused = fast && (sharded ? gf == 1 : fast_fused(h));
-    // a block that fits on chip: the whole solve in one launch (resident.hip)
-    if (fused && !sharded && set.max_iterations <= (1u << 24) && resident_ready(h))
-        return run_pcg_resident(h, rhs[0], set, tel);
-    if (fused && sharded && g.size() == 1 && h->res_agreed == 1 && set.max_iterations <= (1u << 24))
-        return run_pcg_resident(h, rhs[0], set, tel);
-    if (fused && sharded)
-    {
-        if (int e = sharded_fused_init(g, rhs, set.relative_tolerance))
-            return e;
-    }
-    else if (fused)
-        fast_fused_init(h, rhs[0], set.relative_tolerance, st);
-    else if (sharded)
-    {
-        if (int e = fast ? sharded_pcg_init(g, rhs, set.relative_tolerance)
-                         : sharded_parity_init(g, rhs, set.relative_tolerance))
-            return e;
-    }
-    else if (fast)
-        fast_pcg_init(h, rhs[0], set.relative_tolerance, st);
-    else
-        parity_pcg_init(h, rhs[0], set.relative_tolerance, st);
+    // the schedule: planned at the handle's first FAST solve (shards: agreed by every rank), one value per solve
+    if (int e = plan_schedule(g))
+        return e;
+    const PcgSchedule sch =
+        h->mode == CWF_MODE_FAST ? solve_schedule(h->sched, set.max_iterations) : PcgSchedule::Parity;
+    if (int e = pcg_init(sch, g, rhs, set.relative_tolerance))
+        return e;
+    if (sch == PcgSchedule::Resident)  // (one member: the plan is resident for a single handle or PEER shard only)
+        return run_pcg_resident(h, set, tel);
     HIPTRY(h, hipGetLastError());
     uint64_t enq = 0;
     constexpr uint64_t kMaxBatch = 64;
@@ -200,13 +259,8 @@ int run_pcg_group(const std::vector<cwf_hip_system *> &g, const std::vector<cons
         first = std::min<uint64_t>(lo - 24, kMaxFirstBatch);
         batch = 4;
     }
-    if (h->timing && h->ev.size() < 2 * std::max(first, kMaxBatch))
-    {
-        const size_t had = h->ev.size();
-        h->ev.resize(2 * std::max(first, kMaxBatch));
-        for (size_t i = had; i < h->ev.size(); ++i)
-            HIPTRY(h, hipEventCreateWithFlags(&h->ev[i], hipEventDisableSystemFence));  // no L2 write-back per timed launch
-    }
+    if (int e = timing_events(h, 2 * std::max(first, kMaxBatch)))
+        return e;
     uint64_t prev_enq = 0, prev_nb = 0;
     for (;;)
     {
@@ -238,32 +292,10 @@ int run_pcg_group(const std::vector<cwf_hip_system *> &g, const std::vector<cons
         {
             const bool timed = h->timing && (enq + i) % (uint64_t)h->timing == 0;
             hipEvent_t e0 = timed ? h->ev[2 * i] : nullptr, e1 = timed ? h->ev[2 * i + 1] : nullptr;
-            if (fused && sharded)
-            {
-                if (int e = sharded_fused_iteration(g, (unsigned)(enq + i), e0, e1))
-                    return e;
-            }
-            else if (fused)
-                fast_fused_iteration(h, (unsigned)(enq + i), st, e0, e1);
-            else if (fast)
-            {
-                if (int e = fast_pcg_iteration_group(g, rhs, (unsigned)(enq + i), e0, e1))
-                    return e;
-            }
-            else if (sharded)
-            {
-                if (int e = sharded_parity_iteration(g, rhs, e0, e1))
-                    return e;
-            }
-            else
-                parity_pcg_iteration(h, rhs[0], st, e0, e1);
+            if (int e = pcg_iteration(sch, g, rhs, (unsigned)(enq + i), e0, e1))
+                return e;
         }
-        if (fused)  // convergence of the batch's last launch (repeated idempotently by the next launch's start)
-            for (cwf_hip_system *m : g)
-                fast_fused_check(m, (unsigned)(enq + nb), m->stream);
-        else if (fast)  // convergence of the batch's last update (repeated idempotently by the next tiles kernel)
-            for (cwf_hip_system *m : g)
-                fast_check_pcg(m, (unsigned)(enq + nb), m->stream);
+        pcg_batch_check(sch, g, (unsigned)(enq + nb));
         HIPTRY(h, hipGetLastError());
         prev_enq = enq;
         prev_nb = nb;
@@ -271,17 +303,8 @@ int run_pcg_group(const std::vector<cwf_hip_system *> &g, const std::vector<cons
         if (set.check_interval <= 0)
             batch = std::min<uint64_t>(batch * 2, kMaxBatch);
     }
-    if (fused)  // x is updated in every launch; the solve's r output is the last launch's
-    {
-        for (cwf_hip_system *m : g)
-            fast_fused_finish(m, m->stream);
-        if (sharded)
-            if (int e = sharded_fused_end(g))
-                return e;
-    }
-    else if (fast)  // x += alpha_j p_j of the iterations since the last lazy x update
-        for (size_t i = 0; i < g.size(); ++i)
-            fast_flush_x(g[i], rhs[i], g[i]->stream);
+    if (int e = pcg_flush(sch, g, rhs))
+        return e;
     if (sharded)  // ghost x <- owners, so node-wise stepper updates stay consistent on ghost rows
     {
         if (int e = comm_halo(g, &cwf_hip_system::x))
@@ -289,7 +312,7 @@ int run_pcg_group(const std::vector<cwf_hip_system *> &g, const std::vector<cons
         for (cwf_hip_system *m : g)
             HIPTRY(m, hipStreamSynchronize(m->stream));
     }
-    return pcg_finish(g, tel);
+    return pcg_finish(g, sch, tel);
 }
 
 int run_pcg(cwf_hip_system *h, const float *rhs_dev, const cwf_pcg_settings &set, cwf_pcg_telemetry *tel)

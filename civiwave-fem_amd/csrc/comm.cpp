@@ -299,58 +299,6 @@ int fast_pcg_iteration_group(const std::vector<cwf_hip_system *> &g, const std::
 // group or PEER step (against two per iteration in the two-kernel schedule above). Every rank folds the gathered
 // totals in rank order, so every rank takes the same decisions.
 
-// every member (and, through one all-gather, every rank) can run it: the decision is collective, taken at a handle's
-// first sharded solve and kept (the shards' lattice plans do not change). 1 fused, 0 not, < 0 an error status
-int group_fused(const std::vector<cwf_hip_system *> &g)
-{
-    cwf_hip_system *h0 = g[0];
-    if (h0->fused_agreed >= 0)
-        return h0->fused_agreed == 1;
-    // a shard owning a single node plane keeps the two kernels: the fused launch's ghost-plane forms assume owned
-    // planes on both sides of a brick's first and last plane (slabs one cell thick did not converge fused, LOCAL and
-    // PEER alike; tests/test_gpu_lattice.py::test_thin_slab_shards_take_two_kernels)
-    bool mine = true;
-    for (cwf_hip_system *h : g)
-        mine = mine && fast_fused(h) && h->ds.t.lat && h->ds.t.lk1 >= h->ds.t.lk0 + 2;
-    // and the exchange inside the launches (PEER: one member per process); and the resident solve (PEER: every
-    // iteration in one launch, resident.hip), whose tag base every rank then takes from the largest (the ranks'
-    // granules must carry the same tags)
-    const bool px = mine && g.size() == 1 && peer_fused_eligible(h0);
-    const bool res = mine && g.size() == 1 && resident_shard_ready(h0);
-    for (cwf_hip_system *h : g)
-    {
-        const double v[2] = {mine ? 1.0 : 0.0, (px ? 1.0 : 0.0) + (res ? 2.0 : 0.0) + 4.0 * (double)h->res.tag};
-        HIPTRY(h, hipMemcpyAsync(h->g_init + 2 * h->rank, v, sizeof v, hipMemcpyHostToDevice, h->stream));
-        HIPTRY(h, hipStreamSynchronize(h->stream));
-    }
-    // a rank that cannot learn the others' votes must not pick a schedule alone (its peers could agree on
-    // the fused one and then wait for exchange steps it never runs): the solve fails instead, decided by nobody
-    if (int st = comm_allgather(g, &cwf_hip_system::g_init, 2))
-        return st < 0 ? st : set_error(h0, CWF_ERR_COMM, "schedule agreement all-gather failed");
-    std::vector<double> f(2 * (size_t)h0->nranks, 0.0);
-    HIPTRY(h0, hipStreamSynchronize(h0->stream));
-    HIPTRY(h0, hipMemcpy(f.data(), h0->g_init, f.size() * sizeof(double), hipMemcpyDeviceToHost));
-    bool all = true, all_px = true, all_res = true;
-    uint64_t tag = 0;
-    for (int r = 0; r < h0->nranks; ++r)
-    {
-        const uint64_t pv = (uint64_t)f[2 * (size_t)r + 1];
-        all = all && f[2 * (size_t)r] == 1.0;
-        all_px = all_px && (pv & 1u);
-        all_res = all_res && (pv & 2u);
-        tag = std::max<uint64_t>(tag, pv >> 2);
-    }
-    for (cwf_hip_system *h : g)
-    {
-        h->fused_agreed = all ? 1 : 0;
-        h->px_agreed = all && all_px ? 1 : 0;
-        h->res_agreed = all && all_res ? 1 : 0;
-        if (h->res_agreed)
-            h->res.tag = (uint32_t)tag;
-    }
-    return all ? 1 : 0;
-}
-
 namespace
 {
 // after launch j: the rank totals of its shares all-gathered into g_fsh, and Ap_j's ghost rows
@@ -415,16 +363,17 @@ int sharded_fused_prologue(const std::vector<cwf_hip_system *> &g, const std::ve
 }
 }  // namespace
 
-int sharded_fused_init(const std::vector<cwf_hip_system *> &g, const std::vector<const float *> &rhs, double rel_tol)
+int sharded_fused_init(const std::vector<cwf_hip_system *> &g, const std::vector<const float *> &rhs, double rel_tol,
+                       PcgSchedule sch)
 {
     if (int st = sharded_fused_prologue(g, rhs, rel_tol))
         return st;
-    if (g[0]->px_agreed == 1)  // the launches exchange themselves: epochs from here
+    if (sch == PcgSchedule::FusedPeer)  // the launches exchange themselves: epochs from here
         if (int st = peer_fused_begin(g[0]))
             return st;
     for (cwf_hip_system *h : g)
         fast_fused_launch0(h, h->stream);
-    return g[0]->px_agreed == 1 ? 0 : fused_exchange(g, 0);
+    return sch == PcgSchedule::FusedPeer ? 0 : fused_exchange(g, 0);
 }
 
 // the resident solve of PEER slab shards (resident.hip): the prologue only; the one launch then runs every
@@ -434,16 +383,17 @@ int sharded_resident_init(const std::vector<cwf_hip_system *> &g, const std::vec
     return sharded_fused_prologue(g, rhs, rel_tol);
 }
 
-int sharded_fused_iteration(const std::vector<cwf_hip_system *> &g, unsigned it, hipEvent_t e0, hipEvent_t e1)
+int sharded_fused_iteration(const std::vector<cwf_hip_system *> &g, unsigned it, hipEvent_t e0, hipEvent_t e1,
+                            PcgSchedule sch)
 {
     for (size_t i = 0; i < g.size(); ++i)
         fast_fused_iteration(g[i], it, g[i]->stream, i ? nullptr : e0, i ? nullptr : e1);
-    return g[0]->px_agreed == 1 ? 0 : fused_exchange(g, it + 1u);
+    return sch == PcgSchedule::FusedPeer ? 0 : fused_exchange(g, it + 1u);
 }
 
-int sharded_fused_end(const std::vector<cwf_hip_system *> &g)
+int sharded_fused_end(const std::vector<cwf_hip_system *> &g, PcgSchedule sch)
 {
-    return g[0]->px_agreed == 1 ? peer_fused_end(g[0]) : 0;
+    return sch == PcgSchedule::FusedPeer ? peer_fused_end(g[0]) : 0;
 }
 
 // ---- sharded PARITY (SURVEY.md 8e parity gate): the reference's fold orders across ranks --------------------
@@ -837,8 +787,10 @@ int cwf_hip_system_attach(cwf_hip_system *h, cwf_hip_comm *cm, int32_t rank, con
                 break;
             }
     h->pstride = 0;
-    {  // a resident plan made before the attach is the whole block's: re-planned for the shard (its tags go on)
+    {  // a schedule planned before the attach is the whole block's (its fused grid, its resident plan): the shard's
+       // work items are planned again at its first ask (the resident tags go on)
         const uint32_t tag = h->res.tag;
+        h->sched = cwf::SchedulePlan{};
         h->res = cwf::ResidentPlan{};
         h->res.tag = tag;
     }

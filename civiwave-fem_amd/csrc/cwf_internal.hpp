@@ -323,11 +323,35 @@ struct Ctl
     double alpha_h[kXLag];  // FAST: alpha of iteration j at [j % kXLag] (the lazy x update, spmv_tiles.hip)
 };
 
+// The schedule of a PCG solve (schedule.cpp decides it, once per handle; DESIGN.md section 3 "Which schedule runs")
+enum class PcgSchedule
+{
+    Parity,     // the reference's kernel sequence, fold orders included
+    TwoKernel,  // FAST: a K_eff pass and an update pass per iteration
+    Fused,      // one launch per iteration (lattice_fused.inc); shards: one exchange step after each launch
+    FusedPeer,  // ... whose launches exchange through the PEER mailboxes themselves
+    Resident,   // one launch per solve (resident.hip)
+};
+// a handle's FAST plan. Local: a shard's own half (its grid, and in `launch` what it could run alone), the ranks'
+// vote still to come; Decided: what its solves run
+struct SchedulePlan
+{
+    enum State
+    {
+        Unplanned,
+        Local,
+        Decided
+    } state = Unplanned;
+    unsigned grid = 0;    // the fused launch's grid
+    int fused_knob = -1;  // CWF_FUSED as it was at the plan: -1 unset, else its value
+    PcgSchedule launch = PcgSchedule::TwoKernel;  // the launch-per-iteration schedule
+    bool resident = false;  // the resident solve replaces it (solves of at most 2^24 iterations)
+};
+
 // the resident solve of a structured block (resident.hip, resident.cpp): one persistent launch per PCG solve, one
-// workgroup per box of the lattice, the vectors on chip. state: 0 not planned yet, 1 planned, -1 not eligible
+// workgroup per box of the lattice, the vectors on chip
 struct ResidentPlan
 {
-    int state = 0;
     unsigned G = 0, npt = 0, nph = 0;  // workgroups; own / halo entries per thread (the instantiation)
     unsigned own_stride = 0, halo_stride = 0, npub = 0;
     size_t lds = 0;                     // dynamic LDS: the largest box image
@@ -376,14 +400,10 @@ struct cwf_hip_system
     // a failed attach after the handle's plan was rewritten for its owned rows (comm.cpp cwf_hip_comm_attach): every
     // later call but destroy refuses the handle instead of computing a partial plan's rows
     bool unusable = false;
-    int fused_agreed = -1;    // a shard: every rank runs the fused iteration (1) or none (0); -1: not asked yet
-    int px_agreed = 0;        // ... and exchanges inside its launches (PEER, every rank eligible)
-    int res_agreed = 0;       // ... and every rank runs the resident solve (PEER slab shards, every rank eligible)
     int32_t px_send_k[2] = {-1, -1};  // the lattice plane of each neighbour slot's send segment
     uint32_t px_ebase = 0;            // the communicator's epoch before the solve's launch 0
-    unsigned fused_grid = 0, fused_items = 0;  // the fused launch's grid and the work items it was sized for
-    bool fused_on = false;                     // CWF_FUSED as it was when the handle first asked
-    cwf::ResidentPlan res;                     // the resident solve (resident.cpp), planned at the first FAST solve
+    cwf::SchedulePlan sched;          // which schedule FAST solves run (schedule.cpp), planned at the first ask
+    cwf::ResidentPlan res;            // the resident solve's data (resident.cpp), made by that plan
     float *inv = nullptr;   // block Jacobi [9N]; FAST: the symmetrised operator the solve applies
     float *inv6 = nullptr;  // FAST: the same block packed to 16 B per node (blockinv_pack.hpp)
     // inv / inv6 hold the FAST operator for (inv_sK, inv_sM): the block inverse depends only on the handle's
@@ -525,8 +545,8 @@ void fast_update_pcg(cwf_hip_system *h, const float *rhs, unsigned it, hipStream
 void fast_check_pcg(cwf_hip_system *h, unsigned it, hipStream_t st);
 void fast_flush_x(cwf_hip_system *h, const float *rhs, hipStream_t st);  // the lazy x terms still pending
 void fast_tiles_pcg_dry(cwf_hip_system *h, unsigned abl, int reps, hipStream_t st);
-// the fused lattice iteration (lattice_fused.inc): one launch per PCG iteration on an unsharded structured block
-bool fast_fused(const cwf_hip_system *h);
+// the fused lattice iteration (lattice_fused.inc): one launch per PCG iteration on a structured block
+unsigned pcg_lattice_launch_grid(const DevSys &s, unsigned cap);  // its grid, of at most cap workgroups
 void fast_fused_init(cwf_hip_system *h, const float *rhs, double rel_tol, hipStream_t st, bool launch0 = true);
 void fast_fused_iteration(cwf_hip_system *h, unsigned it, hipStream_t st, hipEvent_t e0 = nullptr,
                           hipEvent_t e1 = nullptr);
@@ -539,23 +559,23 @@ const double *fast_fused_shares(const cwf_hip_system *h, unsigned j, unsigned *s
 void fast_fused_cls_out(cwf_hip_system *h, hipStream_t st);  // owned class bytes -> tmp (x components)
 void fast_fused_cls_in(cwf_hip_system *h, hipStream_t st);   // ghost class bytes <- tmp
 constexpr size_t kFusedSlotHost = 8;  // doubles per rank of the gathered fused totals (lattice_fused.inc kFusedSlot)
-// comm.cpp: the sharded fused iteration (one launch + one exchange: the rank totals and the Ap halo)
-int sharded_fused_init(const std::vector<cwf_hip_system *> &g, const std::vector<const float *> &rhs, double rel_tol);
-int sharded_fused_iteration(const std::vector<cwf_hip_system *> &g, unsigned it, hipEvent_t e0, hipEvent_t e1);
-int group_fused(const std::vector<cwf_hip_system *> &g);  // 1 fused, 0 two-kernel, < 0 error
-// the resident solve (resident.cpp / resident.hip): whether this handle runs it (plans it at the first call; CWF_RESIDENT
-// = 0 turns it off), the launch (fast_fused_init has run; one launch runs every iteration) and its residency query
-bool resident_ready(cwf_hip_system *h);
+// comm.cpp: the sharded fused iteration (one launch + one exchange: the rank totals and the Ap halo; sch FusedPeer: the
+// launches exchange themselves)
+int sharded_fused_init(const std::vector<cwf_hip_system *> &g, const std::vector<const float *> &rhs, double rel_tol,
+                       PcgSchedule sch);
+int sharded_fused_iteration(const std::vector<cwf_hip_system *> &g, unsigned it, hipEvent_t e0, hipEvent_t e1,
+                            PcgSchedule sch);
+// the resident solve (resident.cpp / resident.hip): its plan over the whole block, or over a PEER slab shard's owned
+// planes (false: none fits; called by the schedule plan only), the launch (fast_fused_init has run; one launch runs
+// every iteration) and its residency query
+bool plan_resident(cwf_hip_system *h, bool shard);
 void launch_pcg_resident(cwf_hip_system *h, uint32_t max_it, hipStream_t st, hipEvent_t e0, hipEvent_t e1);
 int resident_blocks_per_cu(const DevSys &s, unsigned npt, unsigned nph, size_t lds, bool shard);
 size_t resident_static_lds(const DevSys &s, bool small, bool shard);  // the instantiation's static LDS bytes
 uint64_t resident_offchip_bytes(const cwf_hip_system *h);  // per phase: halo records read, surface records and shares
-// a PEER slab shard's resident solve: planned on the rank's own at the schedule vote (group_fused), run only when every
-// rank planned one (res_agreed); the init is the fused one's without its launch 0 and exchange step (comm.cpp)
-bool resident_shard_ready(cwf_hip_system *h);
-bool resident_on(const cwf_hip_system *h);  // the handle's FAST solves run the resident solve (planned and agreed)
+// a PEER slab shard's resident solve: the init is the fused one's without its launch 0 and exchange step (comm.cpp)
 int sharded_resident_init(const std::vector<cwf_hip_system *> &g, const std::vector<const float *> &rhs, double rel_tol);
-int sharded_fused_end(const std::vector<cwf_hip_system *> &g);  // after the last launch (PEER in-kernel epochs)
+int sharded_fused_end(const std::vector<cwf_hip_system *> &g, PcgSchedule sch);  // after the last launch (FusedPeer: the epochs)
 
 unsigned fast_tile_blocks(const DevSys &s);
 unsigned fast_pipe_grid(const DevSys &s);

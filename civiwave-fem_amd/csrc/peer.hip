@@ -472,7 +472,7 @@ bool peer_fused_eligible(cwf_hip_system *h)
     bool same = false;
     for (int p = 0; p < cm->nranks; ++p)
         same = same || (p != cm->rank && cm->peer_same_device[p] != 0);
-    if (same && (uint64_t)h->fused_grid * (uint64_t)cm->nranks > pcg_lattice_resident_count(h->ds))
+    if (same && (uint64_t)h->sched.grid * (uint64_t)cm->nranks > pcg_lattice_resident_count(h->ds))
         return false;
     return true;
 }

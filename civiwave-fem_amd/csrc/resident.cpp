@@ -37,8 +37,6 @@ void split(unsigned n, unsigned g, unsigned q, unsigned &a, unsigned &b)
 }
 }  // namespace
 
-namespace
-{
 // the plan over the node planes [k0, k1) of the block (a PEER slab shard: its owned planes; the ghost planes beside
 // them are the halo entries' only other source, read from the mailbox). False: the solve keeps the other schedules
 bool plan_resident(cwf_hip_system *h, bool shard)
@@ -363,50 +361,10 @@ bool plan_resident(cwf_hip_system *h, bool shard)
     rp.shard = shard;
     rp.remote_sends = remote_sends;
     rp.ghost_total = ghost_total;
-    rp.state = 1;
     if (knob("CWF_VERBOSE"))
         fprintf(stderr, "[cwf] resident plan: %u boxes (%u x %u x %u), max_own %u, max_halo %u, %u published nodes\n", G,
                 bg[0], bg[1], bg[2], max_own, max_halo, npub);
     return true;
-}
-
-// CWF_RESIDENT=0, or an explicit CWF_FUSED schedule (0: two kernels, 1: the per-launch fused iteration, 2: its
-// persistent walk), keeps the launch-per-iteration schedules
-bool resident_off()
-{
-    const char *kn = knob("CWF_RESIDENT");
-    return (kn && kn[0] == '0') || knob("CWF_FUSED");
-}
-}  // namespace
-
-bool resident_ready(cwf_hip_system *h)
-{
-    ResidentPlan &rp = h->res;
-    if (rp.state)
-        return rp.state > 0 && !rp.shard;
-    if (h->sharded())
-        return false;  // a shard plans at the schedule vote (resident_shard_ready)
-    rp.state = -1;
-    return !resident_off() && plan_resident(h, false);
-}
-
-bool resident_shard_ready(cwf_hip_system *h)
-{
-    ResidentPlan &rp = h->res;
-    if (rp.state)
-        return rp.state > 0 && rp.shard;
-    rp.state = -1;
-    // PEER only: the kernel stores its surface records into the neighbours' mailboxes itself
-    if (resident_off() || !h->sharded() || !h->comm || h->comm->kind != 2 || h->nranks > kMaxPeers)
-        return false;
-    return plan_resident(h, true);
-}
-
-bool resident_on(const cwf_hip_system *h)
-{
-    if (h->sharded())
-        return h->res_agreed == 1 && h->res.state > 0 && h->res.shard;
-    return resident_ready(const_cast<cwf_hip_system *>(h));
 }
 
 uint64_t resident_offchip_bytes(const cwf_hip_system *h)

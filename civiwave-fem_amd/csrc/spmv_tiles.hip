@@ -2007,28 +2007,7 @@ void fast_tiles_pcg_dry(cwf_hip_system *h, unsigned abl, int reps, hipStream_t s
 // ---- the fused lattice iteration (lattice_fused.inc) --------------------------------------------------------
 unsigned pcg_lattice_resident_count(const DevSys &s) { return lattice_resident_count(s); }
 
-// CWF_FUSED=0: the two-kernel iteration on a structured block; CWF_FUSED_MAXWG: the largest grid that fuses (every
-// workgroup folds five shares of each of the previous launch's workgroups)
-bool fast_fused(const cwf_hip_system *h)
-{
-    const DevTiles &t = h->ds.t;
-    if (!(h->mode == CWF_MODE_FAST && t.lat && t.lcls && t.lcz && h->r2 && h->fsh && h->g_fsh && t.ntiles))
-        return false;
-    if (h->fused_grid == 0 || h->fused_items != t.lnwork)  // per handle and plan (attach re-plans a shard's items)
-    {
-        cwf_hip_system *m = const_cast<cwf_hip_system *>(h);
-        const char *on = knob("CWF_FUSED"), *cap = knob("CWF_FUSED_MAXWG");
-        m->fused_grid = pcg_lattice_grid(h->ds, cap && atoi(cap) > 0 ? (unsigned)atoi(cap) : 1024u);
-        m->fused_items = t.lnwork;
-        // default: fused where one round of workgroups covers the work items (C2 fused 46.6k vs two-kernel 46.9k
-        // PCG it/s, same box: one launch and one exchange per iteration for the same time). Beyond one round the
-        // persistent walk (234-248 VGPRs, 2 waves/SIMD) loses to the two kernels: C3 8.3k vs 10.8k it/s
-        // (profiles/r05b). CWF_FUSED=2 forces it, 0 turns it off
-        const int v = on ? atoi(on) : 1;
-        m->fused_on = v == 2 || (v == 1 && m->fused_grid >= t.lnwork);
-    }
-    return h->fused_on;
-}
+unsigned pcg_lattice_launch_grid(const DevSys &s, unsigned cap) { return pcg_lattice_grid(s, cap); }
 
 namespace
 {
@@ -2041,14 +2020,14 @@ uint64_t *fused_trace_buffer(const cwf_hip_system *h)
 {
     if (!knob("CWF_FUSED_TRACE"))
         return nullptr;
-    if (g_ftrace_n < h->fused_grid)
+    if (g_ftrace_n < h->sched.grid)
     {
         if (g_ftrace)
             (void)hipFree(g_ftrace);
         g_ftrace = nullptr;
-        if (hipMalloc(reinterpret_cast<void **>(&g_ftrace), 128ull * h->fused_grid) != hipSuccess)
+        if (hipMalloc(reinterpret_cast<void **>(&g_ftrace), 128ull * h->sched.grid) != hipSuccess)
             return nullptr;
-        g_ftrace_n = h->fused_grid;
+        g_ftrace_n = h->sched.grid;
     }
     return g_ftrace;
 }
@@ -2057,14 +2036,14 @@ void fused_trace_dump(cwf_hip_system *h, unsigned it, hipStream_t st)
     const char *path = knob("CWF_FUSED_TRACE"), *at = knob("CWF_FUSED_TRACE_IT");
     if (!path || !g_ftrace || it != (unsigned)(at ? atoi(at) : 50))
         return;
-    std::vector<uint64_t> v(16ull * h->fused_grid);
+    std::vector<uint64_t> v(16ull * h->sched.grid);
     if (hipStreamSynchronize(st) != hipSuccess ||
         hipMemcpy(v.data(), g_ftrace, v.size() * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess)
         return;
     if (FILE *f = std::fopen(path, "a"))
     {
-        std::fprintf(f, "# launch %u grid %u\n", it + 1u, h->fused_grid);
-        for (unsigned b = 0; b < h->fused_grid; ++b)
+        std::fprintf(f, "# launch %u grid %u\n", it + 1u, h->sched.grid);
+        for (unsigned b = 0; b < h->sched.grid; ++b)
         {
             const uint64_t *w = &v[16ull * b];
             std::fprintf(f, "%u %llu %llu %llu %llu %llu %llu %llu %llu %llu %llu %llu %llu %llu %llu\n", b,
@@ -2087,11 +2066,11 @@ FusedArgs fused_args(cwf_hip_system *h, unsigned j)
     FusedArgs fa{};
     fa.ctl = h->ctl;
     fa.sstride = W;
-    fa.grid = h->fused_grid;
+    fa.grid = h->sched.grid;
     if (h->sharded())  // every rank folds the all-gathered rank totals, in rank order
     {
         fa.sin = h->g_fsh;
-        if (h->px_agreed == 1)  // PEER in-kernel: the totals land in the mailbox's gather area (previous epoch)
+        if (h->sched.launch == PcgSchedule::FusedPeer)  // PEER in-kernel: the totals land in the mailbox's gather area (previous epoch)
         {
             const double *gp = nullptr;
             peer_fused_args(h, j, fa.pe, &gp);
@@ -2105,7 +2084,7 @@ FusedArgs fused_args(cwf_hip_system *h, unsigned j)
     else
     {
         fa.sin = h->fsh + (size_t)((j + 1u) & 1u) * 5 * W;
-        fa.nin = h->fused_grid;
+        fa.nin = h->sched.grid;
         fa.sin_stride = W;
         fa.sis = 1;
     }
@@ -2188,13 +2167,13 @@ float *fast_fused_ap(cwf_hip_system *h, unsigned j) { return (j & 1u) ? h->ap2 :
 void fast_fused_rank_totals(cwf_hip_system *h, unsigned j, hipStream_t st)
 {
     const unsigned W = h->ds.t.lnwork;
-    k_fused_rank_totals<<<1, 256, 0, st>>>(h->fsh + (size_t)(j & 1u) * 5 * W, h->fused_grid, W,
+    k_fused_rank_totals<<<1, 256, 0, st>>>(h->fsh + (size_t)(j & 1u) * 5 * W, h->sched.grid, W,
                                            h->g_fsh + (size_t)kFusedSlot * h->rank);
 }
 const double *fast_fused_shares(const cwf_hip_system *h, unsigned j, unsigned *stride, unsigned *count)
 {
     *stride = h->ds.t.lnwork;
-    *count = h->fused_grid;
+    *count = h->sched.grid;
     return h->fsh + (size_t)(j & 1u) * 5 * h->ds.t.lnwork;
 }
 

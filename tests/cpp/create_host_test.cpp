@@ -1,5 +1,6 @@
 // create_host_test.cpp -- the host-only pieces of cwf_hip_system_create (abi_internal.hpp), on descs built here:
-// the FAST path choice, the push-run padding of the per-tet tiles and the lattice class table. No GPU call.
+// the FAST path choice, the push-run padding of the per-tet tiles and the lattice class table; and the PCG schedule's
+// decision table (schedule.cpp's pure functions) with pcg_error_message. No GPU call.
 // Built and run by tests/test_host.py (g++, -D__HIP_PLATFORM_AMD__, -lcwf_hip). Prints "ok" and returns 0.
 #include <cstdio>
 #include <cstdlib>
@@ -242,6 +243,152 @@ void test_lattice_classes()
     CHECK(lc.interior && lc.interior_mass == kuhn.mass[kuhn.node(1, 1, 1)]);
 }
 
+// ---- the PCG schedule (schedule.cpp): facts -> plan -> one solve's schedule -----------------------------------
+using S = PcgSchedule;
+
+// an unsharded structured block whose fused grid covers its work items and whose resident plan fits, no knob set
+ScheduleFacts block_facts()
+{
+    ScheduleFacts f;
+    f.mode = CWF_MODE_FAST;
+    f.fusable = f.grid_covers = f.resident_plan = true;
+    return f;
+}
+// a PEER slab shard of the same (one member per process), every rank voting for everything
+ScheduleFacts shard_facts()
+{
+    ScheduleFacts f = block_facts();
+    f.sharded = f.thick_slab = f.peer_eligible = true;
+    f.all = ScheduleVote{true, true, true};
+    return f;
+}
+// the plan's launch-per-iteration schedule and whether the resident solve replaces it
+void check_plan(const ScheduleFacts &f, S launch, bool resident)
+{
+    const SchedulePlan p = choose_schedule(f);
+    CHECK(p.state == SchedulePlan::Decided && p.launch == launch && p.resident == resident);
+    CHECK(solve_schedule(p, 1) == (resident ? S::Resident : launch));
+}
+
+void test_schedule_choice()
+{
+    const uint64_t lim = 1u << 24;
+    ScheduleFacts f;  // a PARITY handle, whatever else holds
+    check_plan(f, S::Parity, false);
+    f = block_facts();
+    f.mode = CWF_MODE_PARITY;
+    check_plan(f, S::Parity, false);
+    f = shard_facts();
+    f.mode = CWF_MODE_PARITY;
+    check_plan(f, S::Parity, false);
+    CHECK(exchange_schedule_code(choose_schedule(f)) == -1);  // PARITY shards take no vote
+    f = block_facts();  // a non-lattice FAST handle
+    f.fusable = f.grid_covers = f.resident_plan = false;
+    check_plan(f, S::TwoKernel, false);
+    check_plan(block_facts(), S::Fused, true);  // the grid covers the items
+    f = block_facts();                          // it does not: never resident, even where a plan would fit
+    f.grid_covers = false;
+    check_plan(f, S::TwoKernel, false);
+    // CWF_FUSED unset / 0 / 1 / 2 x CWF_RESIDENT=0 x the grid covering the items: any CWF_FUSED turns resident off
+    for (int knob = -1; knob <= 2; ++knob)
+        for (int off = 0; off < 2; ++off)
+            for (int covers = 0; covers < 2; ++covers)
+            {
+                f = block_facts();
+                f.fused_knob = knob;
+                f.resident_off = off != 0;
+                f.grid_covers = covers != 0;
+                const bool fuse = knob == 2 || (knob != 0 && covers);
+                check_plan(f, fuse ? S::Fused : S::TwoKernel, fuse && knob < 0 && !off);
+                CHECK(choose_schedule(f).fused_knob == knob);
+            }
+    f = block_facts();  // no resident plan could be made
+    f.resident_plan = false;
+    check_plan(f, S::Fused, false);
+
+    // shards: this rank's vote, then the plan from every rank's
+    f = shard_facts();
+    ScheduleVote v = own_vote(f);
+    CHECK(v.fuse && v.peer && v.resident);
+    check_plan(f, S::FusedPeer, true);
+    f.thick_slab = false;  // a thin slab votes against fusing, and so against everything
+    v = own_vote(f);
+    CHECK(!v.fuse && !v.peer && !v.resident);
+    f.all = v;
+    check_plan(f, S::TwoKernel, false);
+    f = shard_facts();  // a LOCAL group of 2: fused with an exchange step, never in-kernel or resident
+    f.group = 2;
+    v = own_vote(f);
+    CHECK(v.fuse && !v.peer && !v.resident);
+    f.all = v;
+    check_plan(f, S::Fused, false);
+    f = shard_facts();  // one rank lacks PEER eligibility
+    f.all.peer = false;
+    check_plan(f, S::Fused, true);
+    f.peer_eligible = false;  // (this one)
+    CHECK(own_vote(f).fuse && !own_vote(f).peer && own_vote(f).resident);
+    f = shard_facts();  // one rank lacks a resident plan
+    f.all.resident = false;
+    check_plan(f, S::FusedPeer, false);
+    f.resident_plan = false;  // (this one)
+    CHECK(own_vote(f).fuse && own_vote(f).peer && !own_vote(f).resident);
+    f = shard_facts();  // one rank cannot fuse: nobody does, whatever this rank could
+    f.all = ScheduleVote{false, false, false};
+    check_plan(f, S::TwoKernel, false);
+    f.all = ScheduleVote{false, true, true};  // (votes that cannot be cast: still nothing without the fused iteration)
+    check_plan(f, S::TwoKernel, false);
+    f = shard_facts();  // an explicit CWF_FUSED, or CWF_RESIDENT=0, on a shard: no resident vote
+    f.fused_knob = 1;
+    CHECK(own_vote(f).peer && !own_vote(f).resident);
+    f = shard_facts();
+    f.resident_off = true;
+    CHECK(own_vote(f).peer && !own_vote(f).resident);
+
+    // the resident solve counts at most 2^24 iterations: a longer solve takes the launch-per-iteration schedule
+    SchedulePlan p = choose_schedule(shard_facts());  // PEER in-kernel exchange underneath
+    CHECK(solve_schedule(p, lim) == S::Resident && solve_schedule(p, lim + 1) == S::FusedPeer);
+    p = choose_schedule(block_facts());  // ... and without
+    CHECK(solve_schedule(p, lim) == S::Resident && solve_schedule(p, lim + 1) == S::Fused);
+    f = block_facts();
+    f.resident_plan = false;
+    p = choose_schedule(f);
+    CHECK(solve_schedule(p, lim) == S::Fused && solve_schedule(p, lim + 1) == S::Fused);
+
+    // cwf_hip_system_exchange_schedule of a shard: -1 until the vote, then 0 two kernels / 1 fused / 2 in-kernel / 3 resident
+    p = SchedulePlan{};
+    CHECK(exchange_schedule_code(p) == -1);
+    p.state = SchedulePlan::Local;  // its own half planned (a query before the first solve)
+    p.launch = S::Fused;
+    CHECK(exchange_schedule_code(p) == -1);
+    f = shard_facts();
+    CHECK(exchange_schedule_code(choose_schedule(f)) == 3);
+    f.all.resident = false;
+    CHECK(exchange_schedule_code(choose_schedule(f)) == 2);
+    f.all.peer = false;
+    CHECK(exchange_schedule_code(choose_schedule(f)) == 1);
+    f.all.resident = true;  // resident over the exchange-step fused iteration
+    CHECK(exchange_schedule_code(choose_schedule(f)) == 3);
+    f.all = ScheduleVote{};
+    CHECK(exchange_schedule_code(choose_schedule(f)) == 0);
+}
+
+void test_pcg_error_message()
+{
+    std::string ctx;
+    // CWF_ERR_HIP: the resident solve's phase barrier after a Resident solve, the PARITY streamed fold otherwise
+    CHECK(pcg_error_message(CWF_ERR_HIP, 7, S::Resident, &ctx) == "resident solve: a workgroup missed the phase barrier");
+    CHECK(ctx == "phase=7");
+    CHECK(pcg_error_message(CWF_ERR_HIP, 7, S::Parity, &ctx) == "PARITY streamed scalar fold timed out");
+    CHECK(ctx == "iteration=7");
+    for (S sch : {S::Parity, S::TwoKernel, S::Fused, S::FusedPeer, S::Resident})  // the other codes: as they were
+    {
+        CHECK(pcg_error_message(CWF_ERR_DENOM_ZERO, 3, sch, &ctx) == "CG denominator approached zero" && ctx == "iteration=3");
+        CHECK(pcg_error_message(CWF_ERR_COMM, 4, sch, &ctx) == "peer exchange timed out" && ctx == "step=4");
+        CHECK(pcg_error_message(CWF_ERR_RHO_ZERO, -1, sch, &ctx) == "preconditioner produced near-zero rho" && ctx == "rho~0");
+        CHECK(pcg_error_message(CWF_ERR_RHO_ZERO, 5, sch, &ctx) == "CG rho approached zero" && ctx == "iteration=5");
+    }
+}
+
 }  // namespace
 
 int main()
@@ -249,6 +396,8 @@ int main()
     test_path_choice();
     test_push_run_padding();
     test_lattice_classes();
+    test_schedule_choice();
+    test_pcg_error_message();
     std::puts("ok");
     return 0;
 }

@@ -166,3 +166,21 @@ def test_resident_c3_slab_block_follows_two_kernels(element, monkeypatch):
         assert tr.iterations == tk.iterations == its
         d = np.linalg.norm(xr.astype(np.float64) - xk) / np.linalg.norm(xk.astype(np.float64))
         assert d <= 1e-5, (its, d)
+
+
+def test_solve_past_the_resident_limit_runs_the_fused_schedule(monkeypatch):
+    """The resident launch counts at most 2^24 iterations, so a solve allowed one more runs the fused launch-per-iteration
+    schedule on the handle whose plan is resident: the kernel sequence of a CWF_FUSED=1 handle from the same start, so
+    the same iteration count and the same x bit for bit."""
+    case = CASES["rayleigh"]()  # the smallest block of the table (7 x 5 x 4 nodes)
+    rhs = case.static_rhs()
+    sr = _system(case, monkeypatch)
+    assert _kernel(sr).startswith("k_pcg_resident"), _kernel(sr)
+    tl, xl, _ = _solve(sr, rhs, 2**24 + 1, 1e-6)
+    sf = _system(case, monkeypatch, fused="1")
+    assert _kernel(sf).startswith("k_pcg_lattice"), _kernel(sf)
+    tf, xf, _ = _solve(sf, rhs, case.cfg.solver.max_iterations, 1e-6)
+    print(f"past the limit {tl.iterations} it, CWF_FUSED=1 {tf.iterations} it")
+    assert tl.converged and tf.converged
+    assert tl.iterations == tf.iterations
+    assert np.array_equal(xl.view(np.uint32), xf.view(np.uint32))
