@@ -39,6 +39,28 @@ template <class T> inline int dalloc(cwf_hip_system *h, T **p, size_t count)
     return 0;
 }
 
+// a hipEvent pair on the handle's stream whose elapsed times add up into *ms
+struct Stopwatch
+{
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ~Stopwatch()
+    {
+        if (e0)
+            (void)hipEventDestroy(e0);
+        if (e1)
+            (void)hipEventDestroy(e1);
+    }
+    bool make() { return hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess; }
+    void start(hipStream_t st) { (void)hipEventRecord(e0, st); }
+    void stop(hipStream_t st, double *ms)
+    {
+        float t = 0.f;
+        if (hipEventRecord(e1, st) == hipSuccess && hipEventSynchronize(e1) == hipSuccess &&
+            hipEventElapsedTime(&t, e0, e1) == hipSuccess)
+            *ms += t;
+    }
+};
+
 // the Dirichlet mask can ride in node_part_off's top bits when the offsets leave them free
 inline bool ht_off_mask_ok(const std::vector<uint32_t> &npo) { return npo.back() <= cwf::kPartOffBits; }
 // ... and then does (the update pass reads the offsets anyway: one 4-B stream less). Returns DevTiles::off_mask

@@ -439,6 +439,10 @@ struct cwf_hip_system
     double *mo_f64 = nullptr;
     float *mo_mass = nullptr;
     uint32_t *mo_mask = nullptr;
+    // refined solve workspace (refine.cpp), allocated at the first refined call and kept in `owned`: fp64 x, b, r and
+    // the previous iterate [D] in the internal node order, the nodes' shares of |r|^2 [N], and the norm's chunk
+    // partials followed by its two results
+    double *rf_x = nullptr, *rf_b = nullptr, *rf_r = nullptr, *rf_xp = nullptr, *rf_share = nullptr, *rf_part = nullptr;
     // live K_eff timing (cwf_hip_system_set_timing)
     int timing = 0;
     std::vector<hipEvent_t> ev;  // 2 per enqueued iteration of one batch

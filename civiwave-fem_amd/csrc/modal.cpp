@@ -68,28 +68,6 @@ float *blk(cwf_hip_system *h, int i) { return h->mo_blk + (size_t)i * h->mo_cols
 double *gram_part(cwf_hip_system *h) { return h->mo_f64; }
 double *gram_out(cwf_hip_system *h, int i) { return h->mo_f64 + ((size_t)modal_gram_chunks(h->ds.D) + i) * kQQ; }
 
-// a hipEvent pair on the handle's stream whose elapsed times add up into *ms
-struct Stopwatch
-{
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    ~Stopwatch()
-    {
-        if (e0)
-            (void)hipEventDestroy(e0);
-        if (e1)
-            (void)hipEventDestroy(e1);
-    }
-    bool make() { return hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess; }
-    void start(hipStream_t st) { (void)hipEventRecord(e0, st); }
-    void stop(hipStream_t st, double *ms)
-    {
-        float t = 0.f;
-        if (hipEventRecord(e1, st) == hipSuccess && hipEventSynchronize(e1) == hipSuccess &&
-            hipEventElapsedTime(&t, e0, e1) == hipSuccess)
-            *ms += t;
-    }
-};
-
 struct ModalPlan
 {
     uint32_t k, q, max_outer;

@@ -65,6 +65,17 @@ class ModalTelemetryC(C.Structure):
                 ("solve_ms", C.c_double), ("block_ms", C.c_double)]
 
 
+class RefineSettingsC(C.Structure):
+    _fields_ = [("max_outer", C.c_uint32), ("relative_tolerance", C.c_double), ("stagnation_ratio", C.c_double),
+                ("inner", PcgSettingsC), ("warm_start", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RefineTelemetryC(C.Structure):
+    _fields_ = [("outer_iterations", C.c_uint32), ("inner_iterations", C.c_uint64), ("residual_norm", C.c_double),
+                ("rhs_norm", C.c_double), ("converged", C.c_int32), ("stagnated", C.c_int32),
+                ("history", C.c_double * 32), ("residual_ms", C.c_double), ("solve_ms", C.c_double)]
+
+
 class StepperDescC(C.Structure):
     _fields_ = [
         ("rayleigh_alpha", C.c_double), ("rayleigh_beta", C.c_double), ("runtime_tolerance", C.c_double),
@@ -164,6 +175,10 @@ def load() -> C.CDLL:
         "cwf_hip_modal_solve": ([P, P, P, P, i32, P], i32),
         "cwf_hip_block_gram": ([P, P, C.c_uint32, P, C.c_uint32, i32, P, i32], i32),
         "cwf_hip_block_rotate": ([P, P, C.c_uint32, P, C.c_uint32, P, P, i32], i32),
+        "cwf_hip_solve_refined": ([P, P, P, P, u64, i32, P], i32),
+        "cwf_hip_residual_f64": ([P, P, P, P, u64, i32, P], i32),
+        "cwf_hip_residual_f64_timed": ([P, i32, P], i32),
+        "cwf_refine_scale_exponent": ([f64, f64], i32),
         "cwf_hip_stepper_create": ([P, P, P], i32),
         "cwf_hip_stepper_destroy": ([P], None),
         "cwf_hip_stepper_step": ([P, f64, i32, P], i32),

@@ -280,3 +280,96 @@ def residual_history(system: MatrixFreeSystem) -> np.ndarray:
     n = C.c_uint64()
     _lib.load().cwf_hip_residual_history(h, _lib.ptr(out), cap, C.byref(n))
     return out[: n.value].copy()
+
+
+# -- refined static solve (cwf_hip_solve_refined; no reference counterpart) --------------------------------------------
+@dataclass
+class RefineSettings:
+    """Tolerance on the true fp64 residual |b - K_eff x| / |b|; ``inner`` drives the f32 PCG of each correction
+    (its warm_start is ignored). The values are cwf_hip.h's defaults."""
+    max_outer: int = 12
+    relative_tolerance: float = 1.0e-10
+    stagnation_ratio: float = 0.5
+    inner: PcgSettings = field(default_factory=lambda: PcgSettings(20000, 1.0e-4, False))
+    warm_start: bool = False
+
+
+@dataclass
+class RefineTelemetry:
+    outer_iterations: int = 0
+    inner_iterations: int = 0
+    residual_norm: float = 0.0
+    rhs_norm: float = 0.0
+    converged: bool = False
+    stagnated: bool = False
+    history: np.ndarray | None = None  # |r| before each inner solve, then the final one
+    residual_ms: float = 0.0
+    solve_ms: float = 0.0
+
+    @classmethod
+    def from_c(cls, t) -> "RefineTelemetry":
+        hist = np.array(t.history[: int(t.outer_iterations) + 1], np.float64)
+        return cls(int(t.outer_iterations), int(t.inner_iterations), t.residual_norm, t.rhs_norm, bool(t.converged),
+                   bool(t.stagnated), hist, t.residual_ms, t.solve_ms)
+
+
+@dataclass
+class RefineResult:
+    solution: Any  # fp64 [dof_count], a numpy array or the device tensor passed in
+    telemetry: RefineTelemetry
+
+
+def _f64(a, name: str):
+    if isinstance(a, np.ndarray):
+        if a.dtype != np.float64 or not a.flags.c_contiguous:
+            raise TypeError(f"{name} must be a contiguous float64 array")
+    elif "float64" not in str(a.dtype) or not a.is_contiguous():
+        raise TypeError(f"{name} must be a contiguous float64 tensor")
+    return a
+
+
+def refine_scale_exponent(residual_norm: float, rhs_norm: float) -> int:
+    """The e with 2^e residual_norm in (rhs_norm / 2, 2 rhs_norm) (cwf_refine_scale_exponent, host only)."""
+    return int(_lib.load().cwf_refine_scale_exponent(float(residual_norm), float(rhs_norm)))
+
+
+def solve_refined(system: MatrixFreeSystem, rhs, settings: RefineSettings | None = None, x=None) -> Expected:
+    """K_eff x = rhs in fp64 by iterative refinement around the handle's PCG. rhs: float64 numpy array or device
+    tensor; x (same kind, optional) is the start value under settings.warm_start and receives the solution in place.
+    The value is a RefineResult; stagnation and max_outer are telemetry, not errors."""
+    s = settings or RefineSettings()
+    _f64(rhs, "rhs")
+    if _size(rhs) != system.dof_count or (x is not None and _size(x) != system.dof_count):
+        return Expected(error=PcgError("rhs span size mismatch", [f"rhs={_size(rhs)}", f"dofs={system.dof_count}"]))
+    if x is None:
+        x = np.zeros(system.dof_count, np.float64) if isinstance(rhs, np.ndarray) else rhs.new_zeros(rhs.shape)
+    _f64(x, "x")
+    if _kind(x) != _kind(rhs):
+        raise TypeError("rhs and x must both be host arrays or both device tensors")
+    h = system.handle()
+    cs = _lib.RefineSettingsC(int(s.max_outer), float(s.relative_tolerance), float(s.stagnation_ratio),
+                              _lib.PcgSettingsC(int(s.inner.max_iterations), float(s.inner.relative_tolerance), 0, 0),
+                              int(s.warm_start), 0)
+    tel = _lib.RefineTelemetryC()
+    st = _lib.load().cwf_hip_solve_refined(h, _lib.ptr(rhs), C.byref(cs), _lib.ptr(x), system.dof_count, _kind(rhs),
+                                           C.byref(tel))
+    if st:
+        return Expected(error=system._err())
+    return Expected(RefineResult(x, RefineTelemetry.from_c(tel)))
+
+
+def residual_f64(system: MatrixFreeSystem, rhs, x) -> Expected:
+    """(r, |r|) with r = rhs - K_eff x formed in fp64 on the device (cwf_hip_residual_f64); r is of rhs's kind."""
+    _f64(rhs, "rhs"), _f64(x, "x")
+    if _size(rhs) != system.dof_count or _size(x) != system.dof_count:
+        return Expected(error=PcgError("rhs span size mismatch", [f"rhs={_size(rhs)}", f"dofs={system.dof_count}"]))
+    if _kind(x) != _kind(rhs):
+        raise TypeError("rhs and x must both be host arrays or both device tensors")
+    r = np.zeros(system.dof_count, np.float64) if isinstance(rhs, np.ndarray) else rhs.new_zeros(rhs.shape)
+    h = system.handle()
+    norm = C.c_double()
+    st = _lib.load().cwf_hip_residual_f64(h, _lib.ptr(rhs), _lib.ptr(x), _lib.ptr(r), system.dof_count, _kind(rhs),
+                                          C.byref(norm))
+    if st:
+        return Expected(error=system._err())
+    return Expected((r, norm.value))

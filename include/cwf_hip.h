@@ -292,6 +292,60 @@ int cwf_hip_block_rotate(cwf_hip_system *h, const float *X, uint32_t q_in, const
                          float *X_out, float *MX_out, int ptr_kind);
 
 /* ---------------------------------------------------------------------------------------
+ * Refined static solve (no reference counterpart): K_eff x = b to a tolerance on the TRUE residual
+ * |b - K_eff x| / |b|, evaluated in fp64. cwf_hip_solve_pcg stops on the recurrence residual of an f32 iteration,
+ * and f32 storage of x bounds the true residual at about cond(K) * 6e-8 however small the tolerance. Here x and b are
+ * fp64 and classical iterative refinement runs around the handle's own PCG: each outer iteration forms
+ * r = b - K_eff x on the device (fp64 element math on the handle's f32 element records, the PARITY operator's fold
+ * order, no atomics: the same inputs give the same bits), scales it by a power of two into b's binade (the PCG's
+ * guards are absolute), solves K_eff d = f32(2^e r) with an ordinary solve in the handle's mode and schedule, and
+ * adds 2^(-e) d. Dirichlet DOFs: x_c = b_c exactly; a constrained row's residual is 0 and a constrained DOF enters
+ * the operator as 0, as in the reference. |b| is taken over the free DOFs. The handle's mode and scalars are not
+ * changed, and its own solves return afterwards what they returned before. tet4 handles of both modes (the PARITY
+ * node tiles are built at the first such call); CWF_ERR_UNSUPPORTED for a handle attached to a communicator and for
+ * a hex8 handle (no fp64 hex8 operator on the device).
+ * ------------------------------------------------------------------------------------- */
+typedef struct cwf_refine_settings
+{
+    uint32_t max_outer;          /* corrections at most; 0 -> 12, at most 31 */
+    double relative_tolerance;   /* on the true fp64 residual |b - K_eff x| / |b|; 0 -> 1e-10 */
+    double stagnation_ratio;     /* stop when |r_k| > ratio |r_(k-1)|; 0 -> 0.5 */
+    cwf_pcg_settings inner;      /* inner.relative_tolerance 0 -> 1e-4, inner.max_iterations 0 -> 20000;
+                                    inner.warm_start is ignored */
+    int32_t warm_start;          /* x_inout holds a start value */
+    int32_t reserved;
+} cwf_refine_settings;
+typedef struct cwf_refine_telemetry
+{
+    uint32_t outer_iterations;   /* corrections applied */
+    uint64_t inner_iterations;   /* over every inner solve */
+    double residual_norm, rhs_norm; /* fp64, true: of the returned x, and |b| over the free DOFs */
+    int32_t converged, stagnated;   /* neither at max_outer; stagnated is reported, not an error */
+    double history[32];          /* |r| before each inner solve, then the final one: outer_iterations + 1 entries */
+    double residual_ms, solve_ms; /* hipEvent time in the fp64 kernels / in the inner solves */
+} cwf_refine_telemetry;
+/* rhs and x_inout are fp64 [n = 3N] in the caller's node order, host or device by ptr_kind; s == NULL: the defaults.
+ * Stops converged (|r| <= tol |b|), stagnated (the rule above; the iterate with the smaller residual is returned) or
+ * at max_outer; all three return CWF_OK. An inner solve that stops at its max_iterations still gave a correction and is
+ * judged by the stagnation rule. A breakdown of an inner solve (CWF_ERR_RHO_ZERO, CWF_ERR_DENOM_ZERO) is the call's
+ * status, its context extended by "outer=<k>"; x_inout then holds the iterate before that solve. |b| = 0 returns
+ * the prescribed values, converged, with no inner solve. */
+int cwf_hip_solve_refined(cwf_hip_system *h, const double *rhs, const cwf_refine_settings *s, double *x_inout,
+                          uint64_t n, int ptr_kind, cwf_refine_telemetry *tel);
+/* r_out (nullable) = b - K_eff x in fp64 with the handle's current scalars, *norm_out (nullable) = |r|: the kernel
+ * of the refined solve on its own. The norm is folded from one share per node in a tree that depends on N alone. */
+int cwf_hip_residual_f64(cwf_hip_system *h, const double *rhs, const double *x, double *r_out, uint64_t n,
+                         int ptr_kind, double *norm_out);
+/* Measurement support: `reps` launches of the fp64 residual's tile kernel alone (no norm fold, no copies) over the
+ * handle's workspace vectors, bracketed by one hipEvent pair; *avg_ms = elapsed / reps. The yardstick is
+ * cwf_hip_keff_timed on a PARITY handle of the same mesh: the same tile walk with f32 vectors. */
+int cwf_hip_residual_f64_timed(cwf_hip_system *h, int reps, double *avg_ms);
+/* Host only: the e with 2^e residual_norm in (rhs_norm / 2, 2 rhs_norm), the refined solve's scale. 0 for a zero
+ * residual; a subnormal residual is counted from its leading bit; rhs_norm == 0 (only prescribed values load the
+ * system) scales to the binade of 1. */
+int cwf_refine_scale_exponent(double residual_norm, double rhs_norm);
+
+/* ---------------------------------------------------------------------------------------
  * Newmark stepper: cwf::gpu::newmark::Stepper (newmark_stepper.hpp:92-190). Device-resident
  * node state (u, v, a, predictor, external force, bc values); one step = predictor -> RHS
  * (+ beta_R * K * d when beta_R != 0) -> Dirichlet clamp -> PCG -> corrector -> adaptive dt.

@@ -255,6 +255,71 @@ inline expected<cwf_hip_system *, PcgError> bind(const MatrixFreeSystem &s, Matr
     return {};
 }
 
+// Refined static solve (cwf_hip_solve_refined; no reference counterpart): fp64 x and b, the tolerance on the true
+// residual |b - K_eff x| / |b|, iterative refinement around the handle's own PCG.
+struct RefineSettings
+{
+    std::uint32_t max_outer{12};
+    double relative_tolerance{1.0e-10};
+    double stagnation_ratio{0.5};
+    PcgSettings inner{20000, 1.0e-4, false};  // inner solves (warm_start is ignored)
+    bool warm_start{false};                   // solution holds a start value
+};
+
+struct RefineTelemetry
+{
+    std::uint32_t outer_iterations{0};
+    std::uint64_t inner_iterations{0};
+    double residual_norm{0.0}, rhs_norm{0.0};  // fp64, true
+    bool converged{false}, stagnated{false};
+    std::vector<double> history;               // |r| before each inner solve, then the final one
+    double residual_ms{0.0}, solve_ms{0.0};
+};
+
+[[nodiscard]] inline auto solve_refined(const MatrixFreeSystem &system, std::span<const double> rhs,
+                                        const RefineSettings &settings, std::span<double> solution,
+                                        MatrixFreeWorkspace &workspace) -> expected<RefineTelemetry, PcgError>
+{
+    if (rhs.size() != system.dof_count || solution.size() != system.dof_count)
+        return unexpected<PcgError>{{"rhs span size mismatch", {"rhs=" + std::to_string(rhs.size()),
+                                                                 "dofs=" + std::to_string(system.dof_count)}}};
+    auto h = detail::bind(system, workspace);
+    if (!h)
+        return unexpected<PcgError>{h.error()};
+    cwf_refine_settings cs{};
+    cs.max_outer = settings.max_outer;
+    cs.relative_tolerance = settings.relative_tolerance;
+    cs.stagnation_ratio = settings.stagnation_ratio;
+    cs.inner = cwf_pcg_settings{settings.inner.max_iterations, settings.inner.relative_tolerance, 0, 0};
+    cs.warm_start = settings.warm_start ? 1 : 0;
+    cwf_refine_telemetry t{};
+    if (cwf_hip_solve_refined(*h, rhs.data(), &cs, solution.data(), rhs.size(), CWF_PTR_HOST, &t) != 0)
+        return unexpected<PcgError>{detail::last(*h)};
+    RefineTelemetry r{t.outer_iterations, t.inner_iterations, t.residual_norm, t.rhs_norm, t.converged != 0,
+                      t.stagnated != 0,   {},                 t.residual_ms,   t.solve_ms};
+    r.history.assign(t.history, t.history + t.outer_iterations + 1);
+    return r;
+}
+
+// r = b - K_eff x in fp64 (cwf_hip_residual_f64): the value is |r|; residual (dof_count, or empty) receives r
+[[nodiscard]] inline auto residual_f64(const MatrixFreeSystem &system, std::span<const double> rhs,
+                                       std::span<const double> x, std::span<double> residual,
+                                       MatrixFreeWorkspace &workspace) -> expected<double, PcgError>
+{
+    if (rhs.size() != system.dof_count || x.size() != system.dof_count ||
+        (!residual.empty() && residual.size() != system.dof_count))
+        return unexpected<PcgError>{{"rhs span size mismatch", {"rhs=" + std::to_string(rhs.size()),
+                                                                 "dofs=" + std::to_string(system.dof_count)}}};
+    auto h = detail::bind(system, workspace);
+    if (!h)
+        return unexpected<PcgError>{h.error()};
+    double norm = 0.0;
+    if (cwf_hip_residual_f64(*h, rhs.data(), x.data(), residual.empty() ? nullptr : residual.data(), rhs.size(),
+                             CWF_PTR_HOST, &norm) != 0)
+        return unexpected<PcgError>{detail::last(*h)};
+    return norm;
+}
+
 }  // namespace pcg
 
 // Modal analysis (cwf_hip_modal_solve; no reference counterpart): the lowest eigenpairs of K phi = lambda M phi.
