@@ -1,0 +1,443 @@
+// abi_explicit.cpp -- the explicit central-difference stepper of the C-ABI (include/cwf_hip.h "Explicit stepper"):
+// create with the stable-step estimate (power iteration on M^-1 K), advance (per step: the handle's operator at
+// scalars (1, 0) on a copy of its DevSys, then the node pass of explicit.hip), state access, the external force,
+// its load pattern and curve, and the two host-only helpers.
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+
+#include "abi_internal.hpp"
+
+using namespace cwf;
+
+struct cwf_hip_explicit
+{
+    cwf_hip_system *sys = nullptr;
+    double alpha = 0.0, beta = 0.0, dt = 0.0, lambda_max = 0.0, critical_dt = 0.0;
+    uint64_t steps = 0;
+    bool input_stale = true;  // beta_R != 0: w has to be formed from u and v before the next step
+    float *u = nullptr, *v = nullptr, *w = nullptr, *y = nullptr, *f = nullptr, *bcv = nullptr;
+    double *lbase = nullptr, *lpat = nullptr;  // set_load_pattern: f64 [3N] each (internal order)
+    uint32_t *non_finite = nullptr;
+    std::vector<double> ctimes, cvalues;  // set_load_curve
+    double last_scale = 0.0;              // c(t) of the last step taken (get_state 4 with a pattern)
+    std::vector<void *> owned;
+};
+
+namespace
+{
+int ex_alloc(cwf_hip_explicit *t, void **p, size_t bytes)
+{
+    if (hipMalloc(p, std::max<size_t>(bytes, 16)) != hipSuccess)
+        return set_error(t->sys, CWF_ERR_ALLOC, "failed to allocate explicit stepper buffers");
+    t->owned.push_back(*p);
+    return 0;
+}
+
+std::string num(double v)
+{
+    char b[40];
+    std::snprintf(b, sizeof b, "%.17g", v);
+    return b;
+}
+
+// std::lerp as libstdc++ has it (loads.cpp:63-85 calls it)
+double lerp_ref(double a, double b, double t)
+{
+    if ((a <= 0 && b >= 0) || (a >= 0 && b <= 0))
+        return t * b + (1 - t) * a;
+    if (t == 1)
+        return b;
+    const double x = a + t * (b - a);
+    return ((t > 1) == (b > a)) ? (b < x ? x : b) : (b > x ? x : b);
+}
+
+// the handle's operator at scalars (1, 0), the handle itself untouched (abi_stepper.cpp's stiffness-only system)
+DevSys stiffness_only(const cwf_hip_system *h)
+{
+    DevSys s = h->ds;
+    s.sK = 1.0;
+    s.sM = 0.0;
+    return s;
+}
+
+int refuse_unfit(cwf_hip_system *h)
+{
+    if (h->sharded())
+        return set_error(h, CWF_ERR_UNSUPPORTED, "explicit stepping of a sharded handle is not supported",
+                         "ranks=" + std::to_string(h->nranks));
+    if (!h->ds.E)
+        return set_error(h, CWF_ERR_UNSUPPORTED, "explicit stepping needs elements", "elements=0");
+    return 0;
+}
+
+// lambda_max(M^-1 K) over the free DOFs: x <- M^-1 K x / lambda_k with lambda_k = (y . M^-1 y) / (y . x), y = K x.
+// Three vectors of its own, freed on return; the dots go through fast_dot / fast_fold (one fp64 partial per
+// 256-DOF block, fixed tree) into the handle's partial and scalar scratch, which every solve rewrites before use
+int power_iteration(cwf_hip_system *h, uint32_t iterations, double *lambda_max, double *last_change)
+{
+    const DevSys s = stiffness_only(h);
+    hipStream_t st = h->stream;
+    const size_t bytes = std::max<size_t>((size_t)s.D, 4) * sizeof(float);
+    void *buf = nullptr;
+    if (hipMalloc(&buf, 3 * bytes) != hipSuccess)
+        return set_error(h, CWF_ERR_ALLOC, "failed to allocate device buffer", "bytes=" + std::to_string(3 * bytes));
+    float *x = static_cast<float *>(buf), *y = x + bytes / sizeof(float), *z = y + bytes / sizeof(float);
+    const uint32_t nb = fast_dot_blocks(s.D);
+    (void)hipMemsetAsync(h->scal, 0, 4 * sizeof(double), st);
+    explicit_power_start(s.N, s.mask, x, st);
+    for (uint32_t it = 0; it < iterations; ++it)
+    {
+        if (h->mode == CWF_MODE_FAST)
+            fast_keff_ds(s, x, y, true, nullptr, nullptr, st);
+        else
+            parity_keff_ds(s, x, y, true, nullptr, st);
+        explicit_power_z(s.N, s.mass, s.mask, y, z, st);
+        fast_dot(y, z, x, s.D, h->part0, h->part1, st);
+        fast_fold(h->part0, nb, h->scal + 0, st);
+        fast_fold(h->part1, nb, h->scal + 1, st);
+        explicit_power_scale(s.D, z, h->scal, x, h->scal + 2 + (it & 1u), st);
+    }
+    double lam[2] = {0.0, 0.0};
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(lam, h->scal + 2, sizeof lam, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(st);
+    (void)hipFree(buf);
+    if (e != hipSuccess)
+        return hip_fail(h, e, "power iteration");
+    const double last = lam[(iterations - 1) & 1u], prev = lam[iterations & 1u];
+    if (!(last > 0.0) || !std::isfinite(last))
+        return set_error(h, CWF_ERR_DENOM_ZERO, "power iteration found no positive stiffness",
+                         "lambda_max=" + num(last));
+    *lambda_max = last;
+    if (last_change)
+        *last_change = iterations > 1 ? std::fabs(last - prev) / last : 1.0;
+    return 0;
+}
+
+double curve_at(const cwf_hip_explicit *t, double time)
+{
+    return cwf_explicit_curve_value(t->ctimes.data(), t->cvalues.data(), t->ctimes.size(), time);
+}
+
+void fill(const cwf_hip_explicit *t, cwf_explicit_telemetry *tel, bool finite)
+{
+    if (!tel)
+        return;
+    cwf_explicit_telemetry T{};
+    T.time = (double)t->steps * t->dt;
+    T.dt = t->dt;
+    T.lambda_max = t->lambda_max;
+    T.critical_dt = t->critical_dt;
+    T.steps = t->steps;
+    T.finite = finite ? 1 : 0;
+    *tel = T;
+}
+}  // namespace
+
+extern "C" {
+
+double cwf_explicit_critical_dt(double lambda_max, double rayleigh_beta)
+{
+    if (!(lambda_max > 0.0))
+        return 0.0;
+    const double omega = std::sqrt(lambda_max);
+    const double xi = rayleigh_beta * omega / 2.0;
+    return (2.0 / omega) * (std::sqrt(1.0 + xi * xi) - xi);
+}
+
+double cwf_explicit_curve_value(const double *times, const double *values, uint64_t n, double t)
+{
+    if (n == 0 || !times || !values)
+        return 1.0;
+    if (t <= times[0])
+        return values[0];
+    for (uint64_t i = 1; i < n; ++i)
+        if (t <= times[i])
+        {
+            const double span = times[i] - times[i - 1];
+            const double w = span > 0.0 ? (t - times[i - 1]) / span : 0.0;
+            return lerp_ref(values[i - 1], values[i], w);
+        }
+    return values[n - 1];
+}
+
+int cwf_hip_lambda_max(cwf_hip_system *h, uint32_t iterations, double *lambda_max, double *last_change)
+{
+    if (int st = check_ready(h))
+        return st;
+    if (!lambda_max)
+        return set_error(h, CWF_ERR_ARGUMENT, "null pointer");
+    if (int st = refuse_unfit(h))
+        return st;
+    return power_iteration(h, iterations ? iterations : 60u, lambda_max, last_change);
+}
+
+void cwf_hip_explicit_destroy(cwf_hip_explicit *t)
+{
+    if (!t)
+        return;
+    (void)hipSetDevice(t->sys->device);
+    (void)hipStreamSynchronize(t->sys->stream);
+    for (void *p : t->owned)
+        (void)hipFree(p);
+    delete t;
+}
+
+int cwf_hip_explicit_create(cwf_hip_system *h, const cwf_explicit_desc *desc, cwf_hip_explicit **out)
+{
+    if (int st = check_ready(h))
+        return st;
+    if (!desc || !out)
+        return set_error(h, CWF_ERR_ARGUMENT, "null pointer");
+    *out = nullptr;
+    if (int st = refuse_unfit(h))
+        return st;
+    const double safety = desc->safety == 0.0 ? 0.9 : desc->safety;
+    if (!(desc->rayleigh_alpha >= 0.0) || !(desc->rayleigh_beta >= 0.0) || !(desc->dt >= 0.0))
+        return set_error(h, CWF_ERR_ARGUMENT, "explicit stepper coefficients must be non-negative",
+                         "rayleigh_alpha=" + num(desc->rayleigh_alpha) + "\nrayleigh_beta=" +
+                             num(desc->rayleigh_beta) + "\ndt=" + num(desc->dt));
+    if (!(safety > 0.0 && safety <= 1.0))
+        return set_error(h, CWF_ERR_ARGUMENT, "safety must be in (0, 1]", "safety=" + num(safety));
+    double lam = 0.0;
+    if (int st = power_iteration(h, desc->power_iterations ? desc->power_iterations : 60u, &lam, nullptr))
+        return st;
+    const double crit = cwf_explicit_critical_dt(lam, desc->rayleigh_beta);
+    const double dt = desc->dt > 0.0 ? desc->dt : safety * crit;
+    if (dt > crit)
+        return set_error(h, CWF_ERR_ARGUMENT, "time step exceeds the critical step",
+                         "dt=" + num(dt) + "\ncritical_dt=" + num(crit));
+    auto *t = new (std::nothrow) cwf_hip_explicit();
+    if (!t)
+        return set_error(h, CWF_ERR_ALLOC, "host allocation failed");
+    t->sys = h;
+    t->alpha = desc->rayleigh_alpha;
+    t->beta = desc->rayleigh_beta;
+    t->dt = dt;
+    t->lambda_max = lam;
+    t->critical_dt = crit;
+    const uint64_t D = h->ds.D;
+    const size_t vb = std::max<uint64_t>(D, 4) * sizeof(float);
+    std::vector<float **> bufs = {&t->u, &t->v, &t->f, &t->bcv};
+    if (t->beta != 0.0)
+        bufs.push_back(&t->w);
+    if (h->mode != CWF_MODE_FAST)
+        bufs.push_back(&t->y);
+    int st = 0;
+    for (float **p : bufs)
+        if (!st)
+            st = ex_alloc(t, reinterpret_cast<void **>(p), vb);
+    if (!st)
+        st = ex_alloc(t, reinterpret_cast<void **>(&t->non_finite), sizeof(uint32_t));
+    if (st)
+    {
+        cwf_hip_explicit_destroy(t);
+        return st;
+    }
+    if (!t->w)
+        t->w = t->u;
+    hipStream_t s = h->stream;
+    for (float *p : {t->u, t->v, t->f, t->bcv})
+        (void)hipMemsetAsync(p, 0, vb, s);
+    (void)hipMemsetAsync(t->non_finite, 0, sizeof(uint32_t), s);
+    if (desc->external_force)
+        st = vec_in(h, desc->external_force, t->f, CWF_PTR_HOST, 3);
+    if (!st && desc->bc_value)
+        st = vec_in(h, desc->bc_value, t->bcv, CWF_PTR_HOST, 3);
+    hipError_t e = hipStreamSynchronize(s);
+    if (!st && e != hipSuccess)
+        st = hip_fail(h, e, "explicit stepper create");
+    if (st)
+    {
+        cwf_hip_explicit_destroy(t);
+        return st;
+    }
+    *out = t;
+    return 0;
+}
+
+int cwf_hip_explicit_advance(cwf_hip_explicit *t, uint64_t n_steps, cwf_explicit_telemetry *tel)
+{
+    if (!t)
+        return set_error(nullptr, CWF_ERR_ARGUMENT, "null handle");
+    cwf_hip_system *h = t->sys;
+    if (int st = check_ready(h))
+        return st;
+    hipStream_t st = h->stream;
+    const DevSys s = stiffness_only(h);
+    const bool fast = h->mode == CWF_MODE_FAST;
+    if (fast != (t->y == nullptr))
+        return set_error(h, CWF_ERR_ARGUMENT, "the handle's mode changed after the explicit stepper was created");
+    const bool damp = t->w != t->u;
+    if (damp && t->input_stale && n_steps)
+        explicit_operator_input(s.N, t->u, t->v, t->beta, t->w, st);
+    const double half = t->alpha * t->dt / 2.0;
+    const bool pattern = t->lbase && !t->ctimes.empty();
+    ExplicitPass a{};
+    a.u = t->u;
+    a.v = t->v;
+    a.w = t->w;
+    a.y = t->y;
+    a.f = t->f;
+    a.bcv = t->bcv;
+    a.lbase = pattern ? t->lbase : nullptr;
+    a.lpat = pattern ? t->lpat : nullptr;
+    a.c1 = (1.0 - half) / (1.0 + half);
+    a.c2 = t->dt / (1.0 + half);
+    a.dt = t->dt;
+    a.beta = t->beta;
+    a.non_finite = t->non_finite;
+    for (uint64_t i = 0; i < n_steps; ++i)
+    {
+        if (pattern)
+            a.scale = t->last_scale = curve_at(t, (double)t->steps * t->dt);
+        if (fast)
+            fast_keff_partials_ds(s, t->w, true, st);
+        else
+            parity_keff_ds(s, t->w, t->y, true, nullptr, st);
+        explicit_update(s, a, st);
+        ++t->steps;
+    }
+    if (n_steps)
+        t->input_stale = false;
+    uint32_t word = 0;
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(&word, t->non_finite, sizeof word, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(st);
+    if (e != hipSuccess)
+        return hip_fail(h, e, "explicit advance");
+    fill(t, tel, word == 0);
+    if (word)
+        return set_error(h, CWF_ERR_HIP, "explicit step produced a non-finite value",
+                         "steps=" + std::to_string(t->steps));
+    return 0;
+}
+
+int cwf_hip_explicit_get_state(cwf_hip_explicit *t, int which, float *out, uint64_t n, int kind)
+{
+    if (!t || !out)
+        return set_error(nullptr, CWF_ERR_ARGUMENT, "null pointer");
+    cwf_hip_system *h = t->sys;
+    if (int st = check_ready(h))
+        return st;
+    if (n != h->ds.D)
+        return set_error(h, CWF_ERR_SIZE, "state span size mismatch");
+    const float *src = which == 0 ? t->u : which == 1 ? t->v : which == 4 ? t->f : nullptr;
+    if (!src)
+        return set_error(h, CWF_ERR_ARGUMENT, "unknown state field");
+    if (which == 4 && t->lbase && !t->ctimes.empty() && t->steps)
+    {
+        // the update pass formed f_n in registers: the same rounding, on request
+        stepper_scaled_load(h->ds.D, t->lbase, t->lpat, t->last_scale, t->f, h->stream);
+        HIPTRY(h, hipGetLastError());
+    }
+    if (int st = vec_out(h, src, out, kind, 3))
+        return st;
+    HIPTRY(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+int cwf_hip_explicit_set_state(cwf_hip_explicit *t, int which, const float *in, uint64_t n, int kind)
+{
+    if (!t || !in)
+        return set_error(nullptr, CWF_ERR_ARGUMENT, "null pointer");
+    cwf_hip_system *h = t->sys;
+    if (int st = check_ready(h))
+        return st;
+    if (n != h->ds.D)
+        return set_error(h, CWF_ERR_SIZE, "state span size mismatch");
+    float *dst = which == 0 ? t->u : which == 1 ? t->v : nullptr;
+    if (!dst)
+        return set_error(h, CWF_ERR_ARGUMENT, "unknown state field");
+    if (int st = vec_in(h, in, dst, kind, 3))
+        return st;
+    t->input_stale = true;
+    HIPTRY(h, hipMemsetAsync(t->non_finite, 0, sizeof(uint32_t), h->stream));
+    HIPTRY(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+int cwf_hip_explicit_set_external_force(cwf_hip_explicit *t, const float *f, uint64_t n, int kind)
+{
+    if (!t || !f)
+        return set_error(nullptr, CWF_ERR_ARGUMENT, "null pointer");
+    cwf_hip_system *h = t->sys;
+    if (int st = check_ready(h))
+        return st;
+    if (n != h->ds.D)
+        return set_error(h, CWF_ERR_SIZE, "external force span size mismatch");
+    if (int st = vec_in(h, f, t->f, kind, 3))
+        return st;
+    HIPTRY(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+int cwf_hip_explicit_set_load_pattern(cwf_hip_explicit *t, const double *base, const double *pattern, uint64_t n)
+{
+    if (!t || !base || !pattern)
+        return set_error(nullptr, CWF_ERR_ARGUMENT, "null pointer");
+    cwf_hip_system *h = t->sys;
+    if (int st = check_ready(h))
+        return st;
+    if (n != h->ds.D)
+        return set_error(h, CWF_ERR_SIZE, "load pattern span size mismatch",
+                         "input=" + std::to_string(n) + "\ndofs=" + std::to_string(h->ds.D));
+    if (!t->lbase)
+    {
+        void *q = nullptr;
+        if (int st = ex_alloc(t, &q, std::max<uint64_t>(2 * n, 2) * sizeof(double)))
+            return st;
+        t->lbase = static_cast<double *>(q);
+        t->lpat = t->lbase + n;
+    }
+    // a node's 3 f64 = 6 floats: the node-order conversion moves them as 6-float records
+    if (int st = vec_in(h, reinterpret_cast<const float *>(base), reinterpret_cast<float *>(t->lbase), CWF_PTR_HOST, 6))
+        return st;
+    if (int st = vec_in(h, reinterpret_cast<const float *>(pattern), reinterpret_cast<float *>(t->lpat), CWF_PTR_HOST,
+                        6))
+        return st;
+    HIPTRY(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+int cwf_hip_explicit_set_load_curve(cwf_hip_explicit *t, const double *times, const double *values, uint64_t count)
+{
+    if (!t)
+        return set_error(nullptr, CWF_ERR_ARGUMENT, "null handle");
+    cwf_hip_system *h = t->sys;
+    if (count == 0)
+    {
+        t->ctimes.clear();
+        t->cvalues.clear();
+        return 0;
+    }
+    if (!times || !values)
+        return set_error(h, CWF_ERR_ARGUMENT, "null pointer");
+    if (count > CWF_EXPLICIT_MAX_CURVE_POINTS)
+        return set_error(h, CWF_ERR_SIZE, "load curve has too many points",
+                         "count=" + std::to_string(count) + "\nmax=" + std::to_string(CWF_EXPLICIT_MAX_CURVE_POINTS));
+    for (uint64_t i = 1; i < count; ++i)
+        if (!(times[i] >= times[i - 1]))
+            return set_error(h, CWF_ERR_ARGUMENT, "load curve times must ascend", "index=" + std::to_string(i));
+    t->ctimes.assign(times, times + count);
+    t->cvalues.assign(values, values + count);
+    return 0;
+}
+
+int cwf_hip_explicit_time(const cwf_hip_explicit *t, double *current_time, double *time_step)
+{
+    if (!t)
+        return set_error(nullptr, CWF_ERR_ARGUMENT, "null handle");
+    if (current_time)
+        *current_time = (double)t->steps * t->dt;
+    if (time_step)
+        *time_step = t->dt;
+    return 0;
+}
+
+}  // extern "C"

@@ -541,6 +541,9 @@ void fast_keff(const cwf_hip_system *h, const float *x, float *y, bool sanitize,
                hipStream_t st);
 void fast_keff_ds(const DevSys &s, const float *x, float *y, bool sanitize, const Ctl *ctl, double *part,
                   hipStream_t st);
+// fast_keff_ds without its finalize pass: the launch that leaves every node's partials in s.t.part (a structured
+// block: its row value). The consumer folds them in k_keff_finalize's order (explicit.hip)
+void fast_keff_partials_ds(const DevSys &s, const float *x, bool sanitize, hipStream_t st);
 void fast_dot(const float *a, const float *b, const float *c, uint32_t D, double *pab, double *pac, hipStream_t st);
 void fast_fold(const double *part, uint32_t count, double *out, hipStream_t st);
 void fast_pcg_init(cwf_hip_system *h, const float *rhs, double rel_tol, hipStream_t st);
@@ -683,5 +686,25 @@ void stepper_update(uint32_t D, const float *x, const float *up, const float *vp
                     float ib, float gob, hipStream_t st);
 void stepper_scaled_load(uint32_t D, const double *base, const double *pattern, double scale, float *f,
                          hipStream_t st);
+
+// ---- explicit.hip ----
+// one central-difference step's node pass (abi_explicit.cpp); s: the handle's DevSys at scalars (1, 0)
+struct ExplicitPass
+{
+    float *u, *v, *w;          // state; w: the operator's next input (== u when beta_R == 0)
+    const float *y;            // the operator's rows (PARITY); FAST: NULL, the pass folds s.t.part itself
+    const float *f, *bcv;      // f32 external force (read without a pattern), Dirichlet values
+    const double *lbase, *lpat;  // load pattern (NULL: none)
+    double scale;              // c(t_n) of the pattern
+    double c1, c2, dt, beta;   // the step's coefficients; beta: beta_R
+    uint32_t *non_finite;      // raised when a stored value is not finite
+};
+void explicit_update(const DevSys &s, const ExplicitPass &a, hipStream_t st);
+void explicit_operator_input(uint32_t N, const float *u, const float *v, double beta, float *w, hipStream_t st);
+// power iteration (cwf_hip_lambda_max): the start vector; z = M^-1 y over the free DOFs; x = z / (num / den),
+// the quotient stored in lam[0]
+void explicit_power_start(uint32_t N, const uint32_t *mask, float *x, hipStream_t st);
+void explicit_power_z(uint32_t N, const float *mass, const uint32_t *mask, const float *y, float *z, hipStream_t st);
+void explicit_power_scale(uint32_t D, const float *z, const double *num_den, float *x, double *lam, hipStream_t st);
 
 }  // namespace cwf

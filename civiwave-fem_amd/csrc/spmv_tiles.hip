@@ -1887,6 +1887,18 @@ void fast_keff_ds(const DevSys &s, const float *x, float *y, bool sanitize, cons
         k_keff_finalize<false><<<g, 256, 0, st>>>(s, x, y);
 }
 
+void fast_keff_partials_ds(const DevSys &s, const float *x, bool sanitize, hipStream_t st)
+{
+    if (s.N == 0 || !s.t.ntiles)
+        return;
+    PcgArgs none{};
+    const int nt = tile_threads();
+    if (s.iso)
+        sanitize ? launch_tiles<true, true, 0>(s, x, none, nt, st) : launch_tiles<true, false, 0>(s, x, none, nt, st);
+    else
+        sanitize ? launch_tiles<false, true, 0>(s, x, none, nt, st) : launch_tiles<false, false, 0>(s, x, none, nt, st);
+}
+
 // FAST search directions rotate over four buffers: p_j (iteration j's) lives in {p, p2, p3, p4}[(j + 1) % 4],
 // so iteration `it` reads p_old from [it % 4] (the prologue's p is in p) and writes the new p to
 // [(it + 1) % 4], and the last kXLag directions stay readable for the lazy x update

@@ -95,6 +95,17 @@ class StepTelemetryC(C.Structure):
     ]
 
 
+class ExplicitDescC(C.Structure):
+    _fields_ = [("rayleigh_alpha", C.c_double), ("rayleigh_beta", C.c_double), ("dt", C.c_double),
+                ("safety", C.c_double), ("power_iterations", C.c_uint32), ("reserved", C.c_uint32),
+                ("external_force", C.c_void_p), ("bc_value", C.c_void_p)]
+
+
+class ExplicitTelemetryC(C.Structure):
+    _fields_ = [("time", C.c_double), ("dt", C.c_double), ("lambda_max", C.c_double), ("critical_dt", C.c_double),
+                ("steps", C.c_uint64), ("finite", C.c_int32), ("reserved", C.c_int32)]
+
+
 class ShardInfoC(C.Structure):
     _fields_ = [
         ("owned_nodes", C.c_uint64), ("local_nodes", C.c_uint64), ("local_elements", C.c_uint64),
@@ -189,6 +200,18 @@ def load() -> C.CDLL:
         "cwf_hip_stepper_set_load_pattern": ([P, P, P, u64], i32),
         "cwf_hip_stepper_set_load_scale": ([P, C.c_double], i32),
         "cwf_hip_stepper_time": ([P, P, P], i32),
+        "cwf_hip_explicit_create": ([P, P, P], i32),
+        "cwf_hip_explicit_destroy": ([P], None),
+        "cwf_hip_explicit_advance": ([P, u64, P], i32),
+        "cwf_hip_explicit_get_state": ([P, i32, P, u64, i32], i32),
+        "cwf_hip_explicit_set_state": ([P, i32, P, u64, i32], i32),
+        "cwf_hip_explicit_set_external_force": ([P, P, u64, i32], i32),
+        "cwf_hip_explicit_set_load_pattern": ([P, P, P, u64], i32),
+        "cwf_hip_explicit_set_load_curve": ([P, P, P, u64], i32),
+        "cwf_hip_explicit_time": ([P, P, P], i32),
+        "cwf_hip_lambda_max": ([P, C.c_uint32, P, P], i32),
+        "cwf_explicit_critical_dt": ([f64, f64], f64),
+        "cwf_explicit_curve_value": ([P, P, u64, f64], f64),
         "cwf_shard_build": ([P, P, P, i32, i32, P], i32),
         "cwf_shard_get": ([P, P, P], i32),
         "cwf_shard_destroy": ([P], None),

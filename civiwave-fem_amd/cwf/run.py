@@ -2,6 +2,7 @@
 
     python -m cwf.run scenario.yaml [--steps N] [--out DIR] [--mode parity|fast] [--paused]
                                     [--time-varying-loads] [--device K]
+                                    [--integrator newmark|explicit] [--safety 0.9]
 
 The reference has no such executable (SURVEY.md section 0.4: its only binary is the viewer demo);
 this wires its pieces in the order the viewer backend does (src/ui/viewer.cpp:200-277):
@@ -10,6 +11,10 @@ frame ``step(simulation_time)``, ``simulation_time = telemetry.simulation_time +
 and OutputManager::handle_frame. The external force is evaluated once at pack time (t = 0), as in the
 reference (newmark_stepper.cpp:1369-1379); ``--time-varying-loads`` re-evaluates the load curves at
 every step's start time instead (the viewer's custom-load path, viewer.cpp:262-266).
+
+``--integrator explicit`` runs the central-difference stepper (cwf.explicit) at ``--safety`` x its estimated critical
+step instead: ``--steps`` still counts output frames, one every ceil(dt_scenario / dt_explicit) explicit steps (the
+scenario's ``time.dt`` is the output interval), through the same VTU and probe writers; loads are those of t = 0.
 
 Mesh paths are resolved like the reference (relative to the working directory) and, failing that,
 relative to the YAML file's directory. One JSON line per step is printed; the last line is a summary.
@@ -96,6 +101,47 @@ def run_scenario(cfg_path: str, steps: int, out_dir: str | None, mode: int = _li
         st.system.close()
 
 
+def run_scenario_explicit(cfg_path: str, steps: int, out_dir: str | None, mode: int = _lib.MODE_PARITY,
+                          device: int = 0, safety: float = 0.9, log=print) -> dict:
+    """`steps` output frames of the explicit stepper, ceil(cfg.time.initial_dt / dt) explicit steps each."""
+    import math
+
+    from .explicit import ExplicitStepper
+
+    cfg, m, P, materials = load_scenario(cfg_path, allow_hex8=mode == _lib.MODE_FAST)
+    try:
+        st = ExplicitStepper(P, materials, compute_rayleigh(cfg.damping), cfg.solver, cfg.time, safety=safety,
+                             mode=mode, device=device)
+    except RuntimeError as e:
+        raise ScenarioError(str(e)) from None
+    om = post.OutputManager(out_dir, m, P, materials, cfg.output, stepper=st) if out_dir else None
+    wall0, last = time.perf_counter(), None
+    try:
+        tel = st.telemetry()
+        per_frame = max(1, math.ceil(cfg.time.initial_dt / tel.dt))
+        for frame in range(steps):
+            r = st.advance(per_frame)
+            if not r.has_value():
+                raise ScenarioError(f"frame {frame}: {r.error().message} {r.error().context}")
+            tel = r.value()
+            if om is not None:
+                o = om.handle_frame(tel.time, frame)
+                if not o.has_value():
+                    raise ScenarioError(f"output frame {frame}: {o.error().message} {o.error().context}")
+            last = dict(frame=frame, time=tel.time, dt=tel.dt, steps=tel.steps)
+            log(json.dumps(last))
+        wall = time.perf_counter() - wall0
+        return dict(scenario=cfg_path, nodes=P.node_count, tets=P.element_count, dofs=P.dof_count, steps=steps,
+                    integrator="explicit", explicit_steps=tel.steps, steps_per_frame=per_frame, dt=tel.dt,
+                    critical_dt=tel.critical_dt, lambda_max=tel.lambda_max, wall_s=wall, final_time=tel.time,
+                    last=last, mode="fast" if mode == _lib.MODE_FAST else "parity")
+    finally:
+        if om is not None:
+            om.close()
+        st.close()
+        st.system.close()
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="python -m cwf.run", description=__doc__.split("\n\n")[0])
     ap.add_argument("scenario")
@@ -105,8 +151,17 @@ def main(argv=None) -> int:
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--paused", action="store_true")
     ap.add_argument("--time-varying-loads", action="store_true")
+    ap.add_argument("--integrator", choices=["newmark", "explicit"], default="newmark")
+    ap.add_argument("--safety", type=float, default=0.9, help="explicit: fraction of the critical step")
     a = ap.parse_args(argv)
     try:
+        if a.integrator == "explicit":
+            if a.time_varying_loads or a.paused:
+                raise ScenarioError("--time-varying-loads and --paused belong to the newmark integrator")
+            s = run_scenario_explicit(a.scenario, a.steps, a.out,
+                                      _lib.MODE_FAST if a.mode == "fast" else _lib.MODE_PARITY, a.device, a.safety)
+            print(json.dumps(dict(summary=s)))
+            return 0
         s = run_scenario(a.scenario, a.steps, a.out, _lib.MODE_FAST if a.mode == "fast" else _lib.MODE_PARITY,
                          a.device, a.paused, a.time_varying_loads)
     except ScenarioError as e:

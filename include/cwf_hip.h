@@ -401,6 +401,80 @@ int cwf_hip_stepper_set_warm_start(cwf_hip_stepper *st, int enabled);
 int cwf_hip_stepper_time(const cwf_hip_stepper *st, double *current_time, double *time_step);
 
 /* ---------------------------------------------------------------------------------------
+ * Explicit stepper: central differences (leapfrog) on the lumped mass, for wave propagation, impact and blast-type
+ * loads, where the physics wants a step near the mesh's stability limit anyway. No solve: a step is one operator
+ * product and one node pass. State: u_n and the half-step velocity v_(n-1/2), f32 [3N]. Per step and free DOF, in
+ * fp64, rounded to f32 only where stored:
+ *     w     = f32(u_n + beta_R v_(n-1/2))                  the operator's input (u_n itself when beta_R == 0)
+ *     y     = K w                                          the handle's operator at scalars (1, 0), f32; a constrained
+ *                                                          DOF enters it as 0, as in cwf_hip_apply_keff
+ *     f_n   = the external force at t_n = n dt             n = steps since create (not accumulated)
+ *     v_new = f32(c1 v + c2 ((f_n - y) / m))               c1 = (1 - alpha_R dt / 2) / (1 + alpha_R dt / 2),
+ *                                                          c2 = dt / (1 + alpha_R dt / 2)
+ *     u_new = f32(u + dt v_new)
+ * Constrained DOFs hold u = bc_value, v = 0. The stiffness-proportional damping force beta_R K v_(n-1/2) is lagged
+ * half a step so that it rides in the same product; it lowers the stability limit to
+ *     critical dt = (2 / omega_max) (sqrt(1 + xi^2) - xi),  xi = beta_R omega_max / 2,  omega_max^2 = lambda_max,
+ * lambda_max the largest eigenvalue of M^-1 K over the free DOFs, estimated by cwf_hip_lambda_max. The handle's
+ * scalars, mode, block inverse and solver vectors are left as they are: a Newmark stepper or a solve on the same
+ * handle is unaffected. A handle attached to a communicator is refused with CWF_ERR_UNSUPPORTED.
+ * ------------------------------------------------------------------------------------- */
+typedef struct cwf_explicit_desc
+{
+    double rayleigh_alpha, rayleigh_beta;
+    double dt;                 /* 0 -> safety * critical dt from the estimate */
+    double safety;             /* 0 -> 0.9; in (0, 1] */
+    uint32_t power_iterations; /* 0 -> 60 */
+    uint32_t reserved;
+    const float *external_force; /* [3N], as in cwf_stepper_desc; nullable: zero */
+    const float *bc_value;       /* [3N] (nullable: zero) */
+} cwf_explicit_desc;
+
+typedef struct cwf_explicit_telemetry
+{
+    double time, dt, lambda_max, critical_dt;
+    uint64_t steps;            /* steps taken since create */
+    int32_t finite, reserved;  /* 0 when a non-finite value was stored */
+} cwf_explicit_telemetry;
+
+typedef struct cwf_hip_explicit cwf_hip_explicit;
+
+#define CWF_EXPLICIT_MAX_CURVE_POINTS 4096
+
+/* Estimates lambda_max with desc->power_iterations iterations. Errors: CWF_ERR_UNSUPPORTED "explicit stepping of a
+ * sharded handle is not supported" {ranks=<n>} and "explicit stepping needs elements"; CWF_ERR_ARGUMENT "time step
+ * exceeds the critical step" {dt=<dt>, critical_dt=<limit>} for a desc->dt above the estimated limit, and for a
+ * negative coefficient or a safety outside (0, 1]. */
+int cwf_hip_explicit_create(cwf_hip_system *system, const cwf_explicit_desc *desc, cwf_hip_explicit **out);
+void cwf_hip_explicit_destroy(cwf_hip_explicit *ex);
+/* Queues n_steps steps on the handle's stream (two launches each on a FAST handle: the operator's tile launch and the
+ * update pass, which folds the node's partials itself; no hipGraph), synchronises once, then reads the device's
+ * non-finite word. tel (nullable) is filled either way. A stored u or v that is not finite raised the word: the call
+ * returns CWF_ERR_HIP "explicit step produced a non-finite value" {steps=<steps since create>} -- the device reported
+ * the failure, not the host -- and so does every later call until set_state rewrites u or v. */
+int cwf_hip_explicit_advance(cwf_hip_explicit *ex, uint64_t n_steps, cwf_explicit_telemetry *tel);
+/* which: 0 = u, 1 = v (half step), 4 = external force at the last step (get only); [3N], the caller's node order */
+int cwf_hip_explicit_get_state(cwf_hip_explicit *ex, int which, float *out, uint64_t n, int ptr_kind);
+int cwf_hip_explicit_set_state(cwf_hip_explicit *ex, int which, const float *in, uint64_t n, int ptr_kind);
+int cwf_hip_explicit_set_external_force(cwf_hip_explicit *ex, const float *f, uint64_t n, int ptr_kind);
+/* base and pattern as cwf_hip_stepper_set_load_pattern. With a pattern and a curve set, the update pass forms
+ * f_n = safe_cast(base + c(t_n) pattern) itself from the f64 arrays (cwf_hip_stepper_set_load_scale's rounding) and
+ * external_force is not read; c(t_n) = cwf_explicit_curve_value of the curve at t_n, passed to step n's launch. */
+int cwf_hip_explicit_set_load_pattern(cwf_hip_explicit *ex, const double *base, const double *pattern, uint64_t n);
+/* piecewise-linear (times ascending), 1 <= count <= CWF_EXPLICIT_MAX_CURVE_POINTS; count == 0 removes the curve */
+int cwf_hip_explicit_set_load_curve(cwf_hip_explicit *ex, const double *times, const double *values, uint64_t count);
+int cwf_hip_explicit_time(const cwf_hip_explicit *ex, double *current_time, double *time_step);
+/* lambda_max of M^-1 K over the free DOFs by `iterations` (0 -> 60) power iterations from a fixed start vector (a hash
+ * of the node index), the handle's operator at scalars (1, 0) and fp64 dots in a fixed order: the same handle gives
+ * the same bits on every call. The estimate is the quotient (K x . M^-1 K x) / (x . K x), which approaches lambda_max
+ * from below; *last_change (nullable) is the last iteration's relative change of it. */
+int cwf_hip_lambda_max(cwf_hip_system *h, uint32_t iterations, double *lambda_max, double *last_change);
+/* Host only, no GPU: the damped stability limit above (2 / sqrt(lambda_max) when rayleigh_beta == 0). */
+double cwf_explicit_critical_dt(double lambda_max, double rayleigh_beta);
+/* Host only, no GPU: evaluate_curve (loads.cpp:63-85) on n points; 1.0 for n == 0. */
+double cwf_explicit_curve_value(const double *times, const double *values, uint64_t n, double t);
+
+/* ---------------------------------------------------------------------------------------
  * Multi-GPU: node-range shards with a ghost element layer (the north
  * star's "mesh shards ... RCCL all-reduce for the PCG dot products and halo-DOF exchange").
  * The reference itself is single-device; its src/gpu/sharding.cpp:38-144 (plan_shards) only
