@@ -2,6 +2,7 @@
 // create with the stable-step estimate (power iteration on M^-1 K), advance (per step: the handle's operator at
 // scalars (1, 0) on a copy of its DevSys, then the node pass of explicit.hip), state access, the external force,
 // its load pattern and curve, and the two host-only helpers.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -21,6 +22,12 @@ struct cwf_hip_explicit
     uint32_t *non_finite = nullptr;
     std::vector<double> ctimes, cvalues;  // set_load_curve
     double last_scale = 0.0;              // c(t) of the last step taken (get_state 4 with a pattern)
+    // set_dashpots: the caller's ids and matrices as given; on the device a u32 slot per node (internal order,
+    // allocated at the first set) and the P | Q records of the current set. Empty ids: no dashpots.
+    std::vector<uint32_t> dash_ids;
+    std::vector<double> dash_C;
+    uint32_t *dslot = nullptr;
+    double *dpq = nullptr;
     std::vector<void *> owned;
 };
 
@@ -183,6 +190,7 @@ void cwf_hip_explicit_destroy(cwf_hip_explicit *t)
     (void)hipStreamSynchronize(t->sys->stream);
     for (void *p : t->owned)
         (void)hipFree(p);
+    (void)hipFree(t->dpq);
     delete t;
 }
 
@@ -290,6 +298,9 @@ int cwf_hip_explicit_advance(cwf_hip_explicit *t, uint64_t n_steps, cwf_explicit
     a.dt = t->dt;
     a.beta = t->beta;
     a.non_finite = t->non_finite;
+    const bool dash = !t->dash_ids.empty();
+    a.dslot = dash ? t->dslot : nullptr;
+    a.dpq = dash ? t->dpq : nullptr;
     for (uint64_t i = 0; i < n_steps; ++i)
     {
         if (pattern)
@@ -426,6 +437,94 @@ int cwf_hip_explicit_set_load_curve(cwf_hip_explicit *t, const double *times, co
             return set_error(h, CWF_ERR_ARGUMENT, "load curve times must ascend", "index=" + std::to_string(i));
     t->ctimes.assign(times, times + count);
     t->cvalues.assign(values, values + count);
+    return 0;
+}
+
+int cwf_hip_explicit_set_dashpots(cwf_hip_explicit *t, uint64_t count, const uint32_t *node_ids, const double *C)
+{
+    if (!t)
+        return set_error(nullptr, CWF_ERR_ARGUMENT, "null handle");
+    cwf_hip_system *h = t->sys;
+    if (int st = check_ready(h))
+        return st;
+    if (count && (!node_ids || !C))
+        return set_error(h, CWF_ERR_ARGUMENT, "null pointer");
+    const uint64_t N = h->ds.N;
+    hipStream_t s = h->stream;
+    if (count == 0)
+    {
+        HIPTRY(h, hipStreamSynchronize(s));
+        (void)hipFree(t->dpq);
+        t->dpq = nullptr;
+        t->dash_ids.clear();
+        t->dash_C.clear();
+        return 0;
+    }
+    // everything that can be refused, on the host, before anything changes
+    std::vector<uint32_t> slot(std::max<uint64_t>(N, 4), kNoDashpot);
+    for (uint64_t i = 0; i < count; ++i)
+    {
+        if (node_ids[i] >= N)
+            return set_error(h, CWF_ERR_ARGUMENT, "dashpot node out of range",
+                             "index=" + std::to_string(i) + "\nnode=" + std::to_string(node_ids[i]));
+        if (slot[node_ids[i]] != kNoDashpot)
+            return set_error(h, CWF_ERR_ARGUMENT, "dashpot node listed twice",
+                             "index=" + std::to_string(i) + "\nnode=" + std::to_string(node_ids[i]));
+        slot[node_ids[i]] = (uint32_t)i;
+    }
+    std::vector<float> mass(std::max<uint64_t>(N, 4));  // the f32 lumped mass in the caller's order
+    if (int st = vec_out(h, h->ds.mass, mass.data(), CWF_PTR_HOST, 1))
+        return st;
+    HIPTRY(h, hipStreamSynchronize(s));
+    std::vector<double> pq(18 * count);
+    for (uint64_t i = 0; i < count; ++i)
+        if (const char *why = dashpot_update(C + 9 * i, (double)mass[node_ids[i]], t->alpha, t->dt, &pq[18 * i],
+                                             &pq[18 * i + 9]))
+            return set_error(h, CWF_ERR_ARGUMENT, why, "index=" + std::to_string(i));
+    void *rec = nullptr;
+    if (hipMalloc(&rec, pq.size() * sizeof(double)) != hipSuccess)
+        return set_error(h, CWF_ERR_ALLOC, "failed to allocate explicit stepper buffers");
+    if (!t->dslot)
+    {
+        void *q = nullptr;
+        if (int st = ex_alloc(t, &q, slot.size() * sizeof(uint32_t)))
+        {
+            (void)hipFree(rec);
+            return st;
+        }
+        t->dslot = static_cast<uint32_t *>(q);
+    }
+    hipError_t e = hipMemcpyAsync(rec, pq.data(), pq.size() * sizeof(double), hipMemcpyHostToDevice, s);
+    int st = 0;
+    if (e == hipSuccess)  // the slots move to the internal order as a one-word node vector (bit copies)
+        st = vec_in(h, reinterpret_cast<const float *>(slot.data()), reinterpret_cast<float *>(t->dslot),
+                    CWF_PTR_HOST, 1);
+    if (e == hipSuccess && !st)
+        e = hipStreamSynchronize(s);
+    if (e != hipSuccess || st)
+    {
+        (void)hipStreamSynchronize(s);
+        (void)hipFree(rec);
+        t->dash_ids.clear();  // the slot array may be half written: no dashpots until the next set
+        t->dash_C.clear();
+        return st ? st : hip_fail(h, e, "explicit set_dashpots");
+    }
+    (void)hipFree(t->dpq);
+    t->dpq = static_cast<double *>(rec);
+    t->dash_ids.assign(node_ids, node_ids + count);
+    t->dash_C.assign(C, C + 9 * count);
+    return 0;
+}
+
+int cwf_hip_explicit_get_dashpots(cwf_hip_explicit *t, uint64_t *count, uint32_t *node_ids, double *C)
+{
+    if (!t || !count)
+        return set_error(nullptr, CWF_ERR_ARGUMENT, "null pointer");
+    *count = t->dash_ids.size();
+    if (node_ids)
+        std::copy(t->dash_ids.begin(), t->dash_ids.end(), node_ids);
+    if (C)
+        std::copy(t->dash_C.begin(), t->dash_C.end(), C);
     return 0;
 }
 

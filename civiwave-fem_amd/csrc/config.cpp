@@ -423,7 +423,51 @@ std::string parse_config(const yl::Node &root)
         for (size_t i = 0; i < probes.size(); ++i)
             j << (i ? ", " : "")
               << guard({"output", "probes", idx(i)}, [&] { return probes[i].as_u32(); });
-    j << "]}}";
+    j << "]}";
+    // absorbing (optional list; the key is emitted only when the document has it)
+    const yl::Node &ab = root["absorbing"];
+    if (ab.defined())
+    {
+        if (!ab.is_seq())
+            throw CfgError{"absorbing must be a sequence when present", {"absorbing"}};
+        j << ", \"absorbing\": [";
+        for (size_t i = 0; i < ab.size(); ++i)
+        {
+            const yl::Node &e = ab[i];
+            if (!e.is_map())
+                throw CfgError{"absorbing entry must be a map", {"absorbing", idx(i)}};
+            if (!e["group"].defined() || !e["group"].is_scalar())
+                throw CfgError{"absorbing.group is missing", {"absorbing", idx(i), "group"}};
+            const std::string group = guard({"absorbing", idx(i), "group"}, [&] { return e["group"].as_string(); });
+            j << (i ? ", " : "") << "{\"group\": " << jstr(group) << ", \"incident\": ";
+            const yl::Node &inc = e["incident"];
+            if (!inc.defined() || inc.is_null())
+            {
+                j << "null}";
+                continue;
+            }
+            if (!inc.is_map())
+                throw CfgError{"absorbing.incident must be a map", {"absorbing", idx(i), "incident"}};
+            const yl::Node &dn = inc["direction"];
+            if (!dn.defined() || !dn.is_seq() || dn.size() != 3)
+                throw CfgError{"absorbing.incident.direction must be a non-zero sequence[3]",
+                               {"absorbing", idx(i), "incident", "direction"}};
+            const Vec3 d = vec3(dn, {"absorbing", idx(i), "incident", "direction"});
+            if (d.v[0] == 0.0 && d.v[1] == 0.0 && d.v[2] == 0.0)
+                throw CfgError{"absorbing.incident.direction must be a non-zero sequence[3]",
+                               {"absorbing", idx(i), "incident", "direction"}};
+            const std::string curve = guard({"absorbing", idx(i), "incident", "velocity_curve"}, [&] {
+                return inc["velocity_curve"].defined() ? inc["velocity_curve"].as_string() : std::string();
+            });
+            if (!curves.count(curve))
+                throw CfgError{"absorbing incident wave references unknown curve",
+                               {"absorbing", idx(i), "incident", "velocity_curve"}};
+            j << "{\"direction\": [" << jnum(d.v[0]) << ", " << jnum(d.v[1]) << ", " << jnum(d.v[2])
+              << "], \"velocity_curve\": " << jstr(curve) << "}}";
+        }
+        j << "]";
+    }
+    j << "}";
     return j.str();
 }
 

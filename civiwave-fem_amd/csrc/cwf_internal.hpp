@@ -374,6 +374,11 @@ struct DevBuf
     size_t bytes = 0;
 };
 
+
+// ---- absorbing.cpp ----
+// cwf_explicit_dashpot_update without the error record: 0, or why C, mass, alpha or dt is refused
+const char *dashpot_update(const double C[9], double mass, double alpha, double dt, double P[9], double Q[9]);
+
 }  // namespace cwf
 
 struct cwf_hip_system
@@ -698,7 +703,10 @@ struct ExplicitPass
     double scale;              // c(t_n) of the pattern
     double c1, c2, dt, beta;   // the step's coefficients; beta: beta_R
     uint32_t *non_finite;      // raised when a stored value is not finite
+    const uint32_t *dslot;     // dashpots (NULL: none): a node's record in dpq, kNoDashpot for a node without one
+    const double *dpq;         // 18 f64 per dashpot node: P then Q, row-major (dashpot_update)
 };
+constexpr uint32_t kNoDashpot = 0xFFFFFFFFu;
 void explicit_update(const DevSys &s, const ExplicitPass &a, hipStream_t st);
 void explicit_operator_input(uint32_t N, const float *u, const float *v, double beta, float *w, hipStream_t st);
 // power iteration (cwf_hip_lambda_max): the start vector; z = M^-1 y over the free DOFs; x = z / (num / den),
@@ -706,5 +714,10 @@ void explicit_operator_input(uint32_t N, const float *u, const float *v, double 
 void explicit_power_start(uint32_t N, const uint32_t *mask, float *x, hipStream_t st);
 void explicit_power_z(uint32_t N, const float *mass, const uint32_t *mask, const float *y, float *z, hipStream_t st);
 void explicit_power_scale(uint32_t D, const float *z, const double *num_den, float *x, double *lam, hipStream_t st);
+
+
+// ---- absorbing.cpp ----
+// cwf_explicit_dashpot_update without the error record: 0, or why C, mass, alpha or dt is refused
+const char *dashpot_update(const double C[9], double mass, double alpha, double dt, double P[9], double Q[9]);
 
 }  // namespace cwf

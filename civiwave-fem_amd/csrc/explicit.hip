@@ -37,7 +37,11 @@ __device__ __forceinline__ float safe_cast(double v)
 // the f64 load pattern. DAMP: beta_R != 0, the operator's next input is its own buffer.
 // Traffic per node, FOLD, no pattern, undamped: u v f read and u v written (5 x 12 B), the partial run (12 B on a
 // structured block), mass and mask (8 B): 80 B; bc_value is read only by constrained nodes.
-template <bool FOLD, bool PATTERN, bool DAMP>
+// DASH: absorbing boundaries. Every node reads its slot (+4 B: 84 B); a dashpot node then loads its P | Q record
+// (18 f64, 144 B, nine 16-B loads that depend on the slot) and takes the matrix form of the scheme, the others the
+// expression above. With dashpots on five faces of a 150^3-node block (3.3 % of the nodes) that is 84 + 0.033 x 144
+// = 88.8 B per node. The branch diverges only in waves that touch the boundary; it is not launched without dashpots.
+template <bool FOLD, bool PATTERN, bool DAMP, bool DASH>
 __global__ __launch_bounds__(kBlock) void k_explicit_update(DevSys s, ExplicitPass a)
 {
     const uint32_t n = blockIdx.x * kBlock + threadIdx.x;
@@ -46,6 +50,9 @@ __global__ __launch_bounds__(kBlock) void k_explicit_update(DevSys s, ExplicitPa
     const F3 u = load3(a.u, n), v = load3(a.v, n);
     const uint32_t mk = s.mask[n];
     const float mass = s.mass[n];
+    uint32_t slot = kNoDashpot;
+    if constexpr (DASH)
+        slot = a.dslot[n];
     F3 y;
     if constexpr (FOLD)
     {
@@ -82,11 +89,40 @@ __global__ __launch_bounds__(kBlock) void k_explicit_update(DevSys s, ExplicitPa
     F3 un, vn, wn;
     const double m = (double)mass;
     bool bad = false;
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
+    if (DASH && slot != kNoDashpot)
     {
-        vn.c[k] = (float)(a.c1 * (double)v.c[k] + a.c2 * (((double)f.c[k] - (double)y.c[k]) / m));
-        un.c[k] = (float)((double)u.c[k] + a.dt * (double)vn.c[k]);
+        // the record is 16-B aligned (144 B records in a hipMalloc'd array)
+        const double2 *rec = reinterpret_cast<const double2 *>(a.dpq + 18ull * slot);
+        double pq[18];
+#pragma unroll
+        for (int i = 0; i < 9; ++i)
+        {
+            const double2 t = rec[i];
+            pq[2 * i] = t.x;
+            pq[2 * i + 1] = t.y;
+        }
+        const double *P = pq, *Q = pq + 9;
+        const double v0 = (double)v.c[0], v1 = (double)v.c[1], v2 = (double)v.c[2];
+        double g[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            g[k] = ((double)f.c[k] - (double)y.c[k]) / m;
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+        {
+            vn.c[k] = (float)(((P[3 * k] * v0 + P[3 * k + 1] * v1) + P[3 * k + 2] * v2) +
+                              ((Q[3 * k] * g[0] + Q[3 * k + 1] * g[1]) + Q[3 * k + 2] * g[2]));
+            un.c[k] = (float)((double)u.c[k] + a.dt * (double)vn.c[k]);
+        }
+    }
+    else
+    {
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+        {
+            vn.c[k] = (float)(a.c1 * (double)v.c[k] + a.c2 * (((double)f.c[k] - (double)y.c[k]) / m));
+            un.c[k] = (float)((double)u.c[k] + a.dt * (double)vn.c[k]);
+        }
     }
     if (mk)
     {
@@ -194,10 +230,18 @@ __global__ __launch_bounds__(kBlock) void k_power_scale(uint32_t D, const float 
 template <bool FOLD, bool PATTERN>
 void launch_update(const DevSys &s, const ExplicitPass &a, hipStream_t st)
 {
-    if (a.w != a.u)
-        k_explicit_update<FOLD, PATTERN, true><<<grid_for(s.N), kBlock, 0, st>>>(s, a);
+    // a stepper without dashpots launches the instantiations it always did
+    if (a.dslot)
+    {
+        if (a.w != a.u)
+            k_explicit_update<FOLD, PATTERN, true, true><<<grid_for(s.N), kBlock, 0, st>>>(s, a);
+        else
+            k_explicit_update<FOLD, PATTERN, false, true><<<grid_for(s.N), kBlock, 0, st>>>(s, a);
+    }
+    else if (a.w != a.u)
+        k_explicit_update<FOLD, PATTERN, true, false><<<grid_for(s.N), kBlock, 0, st>>>(s, a);
     else
-        k_explicit_update<FOLD, PATTERN, false><<<grid_for(s.N), kBlock, 0, st>>>(s, a);
+        k_explicit_update<FOLD, PATTERN, false, false><<<grid_for(s.N), kBlock, 0, st>>>(s, a);
 }
 }  // namespace
 

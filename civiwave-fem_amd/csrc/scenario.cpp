@@ -217,6 +217,8 @@ void build(cwf_scenario &sc, const std::string &cfg_path)
     const std::string json = cwf_config_json(cfg);
     cwf_config_destroy(cfg);
     sc.cfg = yl::parse(json);
+    if (sc.cfg["absorbing"].defined())  // the scenario driver steps by Newmark, whose K_eff carries no dashpots
+        throw ScenErr{CWF_ERR_UNSUPPORTED, "absorbing boundaries need the explicit integrator", "absorbing"};
     // ---- mesh
     const std::string mpath = resolve_mesh_path(cfg_path, sc.cfg["mesh_path"].as_string());
     cwf_mesh *m = nullptr;

@@ -209,6 +209,10 @@ def load() -> C.CDLL:
         "cwf_hip_explicit_set_load_pattern": ([P, P, P, u64], i32),
         "cwf_hip_explicit_set_load_curve": ([P, P, P, u64], i32),
         "cwf_hip_explicit_time": ([P, P, P], i32),
+        "cwf_hip_explicit_set_dashpots": ([P, u64, P, P], i32),
+        "cwf_hip_explicit_get_dashpots": ([P, P, P, P], i32),
+        "cwf_explicit_dashpot_update": ([P, f64, f64, f64, P, P], i32),
+        "cwf_absorbing_dashpots": ([u64, P, u64, C.c_uint32, P, P, u64, P, P, P, u64, C.c_uint32, P, P, P, P], i32),
         "cwf_hip_lambda_max": ([P, C.c_uint32, P, P], i32),
         "cwf_explicit_critical_dt": ([f64, f64], f64),
         "cwf_explicit_curve_value": ([P, P, u64, f64], f64),

@@ -14,8 +14,9 @@ from dataclasses import dataclass, field
 
 from . import _lib
 from .pcg import Expected
-from .physics import (Assignment, Config, Curve, Damping, DirichletFix, Loads, Material, OutputSettings, PointLoad,
-                      PrecisionSettings, SolverSettings, SurfaceTraction, TimeSettings)
+from .physics import (AbsorbingBoundary, Assignment, Config, Curve, Damping, DirichletFix, IncidentWave, Loads,
+                      Material, OutputSettings, PointLoad, PrecisionSettings, SolverSettings, SurfaceTraction,
+                      TimeSettings)
 
 
 @dataclass
@@ -47,6 +48,9 @@ def _from_json(d: dict) -> Config:
         dirichlet=[DirichletFix(x["group"], tuple(x["constrain_axis"]),
                                 tuple(None if v is None else f(v) for v in x["value"])) for x in d["dirichlet"]],
         output=OutputSettings(d["output"]["vtu_stride"], list(d["output"]["probes"])),
+        absorbing=[AbsorbingBoundary(a["group"], None if a["incident"] is None else
+                                     IncidentWave(_f3(a["incident"]["direction"]), a["incident"]["velocity_curve"]))
+                   for a in d.get("absorbing", [])],
     )
 
 

@@ -153,6 +153,28 @@ class ExplicitStepper:
         values = np.ascontiguousarray([p[1] for p in pts], np.float64)
         self._check(_lib.load().cwf_hip_explicit_set_load_curve(self._ex, _lib.ptr(times), _lib.ptr(values), len(pts)))
 
+    def set_dashpots(self, node_ids, C_n):
+        """Absorbing-boundary dashpots (cwf.absorbing.dashpots): distinct node ids and their 3x3 matrices [n,3,3] or
+        [9n]. Replaces the previous set; u, v, the step count and the loads are kept. Raises on a refused set, which
+        leaves the previous one in force."""
+        ids = np.ascontiguousarray(node_ids, np.uint32).reshape(-1)
+        mats = np.ascontiguousarray(C_n, np.float64).reshape(-1)
+        if mats.size != 9 * ids.size:
+            raise ValueError("C must hold 9 values per dashpot node")
+        self._check(_lib.load().cwf_hip_explicit_set_dashpots(self._ex, ids.size, _lib.ptr(ids), _lib.ptr(mats)))
+
+    def get_dashpots(self):
+        """-> (node_ids u32 [n], C f64 [n,3,3]) as they were set."""
+        n = C.c_uint64()
+        self._check(_lib.load().cwf_hip_explicit_get_dashpots(self._ex, C.byref(n), None, None))
+        ids = np.zeros(n.value, np.uint32)
+        mats = np.zeros(9 * n.value, np.float64)
+        self._check(_lib.load().cwf_hip_explicit_get_dashpots(self._ex, C.byref(n), _lib.ptr(ids), _lib.ptr(mats)))
+        return ids, mats.reshape(-1, 3, 3)
+
+    def clear_dashpots(self):
+        self._check(_lib.load().cwf_hip_explicit_set_dashpots(self._ex, 0, None, None))
+
     def close(self):
         if getattr(self, "_ex", None) is not None:
             _lib.load().cwf_hip_explicit_destroy(self._ex)

@@ -93,6 +93,18 @@ class OutputSettings:
 
 
 @dataclass
+class IncidentWave:
+    direction: tuple  # the incident particle velocity is direction * curve(t), in m/s
+    velocity_curve: str
+
+
+@dataclass
+class AbsorbingBoundary:
+    group: str
+    incident: Optional[IncidentWave] = None
+
+
+@dataclass
 class Config:
     mesh_path: str = ""
     materials: list = field(default_factory=list)
@@ -105,6 +117,7 @@ class Config:
     curves: dict = field(default_factory=dict)
     dirichlet: list = field(default_factory=list)
     output: OutputSettings = field(default_factory=OutputSettings)
+    absorbing: list = field(default_factory=list)  # [AbsorbingBoundary] (explicit integrator only)
 
 
 # ---- materials.hpp -----------------------------------------------------------------------

@@ -15,6 +15,8 @@ every step's start time instead (the viewer's custom-load path, viewer.cpp:262-2
 ``--integrator explicit`` runs the central-difference stepper (cwf.explicit) at ``--safety`` x its estimated critical
 step instead: ``--steps`` still counts output frames, one every ceil(dt_scenario / dt_explicit) explicit steps (the
 scenario's ``time.dt`` is the output interval), through the same VTU and probe writers; loads are those of t = 0.
+A scenario's ``absorbing:`` entries (explicit only) put viscous dashpots on their groups' faces; an entry's
+``incident: {direction, velocity_curve}`` feeds that curve in through the dashpots as an incident wave.
 
 Mesh paths are resolved like the reference (relative to the working directory) and, failing that,
 relative to the YAML file's directory. One JSON line per step is printed; the last line is a summary.
@@ -67,6 +69,8 @@ def load_scenario(cfg_path: str, allow_hex8: bool = False):
 def run_scenario(cfg_path: str, steps: int, out_dir: str | None, mode: int = _lib.MODE_PARITY, device: int = 0,
                  paused: bool = False, time_varying_loads: bool = False, log=print) -> dict:
     cfg, m, P, materials = load_scenario(cfg_path, allow_hex8=mode == _lib.MODE_FAST)
+    if cfg.absorbing:
+        raise ScenarioError("absorbing boundaries need the explicit integrator")
     st = Stepper(P, materials, compute_rayleigh(cfg.damping), cfg.solver, cfg.time, mode=mode, device=device)
     om = post.OutputManager(out_dir, m, P, materials, cfg.output, stepper=st) if out_dir else None
     t_sim, total_iters, wall0 = 0.0, 0, time.perf_counter()
@@ -117,6 +121,7 @@ def run_scenario_explicit(cfg_path: str, steps: int, out_dir: str | None, mode: 
     om = post.OutputManager(out_dir, m, P, materials, cfg.output, stepper=st) if out_dir else None
     wall0, last = time.perf_counter(), None
     try:
+        absorbing_nodes = set_absorbing(st, cfg, m, P)
         tel = st.telemetry()
         per_frame = max(1, math.ceil(cfg.time.initial_dt / tel.dt))
         for frame in range(steps):
@@ -134,12 +139,57 @@ def run_scenario_explicit(cfg_path: str, steps: int, out_dir: str | None, mode: 
         return dict(scenario=cfg_path, nodes=P.node_count, tets=P.element_count, dofs=P.dof_count, steps=steps,
                     integrator="explicit", explicit_steps=tel.steps, steps_per_frame=per_frame, dt=tel.dt,
                     critical_dt=tel.critical_dt, lambda_max=tel.lambda_max, wall_s=wall, final_time=tel.time,
-                    last=last, mode="fast" if mode == _lib.MODE_FAST else "parity")
+                    last=last, mode="fast" if mode == _lib.MODE_FAST else "parity", absorbing_nodes=absorbing_nodes)
     finally:
         if om is not None:
             om.close()
         st.close()
         st.system.close()
+
+
+def absorbing_setup(cfg, m, P):
+    """The scenario's ``absorbing:`` entries -> (node_ids, C summed per node, load base, load pattern, curve); the last
+    three are None without an incident wave. base is the static load vector, pattern the entries' incident patterns
+    summed, curve the one curve they name."""
+    import numpy as np
+
+    from . import absorbing
+
+    parts, pattern, names = [], np.zeros(P.dof_count, np.float64), []
+    for i, entry in enumerate(cfg.absorbing):
+        try:
+            ids, Cn = absorbing.dashpots(m, cfg, absorbing.faces_of_group(m, entry.group))
+        except (KeyError, ValueError, RuntimeError) as e:
+            raise ScenarioError(f"absorbing [{i}]: {e.args[0] if e.args else e}") from None
+        if not ids.size:
+            raise ScenarioError(f"absorbing [{i}]: group '{entry.group}' has no boundary faces")
+        parts.append((ids, Cn))
+        if entry.incident is not None:
+            pattern += absorbing.incident_pattern(ids, Cn, entry.incident.direction, P.node_count)
+            if entry.incident.velocity_curve not in names:
+                names.append(entry.incident.velocity_curve)
+    if len(names) > 1:
+        raise ScenarioError("explicit stepper takes one load curve")
+    ids, Cn = absorbing.merge(parts)
+    if not names:
+        return ids, Cn, None, None, None
+    base = pack.assemble_load_vector(m, cfg, P.lumped_mass64)
+    return ids, Cn, base, pattern, cfg.curves[names[0]]
+
+
+def set_absorbing(st, cfg, m, P) -> int:
+    """Put the scenario's absorbing boundaries and incident wave on an ExplicitStepper -> dashpot nodes."""
+    if not cfg.absorbing:
+        return 0
+    ids, Cn, base, pattern, curve = absorbing_setup(cfg, m, P)
+    if curve is not None:
+        st.set_load_pattern(base, pattern)
+        st.set_load_curve(curve)
+    try:
+        st.set_dashpots(ids, Cn)
+    except RuntimeError as e:
+        raise ScenarioError(str(e)) from None
+    return int(ids.size)
 
 
 def main(argv=None) -> int:

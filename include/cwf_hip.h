@@ -418,6 +418,30 @@ int cwf_hip_stepper_time(const cwf_hip_stepper *st, double *current_time, double
  * lambda_max the largest eigenvalue of M^-1 K over the free DOFs, estimated by cwf_hip_lambda_max. The handle's
  * scalars, mode, block inverse and solver vectors are left as they are: a Newmark stepper or a solve on the same
  * handle is unaffected. A handle attached to a communicator is refused with CWF_ERR_UNSUPPORTED.
+ *
+ * Absorbing boundaries (cwf_hip_explicit_set_dashpots): a dashpot node n carries a symmetric positive-semidefinite
+ * 3x3 matrix C_n in N s / m -- a full matrix, not a diagonal: on a face with unit normal nu and tributary area a the
+ * viscous (Lysmer-Kuhlemeyer) boundary is C = rho a (V_p nu nu^T + V_s (I - nu nu^T)), diagonal only on axis-aligned
+ * faces (cwf_absorbing_dashpots). Its force takes the central average the mass-proportional term has,
+ * (alpha_R M + C)(v_new + v) / 2, which is solved per node: with h = alpha_R dt / 2, B = C dt / (2 m) and
+ * A = ((1 + h) I + B)^-1,
+ *     P = A ((1 - h) I - B),   Q = dt A                      3x3 each, fp64, formed once on the host
+ *                                                            (cwf_explicit_dashpot_update)
+ *     g_j     = ((double)f_j - (double)y_j) / m              as above, m the f32 lumped mass widened to double
+ *     v_new_k = f32(((P_k0 v_0 + P_k1 v_1) + P_k2 v_2) + ((Q_k0 g_0 + Q_k1 g_1) + Q_k2 g_2))
+ *     u_new_k = f32(u_k + dt v_new_k)                        then constrained DOFs as above (u = bc_value, v = 0)
+ * in exactly this association order, without fused multiply-adds. A node without a dashpot keeps the expression
+ * above; with C = 0 the matrix form reduces to it (P = c1 I, Q = c2 I) up to the rounding of the products. beta_R != 0
+ * keeps its lagged form, w = f32(u + beta_R v) as stored above. An incident wave enters through such a boundary as
+ * the force 2 C_n v_inc(t) on the dashpot nodes (the compliant base): a load pattern of rows 2 C_n d with the load
+ * curve c(t) gives the incident velocity d c(t).
+ * The critical step is unchanged. C enters implicitly, through the average vbar = (v_new + v) / 2: with
+ * M (v_new - v) / dt + (alpha_R M + C) vbar + K u = f the leapfrog energy
+ * 1/2 v_new^T M v_new + 1/2 u_new^T K u_new - (dt / 2) v_new^T K u_new, which is positive definite exactly below the
+ * critical step of M^-1 K alone, changes per unforced step by -dt vbar^T (alpha_R M + C) vbar <= 0 for every symmetric
+ * C >= 0, however large; per node the eigenvalues of P are ((1 - h) - b) / ((1 + h) + b) with b >= 0 those of B, inside
+ * (-1, 1]. So critical_dt and lambda_max are those of the stepper without dashpots, and dashpots scaled by 1e4 run at
+ * the same step (tests/test_gpu_absorbing.py).
  * ------------------------------------------------------------------------------------- */
 typedef struct cwf_explicit_desc
 {
@@ -464,6 +488,40 @@ int cwf_hip_explicit_set_load_pattern(cwf_hip_explicit *ex, const double *base, 
 /* piecewise-linear (times ascending), 1 <= count <= CWF_EXPLICIT_MAX_CURVE_POINTS; count == 0 removes the curve */
 int cwf_hip_explicit_set_load_curve(cwf_hip_explicit *ex, const double *times, const double *values, uint64_t count);
 int cwf_hip_explicit_time(const cwf_hip_explicit *ex, double *current_time, double *time_step);
+/* Dashpots of the scheme above: `count` distinct nodes (the caller's numbering) and their C_n (f64, 9 per node,
+ * row-major). P and Q are formed per node from the stepper's alpha_R, dt and the node's f32 mass and uploaded with a
+ * u32 slot per node (0xFFFFFFFF: none) and one 144-byte fp64 P | Q record per dashpot node; the update pass reads the
+ * slot only while a set is in force. u, v, the step count and the load state are kept; a later call replaces the set,
+ * count == 0 removes it (the stepper then launches what a stepper that never had dashpots launches). Errors, all
+ * CWF_ERR_ARGUMENT and leaving the previous set in force: "dashpot node out of range" {index=<i>, node=<id>},
+ * "dashpot node listed twice" {index=<i>, node=<id>}, and a refused matrix (cwf_explicit_dashpot_update's texts)
+ * {index=<i>}. A dashpot on a constrained DOF has no effect: the mask wins. */
+int cwf_hip_explicit_set_dashpots(cwf_hip_explicit *ex, uint64_t count, const uint32_t *node_ids, const double *C);
+/* The set in force as it was given; node_ids and C are nullable (count only). */
+int cwf_hip_explicit_get_dashpots(cwf_hip_explicit *ex, uint64_t *count, uint32_t *node_ids, double *C);
+/* Host only, no GPU: P and Q of the scheme above from C (row-major), the node's mass, alpha_R and dt, by the
+ * closed-form 3x3 inverse. CWF_ERR_ARGUMENT for a C that is not finite ("dashpot matrix is not finite"), not symmetric
+ * (|C_ij - C_ji| > 1e-12 trace: "dashpot matrix is not symmetric") or not positive semidefinite (a principal minor
+ * below -1e-12 in units of the trace: "dashpot matrix is not positive semidefinite"), for mass <= 0 ("dashpot node
+ * mass must be positive") and for a negative or non-finite alpha or dt. */
+int cwf_explicit_dashpot_update(const double C[9], double mass, double alpha, double dt, double P[9], double Q[9]);
+/* Host only, no GPU: the viscous-boundary matrices of a face list. coords f64 [3 node_count]; connectivity u32
+ * [nodes_per_element (4: tet4, 8: hex8 in Gmsh corner order) x element_count]; element_material [element_count] indexes
+ * rho, lame_lambda, lame_mu [material_count]; faces u32 [nodes_per_face (3 or 4) x face_count]. Every face must be a
+ * face of exactly one element, whose material gives V_p = sqrt((lambda + 2 mu) / rho) and V_s = sqrt(mu / rho): a
+ * layered block gets its strata's impedances. Area and unit normal come from the face's nodes (a quad: its triangles
+ * (0,1,2) + (0,2,3), the normal along the sum of their cross products); each of the face's k nodes gets
+ * rho (a / k)(V_p nu nu^T + V_s (I - nu nu^T)). Out: *count distinct nodes touched, ascending, in node_ids, and their
+ * accumulated C_n in C (9 per node, row-major); both need room for min(node_count, nodes_per_face x face_count)
+ * entries. Errors: CWF_ERR_ARGUMENT "absorbing face is not a boundary face of the mesh" {face=<i>} and "absorbing
+ * face has zero area" {face=<i>}; CWF_ERR_NODE_RANGE "absorbing face references node out of range" {face=<i>,
+ * node=<id>}. */
+int cwf_absorbing_dashpots(uint64_t node_count, const double *coords, uint64_t element_count,
+                           uint32_t nodes_per_element, const uint32_t *connectivity,
+                           const uint32_t *element_material, uint64_t material_count, const double *rho,
+                           const double *lame_lambda, const double *lame_mu, uint64_t face_count,
+                           uint32_t nodes_per_face, const uint32_t *faces, uint64_t *count, uint32_t *node_ids,
+                           double *C);
 /* lambda_max of M^-1 K over the free DOFs by `iterations` (0 -> 60) power iterations from a fixed start vector (a hash
  * of the node index), the handle's operator at scalars (1, 0) and fp64 dots in a fixed order: the same handle gives
  * the same bits on every call. The estimate is the quotient (K x . M^-1 K x) / (x . K x), which approaches lambda_max

@@ -2,6 +2,7 @@
 """Measure the explicit stepper: steps/s next to the operator's own time and to the Newmark stepper.
 
     python tools/explicit_bench.py [--configs c2 c3 c2:hex8] [--steps 2000] [--newmark-steps 3] [--out FILE]
+    python tools/explicit_bench.py --absorbing [--configs c3] [--steps 2000]
 
 Per config (a FAST handle of the block, created with scalars (1, 0)), in one process and one JSON line each, appended
 to --out (default profiles/explicit_c2.json):
@@ -13,6 +14,11 @@ to --out (default profiles/explicit_c2.json):
     the apply path's finalize pass (44 B per node), so step_us - keff_us is its cost over that pass;
   - simulated seconds per wall second, and the same for the Newmark stepper at the scenario's dt on the same handle
     (newmark-steps steps after one warm-up step).
+
+--absorbing: the cost of absorbing boundaries instead. Per config one line, appended to
+profiles/explicit_absorbing.json: step_us of the stepper without dashpots, with viscous dashpots (cwf.absorbing) on the
+five faces of the block other than z = max, and after clear_dashpots again, in one process on one handle; the share
+of dashpot nodes and the bytes per node the update pass then moves (84 + 144 x share).
 """
 import argparse
 import ctypes as C
@@ -88,17 +94,70 @@ def measure(key, steps, newmark_steps, device):
     return out
 
 
+def timed_steps(ex, steps):
+    assert ex.advance(200).has_value()
+    t0 = time.perf_counter()
+    r = ex.advance(steps)
+    wall = time.perf_counter() - t0
+    assert r.has_value() and r.value().finite, r.error() if not r.has_value() else "non-finite"
+    return 1e6 * wall / steps
+
+
+def measure_absorbing(key, steps, device):
+    import numpy as np
+
+    from cwf import absorbing, meshgen
+
+    name, _, element = key.partition(":")
+    element = element or "tet4"
+    case = scenarios.config_case(name, element=element)
+    P, m = case.packing, case.mesh
+    X = m.coords
+    lo, hi = X.min(0), X.max(0)
+    k = m.tets.shape[1]
+    faces = []
+    for axis, value in ((0, lo[0]), (0, hi[0]), (1, lo[1]), (1, hi[1]), (2, lo[2])):
+        on = np.nonzero(X[:, axis] == value)[0]
+        sel = np.zeros(P.node_count, bool)
+        sel[on] = True
+        t = m.tets[sel[m.tets].sum(1) >= (4 if k == 8 else 3)]  # only elements with a face on that plane
+        faces.append(meshgen.boundary_faces(t, on))
+    t0 = time.perf_counter()
+    ids, Cn = absorbing.dashpots(m, case.cfg, np.concatenate(faces))
+    out = dict(config=key, name=case.name, nodes=P.node_count, dashpot_nodes=int(ids.size),
+               dashpot_share=ids.size / P.node_count, dashpots_s=time.perf_counter() - t0, steps=steps)
+    sysm = pcg.MatrixFreeSystem.from_packing(P, case.materials, 1.0, 0.0, mode=_lib.MODE_FAST, device=device)
+    out["kernel"] = (_lib.load().cwf_hip_system_keff_kernel(sysm.handle()) or b"").decode()
+    ex = ExplicitStepper(P, case.materials, RayleighCoefficients(0.0, 0.0), system=sysm)
+    out["dt"] = ex.telemetry().dt
+    out["step_us"] = timed_steps(ex, steps)
+    ex.set_dashpots(ids, Cn)
+    out["step_us_absorbing"] = timed_steps(ex, steps)
+    ex.clear_dashpots()
+    out["step_us_cleared"] = timed_steps(ex, steps)
+    out["absorbing_over_plain"] = out["step_us_absorbing"] / out["step_us"]
+    out["update_bytes_per_node"] = 80
+    out["update_bytes_per_node_absorbing"] = 84 + 144 * out["dashpot_share"]
+    ex.close()
+    sysm.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", nargs="+", default=["c2", "c3", "c2:hex8"])
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--newmark-steps", type=int, default=3)
     ap.add_argument("--device", type=int, default=0)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "explicit_c2.json"))
+    ap.add_argument("--absorbing", action="store_true", help="the cost of dashpots on five faces (see above)")
+    ap.add_argument("--out", default=None, help="default profiles/explicit_c2.json (--absorbing: "
+                                                 "profiles/explicit_absorbing.json)")
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "explicit_absorbing.json" if a.absorbing else "explicit_c2.json")
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    for key in a.configs:
-        line = json.dumps(measure(key, a.steps, a.newmark_steps, a.device))
+    for key in (["c3"] if a.absorbing and a.configs == ap.get_default("configs") else a.configs):
+        line = json.dumps(measure_absorbing(key, a.steps, a.device) if a.absorbing else
+                          measure(key, a.steps, a.newmark_steps, a.device))
         print(line, flush=True)
         with open(a.out, "a") as f:
             f.write(line + "\n")
