@@ -587,28 +587,32 @@ __global__ __launch_bounds__(NT) void k_keff_tiles(DevSys s, const float *__rest
             a1 += sf[(c + 1) * kTileElems + el];
             a2 += sf[(c + 2) * kTileElems + el];
         }
+        if constexpr (MODE == 1)
+        {
+            const float p0 = sp[i], p1 = sp[ms + i], p2 = sp[2 * ms + i];
+            // the node's owner slot carries its mass term m s_M p (once), as k_keff_tiles_pipe's does: the update
+            // pass forms r -= alpha Ap from the partials alone (k_pcg_update_tiles adds no mass term of its own)
+            if (tn.x & 0x80000000u)
+            {
+                const float m = s.mass[tn.x & 0x7fffffffu] * sM;
+                a0 = fmaf(m, p0, a0);
+                a1 = fmaf(m, p1, a1);
+                a2 = fmaf(m, p2, a2);
+                if (pa.pnew)  // and stores the new p for the update pass
+                {
+                    float *q = pa.pnew + 3ull * (tn.x & 0x7fffffffu);
+                    q[0] = p0;
+                    q[1] = p1;
+                    q[2] = p2;
+                }
+            }
+            if (!ablate(pa, 4u) && (tn.x & 0x7fffffffu) < s.Nown)  // ghosts: another rank's row
+                pap += (double)fmaf(p2, a2, fmaf(p1, a1, p0 * a0));  // fp32 per node, fp64 across nodes
+        }
         float *o = T.part + 3ull * (nb + i);
         o[0] = a0;
         o[1] = a1;
         o[2] = a2;
-        if (MODE == 1 && pa.pnew && (tn.x & 0x80000000u))  // owner slot: the new p for the update pass
-        {
-            float *q = pa.pnew + 3ull * (tn.x & 0x7fffffffu);
-            q[0] = sp[i];
-            q[1] = sp[ms + i];
-            q[2] = sp[2 * ms + i];
-        }
-        if (MODE == 1 && !ablate(pa, 4u) && (tn.x & 0x7fffffffu) < s.Nown)  // ghosts: another rank's row
-        {
-            const float p0 = sp[i], p1 = sp[ms + i], p2 = sp[2 * ms + i];
-            pap += (double)fmaf(p2, a2, fmaf(p1, a1, p0 * a0));  // fp32 per node, fp64 across nodes
-            if (tn.x & 0x80000000u)  // the node's owner slot adds its mass term m s_M |p|^2 once
-            {
-                const float m = s.mass[tn.x & 0x7fffffffu] * sM;
-                pap += (double)(m * p0) * (double)p0 + (double)(m * p1) * (double)p1 +
-                       (double)(m * p2) * (double)p2;
-            }
-        }
     }
     if constexpr (MODE == 1)
     {

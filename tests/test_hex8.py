@@ -61,7 +61,8 @@ def test_hex8_preprocess_rejects_inverted_element():
     assert e.value.context == ["elements [1]"]
 
 
-def test_hex8_oracle_rigid_modes_and_patch_test():
+def test_hex8_oracle_rigid_modes_and_patch_test(D=D_STEEL):
+    """D (tests/test_materials_host.py): another stiffness than the steel's; 30 GPa stays the scale of its entries."""
     tm, inner = jittered_hex(4, 3, 3, amp=0.2)
     c, hexes = tm.coords, tm.tets
     N, E = c.shape[0], hexes.shape[0]
@@ -73,16 +74,16 @@ def test_hex8_oracle_rigid_modes_and_patch_test():
     # rigid translation and (linearised) rotation -> no forces
     for u in (np.tile([1.0, -2.0, 0.5], N),
               np.cross(np.array([0.3, -0.2, 0.5]), c - c.mean(0)).reshape(-1)):
-        y = O.hex8_apply(c, hexes, mat, D_STEEL, 1.0, 0.0, mass, mask, u.astype(np.float32))
+        y = O.hex8_apply(c, hexes, mat, D, 1.0, 0.0, mass, mask, u.astype(np.float32))
         assert np.abs(y).max() <= 1e-6 * scale * np.abs(u).max()
     # constant-strain patch test on distorted hexes: interior nodes carry no force
     A = np.array([[1.0, 2.0, -3.0], [0.5, -1.0, 2.0], [3.0, 1.0, 0.25]]) * 1e-3
     u = (c @ A.T).astype(np.float32).reshape(-1)
-    y = O.hex8_apply(c, hexes, mat, D_STEEL, 1.0, 0.0, mass, mask, u).reshape(-1, 3)
+    y = O.hex8_apply(c, hexes, mat, D, 1.0, 0.0, mass, mask, u).reshape(-1, 3)
     assert np.abs(y[inner]).max() <= 1e-6 * np.abs(y[~inner]).max()
 
 
-def test_hex8_oracle_symmetric_positive_and_diag_blocks():
+def test_hex8_oracle_symmetric_positive_and_diag_blocks(D=D_STEEL):
     tm, _ = jittered_hex(3, 3, 2, amp=0.2)
     c, hexes = tm.coords, tm.tets
     N, E = c.shape[0], hexes.shape[0]
@@ -91,17 +92,17 @@ def test_hex8_oracle_symmetric_positive_and_diag_blocks():
     mass = np.zeros(N, np.float32)
     rng = np.random.Generator(np.random.PCG64(5))
     a, b = rng.standard_normal((2, 3 * N)).astype(np.float32)
-    Ka = O.hex8_apply(c, hexes, mat, D_STEEL, 1.0, 0.0, mass, mask, a).astype(np.float64)
-    Kb = O.hex8_apply(c, hexes, mat, D_STEEL, 1.0, 0.0, mass, mask, b).astype(np.float64)
+    Ka = O.hex8_apply(c, hexes, mat, D, 1.0, 0.0, mass, mask, a).astype(np.float64)
+    Kb = O.hex8_apply(c, hexes, mat, D, 1.0, 0.0, mass, mask, b).astype(np.float64)
     assert abs(b @ Ka - a @ Kb) <= 1e-6 * abs(a @ Ka)
     assert a @ Ka > 0 and b @ Kb > 0
-    blk = O.hex8_diag_blocks(c, hexes, mat, D_STEEL, 1.0)
+    blk = O.hex8_diag_blocks(c, hexes, mat, D, 1.0)
     for n in (0, N // 2, N - 1):
         col = np.zeros((3, 3))
         for k in range(3):
             e = np.zeros(3 * N, np.float32)
             e[3 * n + k] = 1.0
-            col[:, k] = O.hex8_apply(c, hexes, mat, D_STEEL, 1.0, 0.0, mass, mask, e)[3 * n:3 * n + 3]
+            col[:, k] = O.hex8_apply(c, hexes, mat, D, 1.0, 0.0, mass, mask, e)[3 * n:3 * n + 3]
         assert np.abs(col - blk[n]).max() <= 1e-6 * np.abs(blk[n]).max()
 
 

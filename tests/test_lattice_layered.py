@@ -122,17 +122,24 @@ def test_layered_block_is_described(layered):
     assert describe_plain(fast_system(case)) is None
 
 
-def test_layered_tables_reproduce_the_oracle_operator(layered):
+def test_layered_tables_reproduce_the_oracle_operator(layered, materials=None):
+    """materials (tests/test_materials_host.py): other strata stiffnesses than the case's; the tables are then
+    described from them, not taken from the fixture."""
     case, shape, layers, d = layered
     P = case.packing
     sK, sM = case.scalars()
+    if materials is not None:
+        d = describe_layers(pcg.MatrixFreeSystem.from_packing(P, materials, sK, sM, mode=_lib.MODE_FAST))
+        assert d is not None and not d["hex"]
+    else:
+        materials = case.materials
     rng = np.random.Generator(np.random.PCG64(1))
     x = rng.uniform(-1, 1, P.dof_count).astype(np.float32)
     mask = (np.repeat(P.bc_mask, 3) & np.tile(np.array([1, 2, 4], np.uint32), P.node_count)) != 0
     xs = np.where(mask, 0.0, x.astype(np.float64))
     y = layered_apply(d, xs, sK).reshape(-1) + sM * np.repeat(P.lumped_mass.astype(np.float64), 3) * xs
     y = np.where(mask, x, y)
-    ref = oracle_system(P, case.materials, sK, sM).apply_keff(x).astype(np.float64)
+    ref = oracle_system(P, materials, sK, sM).apply_keff(x).astype(np.float64)
     err = np.max(np.abs(y - ref)) / np.max(np.abs(ref))
     print(f"layered tables vs oracle: {err:.3e} of max |row|")
     assert err <= 1e-6
