@@ -114,14 +114,19 @@ std::vector<uint32_t> parity_compact_tiles(const std::vector<uint32_t> &off, con
     return nodes;
 }
 
+// compact tiles for single handles (a shard's PCG loop folds p.Ap into rank-ordered chunk partials in the tile
+// kernel, which needs tiles of consecutive nodes); CWF_PARITY_TILES=strip keeps the strips
+bool parity_compact_tiles_wanted(const cwf_hip_system *h)
+{
+    const char *pt = knob("CWF_PARITY_TILES");
+    return !h->sharded() && h->ds.E <= kParityCompactMaxTets && !(pt && std::strcmp(pt, "strip") == 0);
+}
+
 int parity_incidence_slots(cwf_hip_system *h)
 {
     DevSys &s = h->ds;
     const uint64_t N = s.N, E = s.E;
-    // compact tiles for single handles (a shard's PCG loop folds p.Ap into rank-ordered chunk partials in the tile
-    // kernel, which needs tiles of consecutive nodes); CWF_PARITY_TILES=strip keeps the strips
-    const char *pt = knob("CWF_PARITY_TILES");
-    const bool compact = !h->sharded() && E <= kParityCompactMaxTets && !(pt && std::strcmp(pt, "strip") == 0);
+    const bool compact = parity_compact_tiles_wanted(h);
     std::vector<uint32_t> off, inc, toff, tets, pinc, conn, tnodes;
     try
     {
@@ -1233,61 +1238,19 @@ int cwf_hip_system_exchange_schedule(const cwf_hip_system *h)
     return h && h->sharded() ? exchange_schedule_code(h->sched) : -1;
 }
 
+// the PCG loop's instantiation (no sanitize) of the element pass, from the picker that launches it
 const char *cwf_hip_system_keff_kernel(const cwf_hip_system *h)
 {
     if (!h)
         return nullptr;
-    const DevTiles &t = h->ds.t;
-    if (h->mode != CWF_MODE_FAST || !t.ntiles)  // the PCG-loop instantiation (no sanitize) of the element pass
-    {
-        // the PCG loop's: strips fuse the p.Ap partials (DOT), compact tiles do not (parity_incidence_slots)
-        const char *pt = knob("CWF_PARITY_TILES");
-        const bool compact = h->ds.ptile_nodes || (!h->ds.ptile_off && !h->sharded() && h->ds.E <= kParityCompactMaxTets &&
-                                                    !(pt && !std::strcmp(pt, "strip")));
-        if (compact)
-            return h->ds.iso ? "k_keff_parity_tile<true, false, false, true>" : "k_keff_parity_tile<false, false, false, true>";
-        return h->ds.iso ? "k_keff_parity_tile<true, false, true, false>" : "k_keff_parity_tile<false, false, true, false>";
-    }
+    if (h->mode != CWF_MODE_FAST || !h->ds.t.ntiles)  // the tiles as built, else as parity_incidence_slots will build them
+        return parity_keff_kernel_name(h, h->ds.ptile_nodes || (!h->ds.ptile_off && parity_compact_tiles_wanted(h)));
     const PcgSchedule sch = schedule_of(h);
     if (sch == PcgSchedule::Resident)
-    {  // the resident solve's one launch per solve (resident.hip)
-        static thread_local char name[96];
-        snprintf(name, sizeof name, "k_pcg_resident<%s, %s, %u, %u, %s>", t.lsym ? "true" : "false",
-                 t.lhex ? "LatHex" : "LatKuhn", h->res.npt, h->res.nph, h->res.shard ? "true" : "false");
-        return name;
-    }
-    if (sch == PcgSchedule::Fused || sch == PcgSchedule::FusedPeer)  // the fused iteration's one launch (lattice_fused.inc)
-    {
-        static thread_local char name[112];
-        snprintf(name, sizeof name, "k_pcg_lattice<%s, %s, %s, %s, %s, %s>", t.lsym ? "true" : "false",
-                 t.lhex ? "LatHex" : "LatKuhn", t.lmu ? "true" : "false", t.lpstride ? "true" : "false",
-                 !t.lpstride && h->ds.Nown < h->ds.N ? "true" : "false",
-                 h->sched.grid < t.lnwork ? "true" : "false");
-        return name;
-    }
-    if (t.lat && t.llayers)
-    {
-        static thread_local char name[96];
-        snprintf(name, sizeof name, "k_keff_lattice_layered<1, false, %s, %s>", t.lhex ? "LatHex" : "LatKuhn",
-                 t.lpstride ? "true" : "false");
-        return name;
-    }
-    if (t.lat)  // as rocprofv3 names it, less the namespaces
-    {
-        static thread_local char name[96];
-        snprintf(name, sizeof name, "k_keff_lattice<1, false, %s, %s, %s, %s, %s>", t.lsym ? "true" : "false",
-                 t.lhex ? "LatHex" : "LatKuhn", t.lmu ? "true" : "false", t.lmu && t.lzr ? "true" : "false",
-                 t.lpstride ? "true" : "false");
-        return name;
-    }
-    if (t.grp)  // the PCG-mode instantiation, as rocprofv3 names it (so a profile of another one is not taken)
-    {
-        static thread_local char name[96];
-        snprintf(name, sizeof name, "k_keff_groups_pipe<%s, false, 1, %d, %s>", h->ds.iso ? "true" : "false",
-                 t.pipe_nt, h->ds.M == 1 ? "true" : "false");
-        return name;
-    }
-    return t.hex ? "k_keff_hex_tiles" : t.pipe ? "k_keff_tiles_pipe" : "k_keff_tiles";
+        return resident_kernel_name(h->ds, h->res);
+    if (sch == PcgSchedule::Fused || sch == PcgSchedule::FusedPeer)
+        return pcg_lattice_kernel_name(h->ds, h->sched.grid);
+    return fast_tiles_kernel_name(h->ds);
 }
 
 int cwf_hip_derived_fields(cwf_hip_system *h, const float *u, uint64_t n, int u_kind, float *elements,

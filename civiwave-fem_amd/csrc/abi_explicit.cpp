@@ -96,7 +96,7 @@ int power_iteration(cwf_hip_system *h, uint32_t iterations, double *lambda_max, 
     for (uint32_t it = 0; it < iterations; ++it)
     {
         if (h->mode == CWF_MODE_FAST)
-            fast_keff_ds(s, x, y, true, nullptr, nullptr, st);
+            fast_keff_ds(s, x, y, true, st);
         else
             parity_keff_ds(s, x, y, true, nullptr, st);
         explicit_power_z(s.N, s.mass, s.mask, y, z, st);

@@ -164,6 +164,7 @@ struct LatticeClasses
 LatticeClasses lattice_classes(const Lattice &lat, const uint32_t *bc_mask, const float *lumped_mass);
 
 bool iso_pattern(const double *D);
+bool parity_compact_tiles_wanted(const cwf_hip_system *h);
 int parity_incidence_slots(cwf_hip_system *h);
 int parity_force_buffer(cwf_hip_system *h);
 int check_ready(cwf_hip_system *h);

@@ -126,7 +126,7 @@ int cwf_hip_stepper_step(cwf_hip_stepper *t, double sim_time, int paused, cwf_st
         stiff.sK = 1.0;
         stiff.sM = 0.0;
         if (h->mode == CWF_MODE_FAST)
-            fast_keff_ds(stiff, t->damp, t->kd, true, nullptr, nullptr, s);
+            fast_keff_ds(stiff, t->damp, t->kd, true, s);
         else
             parity_keff_ds(stiff, t->damp, t->kd, true, nullptr, s);
         stepper_rhs_damping(D, t->srhs, t->kd, (float)t->d.rayleigh_beta, s);

@@ -526,6 +526,11 @@ void parity_update(cwf_hip_system *h, const float *rhs, double *prr, double *prz
 // the PCG loop's K_eff p and the chunk partials of p . Ap over the owned nodes (fused for 256-DOF chunks); and
 // parity_update's r . r / r . z partials likewise
 void parity_keff_dot(const cwf_hip_system *h, const float *p, float *Ap, const Ctl *ctl, double *pdot, hipStream_t st);
+// cwf_hip_system_keff_kernel's answers: the PCG loop's instantiation as the family's picker names it (keff_pick.hpp)
+const char *parity_keff_kernel_name(const cwf_hip_system *h, bool compact);
+const char *fast_tiles_kernel_name(const DevSys &s);
+const char *pcg_lattice_kernel_name(const DevSys &s, unsigned grid);
+const char *resident_kernel_name(const DevSys &s, const ResidentPlan &rp);
 void parity_beta(cwf_hip_system *h, const double *p_rr, const double *p_rz, uint32_t count, hipStream_t st);
 void parity_p_update(cwf_hip_system *h, hipStream_t st);
 void parity_pcg_init(cwf_hip_system *h, const float *rhs, double rel_tol, hipStream_t st);
@@ -544,8 +549,7 @@ uint32_t fast_block_count(const cwf_hip_system *h);
 uint32_t fast_dot_blocks(uint32_t D);
 void fast_keff(const cwf_hip_system *h, const float *x, float *y, bool sanitize, const Ctl *ctl, double *part,
                hipStream_t st);
-void fast_keff_ds(const DevSys &s, const float *x, float *y, bool sanitize, const Ctl *ctl, double *part,
-                  hipStream_t st);
+void fast_keff_ds(const DevSys &s, const float *x, float *y, bool sanitize, hipStream_t st);
 // fast_keff_ds without its finalize pass: the launch that leaves every node's partials in s.t.part (a structured
 // block: its row value). The consumer folds them in k_keff_finalize's order (explicit.hip)
 void fast_keff_partials_ds(const DevSys &s, const float *x, bool sanitize, hipStream_t st);

@@ -447,48 +447,19 @@ __global__ __launch_bounds__(NT) void k_keff_hex_tiles(DevSys s, const float *__
 
 inline size_t hex_lds(int nt) { return sizeof(float) * 3 * 8 * nt + 2 * (size_t)nt * (16 + 8); }
 
-template <bool ISO, int NT>
-unsigned hex_grid_query_nt(const DevSys &s)
+template <bool ISO, bool SAN, int MODE, int NT, bool AFF> Pick<HdrTileFn> hex_pick()
 {
-    int dev = 0, bpc = 0, cus = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (s.t.hex_all_affine)
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, k_keff_hex_tiles<ISO, false, 1, NT, true>, NT,
-                                                           hex_lds(NT));
-    else
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, k_keff_hex_tiles<ISO, false, 1, NT, false>, NT,
-                                                           hex_lds(NT));
-    unsigned g = (unsigned)((bpc > 0 ? bpc : 1) * (cus > 0 ? cus : 1));
-    g = g < 8u ? 8u : g - g % 8u;  // whole XCD groups
-    const unsigned need = ((s.t.ntiles + 7u) / 8u) * 8u;
-    return g < need ? g : (need ? need : 8u);
+    static const std::string name = kernel_name("k_keff_hex_tiles", ISO, SAN, MODE, NT, AFF);
+    return {k_keff_hex_tiles<ISO, SAN, MODE, NT, AFF>, name.c_str()};
 }
 
-template <bool ISO>
-unsigned hex_grid_query(const DevSys &s)
+HdrTilePick pick_hex(const DevSys &s, bool pcg, bool sanitize)
 {
-    return s.t.hex_nt == 256 ? hex_grid_query_nt<ISO, 256>(s) : hex_grid_query_nt<ISO, 128>(s);
-}
-
-template <bool ISO, bool SAN, int MODE, bool AFF, int NT>
-void launch_hex_v(const DevSys &s, const float *x, const PcgArgs &pa, hipStream_t st, hipEvent_t e0, hipEvent_t e1)
-{
-    const size_t lds = hex_lds(NT);
-    if (e0 && e1)
-        hipExtLaunchKernelGGL(k_keff_hex_tiles<ISO, SAN, MODE, NT, AFF>, dim3(s.t.pipe_grid), dim3(NT),
-                              (uint32_t)lds, st, e0, e1, 0, s, x, pa, s.t.hdr);
-    else
-        k_keff_hex_tiles<ISO, SAN, MODE, NT, AFF><<<s.t.pipe_grid, NT, lds, st>>>(s, x, pa, s.t.hdr);
-}
-
-template <bool ISO, bool SAN, int MODE>
-void launch_hex(const DevSys &s, const float *x, const PcgArgs &pa, hipStream_t st, hipEvent_t e0, hipEvent_t e1)
-{
-    if (s.t.hex_nt == 256)
-        s.t.hex_all_affine ? launch_hex_v<ISO, SAN, MODE, true, 256>(s, x, pa, st, e0, e1)
-                           : launch_hex_v<ISO, SAN, MODE, false, 256>(s, x, pa, st, e0, e1);
-    else
-        s.t.hex_all_affine ? launch_hex_v<ISO, SAN, MODE, true, 128>(s, x, pa, st, e0, e1)
-                           : launch_hex_v<ISO, SAN, MODE, false, 128>(s, x, pa, st, e0, e1);
+    const int nt = s.t.hex_nt == 256 ? 256 : 128;
+    return {with_bools(
+                [](auto iso, auto pc, auto san, auto wide, auto aff) {
+                    return hex_pick<iso(), !pc() && san(), pc() ? 1 : 0, wide() ? 256 : 128, aff()>();
+                },
+                s.iso != 0, pcg, sanitize, nt == 256, s.t.hex_all_affine != 0),
+            nt, hex_lds(nt)};
 }

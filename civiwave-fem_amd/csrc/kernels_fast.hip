@@ -132,7 +132,7 @@ uint32_t fast_block_count(const cwf_hip_system *h) { return grid_for(h->ds.N, kB
 void fast_keff(const cwf_hip_system *h, const float *x, float *y, bool sanitize, const Ctl *ctl, double *part,
                hipStream_t st)
 {
-    fast_keff_ds(h->ds, x, y, sanitize, ctl, part, st);
+    fast_keff_ds(h->ds, x, y, sanitize, st);
 }
 
 // dot over D dofs: one partial per 256-dof block (grid = ceil(D/256) capped) then fold

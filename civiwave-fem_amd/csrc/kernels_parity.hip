@@ -9,6 +9,7 @@
 //    round-to-nearest sum that starts at +0.0 is never -0.0, so adding a +-0 term is a no-op;
 //  * this TU is compiled with -ffp-contract=off (no FMA contraction), IEEE fp64 div/sqrt.
 #include "cwf_internal.hpp"
+#include "keff_pick.hpp"
 #include "knobs.hpp"
 
 #include <algorithm>
@@ -1360,42 +1361,59 @@ uint32_t parity_chunk_count(const cwf_hip_system *h)
     return (uint32_t)((h->ds.D + B - 1) / B);
 }
 
-// the node-tile K_eff (the handle builds its tiles whenever it runs PARITY: abi.cpp parity_force_buffer)
-template <bool SAN, bool DOT>
-void launch_parity_tile(const DevSys &s, const float *x, float *y, const Ctl *ctl, double *pdot, uint32_t nlim,
-                        uint32_t chunks, hipStream_t st)
+namespace
 {
-    const dim3 b(kBlock);
-    if (s.ptile_nodes && !DOT)
-    {
-        const dim3 gn(s.pntile);
-        if (s.iso)
-            k_keff_parity_tile<true, SAN, false, true><<<gn, b, 0, st>>>(s, x, y, ctl, pdot, nlim, chunks);
-        else
-            k_keff_parity_tile<false, SAN, false, true><<<gn, b, 0, st>>>(s, x, y, ctl, pdot, nlim, chunks);
-        return;
-    }
-    const dim3 gn(grid_for(s.N, kBlock));
-    if (s.iso)
-        k_keff_parity_tile<true, SAN, DOT, false><<<gn, b, 0, st>>>(s, x, y, ctl, pdot, nlim, chunks);
-    else
-        k_keff_parity_tile<false, SAN, DOT, false><<<gn, b, 0, st>>>(s, x, y, ctl, pdot, nlim, chunks);
+using ParityTileFn = void (*)(DevSys, const float *, float *, const Ctl *, double *, uint32_t, uint32_t);
+
+template <bool ISO, bool SAN, bool DOT, bool SET> Pick<ParityTileFn> parity_tile_pick()
+{
+    static const std::string name = kernel_name("k_keff_parity_tile", ISO, SAN, DOT, SET);
+    return {k_keff_parity_tile<ISO, SAN, DOT, SET>, name.c_str()};
+}
+
+// dot: the PCG loop's fused p . Ap chunk partials, which need strip tiles (SET: compact tiles) and never sanitise
+Pick<ParityTileFn> pick_parity_tile(const DevSys &s, bool sanitize, bool dot, bool compact)
+{
+    // (plain = !dot first, then the bools in this order: the code object keeps the kernels in the order it always had them)
+    return with_bools(
+        [](auto plain, auto san, auto set, auto iso) {
+            return parity_tile_pick<iso(), plain() && san(), !plain(), plain() && set()>();
+        },
+        !dot, sanitize, compact, s.iso != 0);
+}
+
+// the PCG loop fuses the partials into the node fold when the reduction chunk is 256 DOFs (every workgroup then owns
+// three whole chunks) and the tiles are strips
+inline bool parity_fused_dot(const cwf_hip_system *h, bool compact) { return h->reduction_block == 256 && !compact; }
+
+// the node-tile K_eff (the handle builds its tiles whenever it runs PARITY: abi.cpp parity_force_buffer)
+void launch_parity_tile(const DevSys &s, const float *x, float *y, bool sanitize, bool dot, const Ctl *ctl, double *pdot,
+                        uint32_t nlim, uint32_t chunks, hipStream_t st)
+{
+    const bool compact = s.ptile_nodes && !dot;
+    launch_kernel(pick_parity_tile(s, sanitize, dot, compact).fn, compact ? s.pntile : grid_for(s.N, kBlock), kBlock, 0,
+                  st, nullptr, nullptr, s, x, y, ctl, pdot, nlim, chunks);
+}
+}  // namespace
+
+// compact: the handle's tiles are, or will be, the compact ones (abi.cpp parity_compact_tiles_wanted)
+const char *parity_keff_kernel_name(const cwf_hip_system *h, bool compact)
+{
+    return pick_parity_tile(h->ds, false, parity_fused_dot(h, compact), compact).name;
 }
 
 void parity_keff_ds(const DevSys &s, const float *x, float *y, bool sanitize, const Ctl *ctl, hipStream_t st)
 {
     if (s.N == 0)
         return;
-    sanitize ? launch_parity_tile<true, false>(s, x, y, ctl, nullptr, 0u, 0u, st)
-             : launch_parity_tile<false, false>(s, x, y, ctl, nullptr, 0u, 0u, st);
+    launch_parity_tile(s, x, y, sanitize, false, ctl, nullptr, 0u, 0u, st);
 }
 
-// the PCG loop's K_eff p with the chunk partials of p . Ap over nodes [0, Nown) into pdot: fused into the node fold
-// when the reduction chunk is 256 DOFs (every workgroup then owns three whole chunks), a separate pass otherwise
+// the PCG loop's K_eff p with the chunk partials of p . Ap over nodes [0, Nown) into pdot: fused, or a separate pass
 void parity_keff_dot(const cwf_hip_system *h, const float *p, float *Ap, const Ctl *ctl, double *pdot, hipStream_t st)
 {
     const DevSys &s = h->ds;
-    if (h->reduction_block != 256 || s.ptile_nodes)  // compact tiles: the partials in their own pass
+    if (!parity_fused_dot(h, s.ptile_nodes != nullptr))
     {
         parity_keff_ds(s, p, Ap, false, ctl, st);
         parity_dot_partials_n(3u * s.Nown, (uint32_t)h->reduction_block, p, Ap, nullptr, pdot, nullptr, ctl, st);
@@ -1403,7 +1421,7 @@ void parity_keff_dot(const cwf_hip_system *h, const float *p, float *Ap, const C
     }
     if (s.N == 0)
         return;
-    launch_parity_tile<false, true>(s, p, Ap, ctl, pdot, s.Nown, grid_for(3u * s.Nown, 256u), st);
+    launch_parity_tile(s, p, Ap, false, true, ctl, pdot, s.Nown, grid_for(3u * s.Nown, 256u), st);
 }
 
 void parity_keff(const cwf_hip_system *h, const float *x, float *y, bool sanitize, const Ctl *ctl, hipStream_t st)

@@ -303,56 +303,40 @@ __global__ __launch_bounds__(kLatNT) void k_keff_lattice_layered(DevSys s, const
 #include "lattice_body.inc"
 }
 
-template <int MODE, bool SAN, class E>
-void launch_lattice_layered(const DevSys &s, const float *x, const PcgArgs &pa, hipStream_t st, hipEvent_t e0,
-                            hipEvent_t e1)
+using LatticeFn = void (*)(DevSys, const float *, PcgArgs, const float *, const uint32_t *);
+using LayeredFn = void (*)(DevSys, const float *, PcgArgs, const float *, const uint32_t *, const uint32_t *);
+
+template <int MODE, bool SAN, bool SYM, class E, bool MU, bool ZR, bool AFF>
+Pick<LatticeFn> lattice_pick()
 {
-    constexpr bool kAff = MODE == 1;  // as launch_lattice_k
-    const auto k = kAff && s.t.lpstride ? k_keff_lattice_layered<MODE, SAN, E, kAff>
-                                        : k_keff_lattice_layered<MODE, SAN, E, false>;
-    if (e0 && e1)
-        hipExtLaunchKernelGGL(k, dim3(s.t.lnwork), dim3(kLatNT), 0, st, e0, e1, 0, s, x, pa, s.t.lcoef, s.t.lplane,
-                              lattice_layers(s.t));
-    else
-        k<<<s.t.lnwork, kLatNT, 0, st>>>(s, x, pa, s.t.lcoef, s.t.lplane, lattice_layers(s.t));
+    static const std::string name = kernel_name("k_keff_lattice", MODE, SAN, SYM, lat_kind<E>(), MU, ZR, AFF);
+    return {k_keff_lattice<MODE, SAN, SYM, E, MU, ZR, AFF>, name.c_str()};
 }
 
-template <int MODE, bool SAN, class E, bool MU, bool ZR>
-void launch_lattice_k(const DevSys &s, const float *x, const PcgArgs &pa, hipStream_t st, hipEvent_t e0, hipEvent_t e1)
+// The PCG loop (pcg) takes z from r when lzr (then pa.z is r) and the strict interior's one mass when lmu; the apply
+// path keeps the per-node mass and reads x. The affine instantiations only for the PCG loop (apply_keff is not a hot
+// path); only the apply path sanitises
+Pick<LatticeFn> pick_lattice(const DevSys &s, bool pcg, bool sanitize)
 {
-    // the affine instantiations only for the PCG loop (apply_keff is not a hot path)
-    constexpr bool kAff = MODE == 1;
-    const auto k = s.t.lsym ? (kAff && s.t.lpstride ? k_keff_lattice<MODE, SAN, true, E, MU, ZR, kAff>
-                                                    : k_keff_lattice<MODE, SAN, true, E, MU, ZR, false>)
-                            : (kAff && s.t.lpstride ? k_keff_lattice<MODE, SAN, false, E, MU, ZR, kAff>
-                                                    : k_keff_lattice<MODE, SAN, false, E, MU, ZR, false>);
-    if (e0 && e1)
-        hipExtLaunchKernelGGL(k, dim3(s.t.lnwork), dim3(kLatNT), 0, st, e0, e1, 0, s, x, pa, s.t.lcoef, s.t.lplane);
-    else
-        k<<<s.t.lnwork, kLatNT, 0, st>>>(s, x, pa, s.t.lcoef, s.t.lplane);
+    return with_bools(
+        [](auto pc, auto san, auto sym, auto hex, auto mu, auto zr, auto aff) {
+            return lattice_pick<pc() ? 1 : 0, !pc() && san(), sym(), LatE<hex()>, pc() && mu(), pc() && mu() && zr(),
+                                pc() && aff()>();
+        },
+        pcg, sanitize, s.t.lsym != 0, s.t.lhex != 0, s.t.lmu != 0, s.t.lzr != 0, s.t.lpstride != 0);
 }
 
-// the apply path (MODE 0) keeps the per-node mass and reads x; the PCG loop takes z from r when lzr (then pa.z is r)
-template <int MODE, bool SAN, class E>
-void launch_lattice_e(const DevSys &s, const float *x, const PcgArgs &pa, hipStream_t st, hipEvent_t e0, hipEvent_t e1)
+template <int MODE, bool SAN, class E, bool AFF> Pick<LayeredFn> layered_pick()
 {
-    if (MODE == 1 && s.t.lmu && s.t.lzr)
-        launch_lattice_k<MODE, SAN, E, MODE == 1, MODE == 1>(s, x, pa, st, e0, e1);
-    else if (MODE == 1 && s.t.lmu)
-        launch_lattice_k<MODE, SAN, E, MODE == 1, false>(s, x, pa, st, e0, e1);
-    else
-        launch_lattice_k<MODE, SAN, E, false, false>(s, x, pa, st, e0, e1);
+    static const std::string name = kernel_name("k_keff_lattice_layered", MODE, SAN, lat_kind<E>(), AFF);
+    return {k_keff_lattice_layered<MODE, SAN, E, AFF>, name.c_str()};
 }
 
-template <int MODE, bool SAN>
-void launch_lattice(const DevSys &s, const float *x, const PcgArgs &pa, hipStream_t st, hipEvent_t e0, hipEvent_t e1)
+Pick<LayeredFn> pick_lattice_layered(const DevSys &s, bool pcg, bool sanitize)
 {
-    if (s.t.llayers && s.t.lhex)
-        launch_lattice_layered<MODE, SAN, LatHex>(s, x, pa, st, e0, e1);
-    else if (s.t.llayers)
-        launch_lattice_layered<MODE, SAN, LatKuhn>(s, x, pa, st, e0, e1);
-    else if (s.t.lhex)
-        launch_lattice_e<MODE, SAN, LatHex>(s, x, pa, st, e0, e1);
-    else
-        launch_lattice_e<MODE, SAN, LatKuhn>(s, x, pa, st, e0, e1);
+    return with_bools(
+        [](auto pc, auto san, auto hex, auto aff) {
+            return layered_pick<pc() ? 1 : 0, !pc() && san(), LatE<hex()>, pc() && aff()>();
+        },
+        pcg, sanitize, s.t.lhex != 0, s.t.lpstride != 0);
 }

@@ -1,14 +1,16 @@
 // lattice_common.hpp -- what the structured-block kernels share across translation units (spmv_tiles.hip: the
 // K_eff / fused-iteration kernels; resident.hip: the resident solve): vector types, the control-block reads, the
 // lattice element kinds and their class-table preconditioner, and the fused iteration's per-node arithmetic and
-// scalar decision. Device code only, in an anonymous namespace per including unit.
+// scalar decision. Device code (and the names a picker needs of it), in an anonymous namespace per including unit.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
+#include <type_traits>
 
 #include "cwf_internal.hpp"
+#include "keff_pick.hpp"
 #include "reduce.hpp"
 
 namespace cwf
@@ -72,6 +74,9 @@ struct LatHex
     static constexpr const int (&pairOff)[kLatHexPairs] = kLatHexPairOff;
     static constexpr int pairStart[9] = {0, 8, 16, 24, 32, 40, 48, 56, 64};
 };
+// the element kind of a picker's bool, and as a kernel's name spells it (keff_pick.hpp)
+template <bool HEX> using LatE = std::conditional_t<HEX, LatHex, LatKuhn>;
+template <class E> constexpr const char *lat_kind() { return std::is_same_v<E, LatHex> ? "LatHex" : "LatKuhn"; }
 constexpr uint32_t kLatOob3 = 0x15555555u;  // 12 * kLatOob3 = 0xFFFFFFFC: past any 12-B-per-node buffer
 constexpr uint32_t kLatOob1 = 0x3FFFFFFFu;  // 4 * kLatOob1: past any 4-B-per-node buffer
 

@@ -808,79 +808,47 @@ __global__ __launch_bounds__(256) void k_fused_finish(const Ctl *__restrict__ ct
         r0[d] = r1[d];
 }
 
-template <bool SYM, class E, bool MU>
-void launch_pcg_lattice_e(const DevSys &s, const FusedArgs &fa, hipStream_t st, hipEvent_t e0, hipEvent_t e1)
+using FusedFn = void (*)(DevSys, FusedArgs, const float *, const uint32_t *);
+
+template <bool SYM, class E, bool MU, bool AFF, bool SHARD, bool PERSIST> Pick<FusedFn> pcg_lattice_pick()
 {
-    // a shard (the plane table, never affine): ghost planes store their r_j / p_j; a grid below the work items
-    // walks them persistently
-    const bool per = fa.grid < s.t.lnwork;
-    const auto k = s.t.lpstride ? (per ? k_pcg_lattice<SYM, E, MU, true, false, true>
-                                       : k_pcg_lattice<SYM, E, MU, true, false, false>)
-                                : (s.Nown < s.N ? (per ? k_pcg_lattice<SYM, E, MU, false, true, true>
-                                                       : k_pcg_lattice<SYM, E, MU, false, true, false>)
-                                                : (per ? k_pcg_lattice<SYM, E, MU, false, false, true>
-                                                       : k_pcg_lattice<SYM, E, MU, false, false, false>));
-    const unsigned g = fa.grid;
-    if (e0 && e1)
-        hipExtLaunchKernelGGL(k, dim3(g), dim3(kLatNT), 0, st, e0, e1, 0, s, fa, s.t.lcoef, s.t.lplane);
-    else
-        k<<<g, kLatNT, 0, st>>>(s, fa, s.t.lcoef, s.t.lplane);
+    static const std::string name = kernel_name("k_pcg_lattice", SYM, lat_kind<E>(), MU, AFF, SHARD, PERSIST);
+    return {k_pcg_lattice<SYM, E, MU, AFF, SHARD, PERSIST>, name.c_str()};
+}
+
+// a shard (the plane table, never affine): ghost planes store their r_j / p_j; persist (a grid below the work items)
+// walks them persistently
+Pick<FusedFn> pick_pcg_lattice(const DevSys &s, bool persist)
+{
+    return with_bools(
+        [](auto sym, auto hex, auto mu, auto aff, auto shard, auto per) {
+            return pcg_lattice_pick<sym(), LatE<hex()>, mu(), aff(), !aff() && shard(), per()>();
+        },
+        s.t.lsym != 0, s.t.lhex != 0, s.t.lmu != 0, s.t.lpstride != 0, s.Nown < s.N, persist);
+}
+
+// resident workgroups of the one-item instantiation (168-170 VGPRs: 3 per CU) or of the persistent one (234-248
+// VGPRs: 2 per CU)
+unsigned lattice_resident_count(const DevSys &s, bool persist = false)
+{
+    return resident_blocks(pick_pcg_lattice(s, persist).fn, kLatNT, 0);
 }
 
 // the fused launch's grid: every work item when they fit in one round of resident workgroups of the one-item
-// instantiation (168-170 VGPRs: 3 per CU), else one round of the persistent one (234-248 VGPRs: 2 per CU; a
-// multiple of 8, so an item keeps its XCD) walking the items; at most `cap`
-template <bool SYM, class E, bool MU, bool PERSIST>
-unsigned pcg_lattice_resident(const DevSys &s)
-{
-    int dev = 0, bpc = 0, cus = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    const auto k = s.t.lpstride ? k_pcg_lattice<SYM, E, MU, true, false, PERSIST>
-                                : (s.Nown < s.N ? k_pcg_lattice<SYM, E, MU, false, true, PERSIST>
-                                                : k_pcg_lattice<SYM, E, MU, false, false, PERSIST>);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, k, kLatNT, 0);
-    return (unsigned)((bpc > 0 ? bpc : 1) * (cus > 0 ? cus : 1));
-}
-
-template <bool PERSIST>
-unsigned lattice_resident_count_p(const DevSys &s)
-{
-    const bool mu = s.t.lmu != 0;
-    return s.t.lhex ? (s.t.lsym ? (mu ? pcg_lattice_resident<true, LatHex, true, PERSIST>(s)
-                                      : pcg_lattice_resident<true, LatHex, false, PERSIST>(s))
-                                : (mu ? pcg_lattice_resident<false, LatHex, true, PERSIST>(s)
-                                      : pcg_lattice_resident<false, LatHex, false, PERSIST>(s)))
-                    : (s.t.lsym ? (mu ? pcg_lattice_resident<true, LatKuhn, true, PERSIST>(s)
-                                      : pcg_lattice_resident<true, LatKuhn, false, PERSIST>(s))
-                                : (mu ? pcg_lattice_resident<false, LatKuhn, true, PERSIST>(s)
-                                      : pcg_lattice_resident<false, LatKuhn, false, PERSIST>(s)));
-}
-
-// resident workgroups of the launch a grid of every item runs (the one-item instantiation)
-unsigned lattice_resident_count(const DevSys &s) { return lattice_resident_count_p<false>(s); }
-
+// instantiation, else one round of the persistent one (a multiple of 8, so an item keeps its XCD) walking the items;
+// at most `cap`
 unsigned pcg_lattice_grid(const DevSys &s, unsigned cap)
 {
-    if (s.t.lnwork <= std::min(lattice_resident_count_p<false>(s), cap))
+    if (s.t.lnwork <= std::min(lattice_resident_count(s), cap))
         return std::max(s.t.lnwork, 1u);
     // never above the items: a grid past lnwork would decode items that do not exist and store their shares past
     // the W = lnwork columns of fsh (a cap below 8 with fewer than 8 items)
-    const unsigned lim = std::min(lattice_resident_count_p<true>(s), cap);
+    const unsigned lim = std::min(lattice_resident_count(s, true), cap);
     return std::min(std::max(lim - lim % 8u, 8u), std::max(s.t.lnwork, 1u));
 }
 
 void launch_pcg_lattice(const DevSys &s, const FusedArgs &fa, hipStream_t st, hipEvent_t e0, hipEvent_t e1)
 {
-    const bool mu = s.t.lmu != 0;
-    if (s.t.lhex)
-        s.t.lsym ? (mu ? launch_pcg_lattice_e<true, LatHex, true>(s, fa, st, e0, e1)
-                       : launch_pcg_lattice_e<true, LatHex, false>(s, fa, st, e0, e1))
-                 : (mu ? launch_pcg_lattice_e<false, LatHex, true>(s, fa, st, e0, e1)
-                       : launch_pcg_lattice_e<false, LatHex, false>(s, fa, st, e0, e1));
-    else
-        s.t.lsym ? (mu ? launch_pcg_lattice_e<true, LatKuhn, true>(s, fa, st, e0, e1)
-                       : launch_pcg_lattice_e<true, LatKuhn, false>(s, fa, st, e0, e1))
-                 : (mu ? launch_pcg_lattice_e<false, LatKuhn, true>(s, fa, st, e0, e1)
-                       : launch_pcg_lattice_e<false, LatKuhn, false>(s, fa, st, e0, e1));
+    launch_kernel(pick_pcg_lattice(s, fa.grid < s.t.lnwork).fn, fa.grid, kLatNT, 0, st, e0, e1, s, fa, s.t.lcoef,
+                  s.t.lplane);
 }

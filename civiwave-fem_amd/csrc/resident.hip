@@ -596,48 +596,43 @@ __global__ __launch_bounds__(kResNT) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     }
 }
 
-template <bool SYM, class E, int NPT, int NPH, bool MR>
-void launch_resident_e(const DevSys &s, const ResArgs &ra, unsigned G, size_t lds, hipStream_t st, hipEvent_t e0,
-                       hipEvent_t e1)
+using ResidentFn = void (*)(DevSys, ResArgs, const float *);
+
+template <bool SYM, class E, int NPT, int NPH, bool MR> Pick<ResidentFn> resident_pick()
 {
-    const auto k = k_pcg_resident<SYM, E, NPT, NPH, MR>;
-    if (e0 && e1)
-        hipExtLaunchKernelGGL(k, dim3(G), dim3(kResNT), lds, st, e0, e1, 0, s, ra, s.t.lcoef);
-    else
-        k<<<G, kResNT, lds, st>>>(s, ra, s.t.lcoef);
+    static const std::string name = kernel_name("k_pcg_resident", SYM, lat_kind<E>(), NPT, NPH, MR);
+    return {k_pcg_resident<SYM, E, NPT, NPH, MR>, name.c_str()};
 }
 
-template <int NPT, int NPH, bool MR>
-void launch_resident_n(const DevSys &s, const ResArgs &ra, unsigned G, size_t lds, hipStream_t st, hipEvent_t e0,
-                       hipEvent_t e1)
+// the instantiations: <= 3 own + 2 halo entries per thread, state in registers (small: boxes of <= 1,536 nodes and
+// <= 1,024 ring entries: C2's 14 x 10 x 10), or <= 4 + 3 with the state in LDS (<= 2,048 nodes, <= 1,536 entries: the
+// C3 / 8 slab's 19 x 19 x 5); 2 waves per SIMD, one workgroup per CU, no scratch
+Pick<ResidentFn> pick_resident(const DevSys &s, bool small, bool shard)
 {
-    if (s.t.lhex)
-        s.t.lsym ? launch_resident_e<true, LatHex, NPT, NPH, MR>(s, ra, G, lds, st, e0, e1)
-                 : launch_resident_e<false, LatHex, NPT, NPH, MR>(s, ra, G, lds, st, e0, e1);
-    else
-        s.t.lsym ? launch_resident_e<true, LatKuhn, NPT, NPH, MR>(s, ra, G, lds, st, e0, e1)
-                 : launch_resident_e<false, LatKuhn, NPT, NPH, MR>(s, ra, G, lds, st, e0, e1);
+    // (the bools in this order: the code object keeps the kernels in the order it always had them)
+    return with_bools(
+        [](auto sm, auto mr, auto hex, auto sym) {
+            return resident_pick<sym(), LatE<hex()>, sm() ? 3 : 4, sm() ? 2 : 3, mr()>();
+        },
+        small, shard, s.t.lhex != 0, s.t.lsym != 0);
 }
+inline bool resident_small(unsigned npt, unsigned nph) { return npt <= 3 && nph <= 2; }
+}  // namespace
 
-template <int NPT, int NPH, bool MR>
-size_t res_static_lds(const DevSys &s)
+// ---- the resident solve (the kernel above): one launch per PCG solve ------------------------------------------------
+size_t resident_static_lds(const DevSys &s, bool small, bool shard)
 {
-    const auto k = s.t.lhex ? (s.t.lsym ? k_pcg_resident<true, LatHex, NPT, NPH, MR>
-                                        : k_pcg_resident<false, LatHex, NPT, NPH, MR>)
-                            : (s.t.lsym ? k_pcg_resident<true, LatKuhn, NPT, NPH, MR>
-                                        : k_pcg_resident<false, LatKuhn, NPT, NPH, MR>);
     hipFuncAttributes a{};
-    return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(k)) == hipSuccess ? a.sharedSizeBytes : 0;
+    const void *k = reinterpret_cast<const void *>(pick_resident(s, small, shard).fn);
+    return hipFuncGetAttributes(&a, k) == hipSuccess ? a.sharedSizeBytes : 0;
 }
 
-template <int NPT, int NPH, bool MR>
-int res_bpc(const DevSys &s, size_t lds)
+int resident_blocks_per_cu(const DevSys &s, unsigned npt, unsigned nph, size_t lds, bool shard)
 {
+    if (npt > 4 || nph > 3)
+        return 0;
     int bpc = 0;
-    const auto k = s.t.lhex ? (s.t.lsym ? k_pcg_resident<true, LatHex, NPT, NPH, MR>
-                                        : k_pcg_resident<false, LatHex, NPT, NPH, MR>)
-                            : (s.t.lsym ? k_pcg_resident<true, LatKuhn, NPT, NPH, MR>
-                                        : k_pcg_resident<false, LatKuhn, NPT, NPH, MR>);
+    const ResidentFn k = pick_resident(s, resident_small(npt, nph), shard).fn;
     // the image is dynamic LDS beside ~100 KB of static arrays: allow the workgroup its size (gfx950: 160 KB)
     if (hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
             hipSuccess ||
@@ -645,26 +640,10 @@ int res_bpc(const DevSys &s, size_t lds)
         return 0;
     return bpc;
 }
-}  // namespace
 
-// ---- the resident solve (the kernel above): one launch per PCG solve ------------------------------------------------
-// the instantiations: <= 3 own + 2 halo entries per thread, state in registers (boxes of <= 1,536 nodes and <= 1,024
-// ring entries: C2's 14 x 10 x 10), or <= 4 + 3 with the state in LDS (<= 2,048 nodes, <= 1,536 entries: the C3 / 8
-// slab's 19 x 19 x 5); 2 waves per SIMD, one workgroup per CU, no scratch
-size_t resident_static_lds(const DevSys &s, bool small, bool shard)
+const char *resident_kernel_name(const DevSys &s, const ResidentPlan &rp)
 {
-    if (small)
-        return shard ? res_static_lds<3, 2, true>(s) : res_static_lds<3, 2, false>(s);
-    return shard ? res_static_lds<4, 3, true>(s) : res_static_lds<4, 3, false>(s);
-}
-
-int resident_blocks_per_cu(const DevSys &s, unsigned npt, unsigned nph, size_t lds, bool shard)
-{
-    if (npt <= 3 && nph <= 2)
-        return shard ? res_bpc<3, 2, true>(s, lds) : res_bpc<3, 2, false>(s, lds);
-    if (npt <= 4 && nph <= 3)
-        return shard ? res_bpc<4, 3, true>(s, lds) : res_bpc<4, 3, false>(s, lds);
-    return 0;
+    return pick_resident(s, resident_small(rp.npt, rp.nph), rp.shard).name;
 }
 
 void launch_pcg_resident(cwf_hip_system *h, uint32_t max_it, hipStream_t st, hipEvent_t e0, hipEvent_t e1)
@@ -709,12 +688,8 @@ void launch_pcg_resident(cwf_hip_system *h, uint32_t max_it, hipStream_t st, hip
     }
     const char *rk = knob("CWF_RESIDENT_REREAD");  // tests/test_gpu_resident_handoff.py
     ra.reread = rk && rk[0] == '1' ? 1u : 0u;
-    if (rp.npt <= 3 && rp.nph <= 2)
-        rp.shard ? launch_resident_n<3, 2, true>(h->ds, ra, rp.G, rp.lds, st, e0, e1)
-                 : launch_resident_n<3, 2, false>(h->ds, ra, rp.G, rp.lds, st, e0, e1);
-    else
-        rp.shard ? launch_resident_n<4, 3, true>(h->ds, ra, rp.G, rp.lds, st, e0, e1)
-                 : launch_resident_n<4, 3, false>(h->ds, ra, rp.G, rp.lds, st, e0, e1);
+    launch_kernel(pick_resident(h->ds, resident_small(rp.npt, rp.nph), rp.shard).fn, rp.G, kResNT, rp.lds, st, e0, e1,
+                  h->ds, ra, h->ds.t.lcoef);
     if (tp && trace)
     {
         std::vector<uint64_t> v(8ull * rp.G);

@@ -1687,14 +1687,30 @@ inline size_t tiles_lds(const DevSys &s)
     return sizeof(float) * (14 * kTileElems + (s.t.geo ? 6 : 3) * (size_t)s.t.max_tile_nodes);
 }
 
-template <bool ISO, bool SAN, int MODE, bool GEO>
-void launch_tiles_g(const DevSys &s, const float *x, const PcgArgs &pa, int nt, hipStream_t st)
+using TileFn = void (*)(DevSys, const float *, PcgArgs);
+// the persistent tile kernels (fan groups, hex tiles, pipelined per-tet tiles) share a signature, the tile headers as
+// their last argument, and the grid t.pipe_grid; a pick of one comes with its block size and LDS bytes
+using HdrTileFn = void (*)(DevSys, const float *, PcgArgs, const uint4 *);
+struct HdrTilePick
 {
-    const size_t lds = tiles_lds(s);
-    if (nt == 512)
-        k_keff_tiles<ISO, SAN, MODE, 512, GEO><<<s.t.ntiles, 512, lds, st>>>(s, x, pa);
-    else
-        k_keff_tiles<ISO, SAN, MODE, 256, GEO><<<s.t.ntiles, 256, lds, st>>>(s, x, pa);
+    Pick<HdrTileFn> k;
+    int nt;
+    size_t lds;
+};
+
+template <bool ISO, bool SAN, int MODE, bool GEO> Pick<TileFn> tiles_pick()
+{
+    static const std::string name = kernel_name("k_keff_tiles", ISO, SAN, MODE, 256, GEO);
+    return {k_keff_tiles<ISO, SAN, MODE, 256, GEO>, name.c_str()};
+}
+
+// Every FAST element pass has three uses: the PCG loop (pcg: MODE 1, never sanitised) and the apply path (MODE 0)
+// with or without the Dirichlet sanitise. The pickers spell them <!pcg && sanitize, pcg ? 1 : 0>
+Pick<TileFn> pick_tiles(const DevSys &s, bool pcg, bool sanitize)
+{
+    return with_bools(
+        [](auto iso, auto pc, auto san, auto geo) { return tiles_pick<iso(), !pc() && san(), pc() ? 1 : 0, geo()>(); },
+        s.iso != 0, pcg, sanitize, s.t.geo != 0);
 }
 
 #include "hex8_tiles.inc"
@@ -1710,112 +1726,72 @@ inline size_t pipe_lds(const DevSys &s)
     return sizeof(float) * 3 * (4 * te + 2 * (size_t)s.t.pipe_nt) + ms * (16 + 8);
 }
 
-template <bool ISO, int NT>
-unsigned pipe_grid_query(const DevSys &s)
+template <bool ISO, bool SAN, int MODE, int NT> Pick<HdrTileFn> pipe_pick()
 {
-    int dev = 0, bpc = 0, cus = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, k_keff_tiles_pipe<ISO, false, 1, NT>, NT,
-                                                       pipe_lds(s));
-    unsigned g = (unsigned)((bpc > 0 ? bpc : 1) * (cus > 0 ? cus : 1));
-    g = g < 8u ? 8u : g - g % 8u;  // whole XCD groups
-    const unsigned need = ((s.t.ntiles + 7u) / 8u) * 8u;
-    return g < need ? g : (need ? need : 8u);
+    static const std::string name = kernel_name("k_keff_tiles_pipe", ISO, SAN, MODE, NT);
+    return {k_keff_tiles_pipe<ISO, SAN, MODE, NT>, name.c_str()};
 }
 
-template <bool ISO, bool SAN, int MODE, int NT>
-void launch_pipe(const DevSys &s, const float *x, const PcgArgs &pa, hipStream_t st, hipEvent_t e0, hipEvent_t e1)
+HdrTilePick pick_pipe(const DevSys &s, bool pcg, bool sanitize)
 {
-    const size_t lds = pipe_lds(s);
-    if (e0 && e1)
-        hipExtLaunchKernelGGL(k_keff_tiles_pipe<ISO, SAN, MODE, NT>, dim3(s.t.pipe_grid), dim3(NT),
-                              (uint32_t)lds, st, e0, e1, 0, s, x, pa, s.t.hdr);
-    else
-        k_keff_tiles_pipe<ISO, SAN, MODE, NT><<<s.t.pipe_grid, NT, lds, st>>>(s, x, pa, s.t.hdr);
+    const int nt = s.t.pipe_nt == 128 ? 128 : 256;
+    return {with_bools(
+                [](auto iso, auto pc, auto san, auto wide) {
+                    return pipe_pick<iso(), !pc() && san(), pc() ? 1 : 0, wide() ? 256 : 128>();
+                },
+                s.iso != 0, pcg, sanitize, nt == 256),
+            nt, pipe_lds(s)};
 }
 
 // pushed forces {f_x, f_y} + f_z per slot, then per tile node {x y z v_x} {v_y v_z} and its u16 run start
 constexpr size_t group_lds(int nt) { return sizeof(float) * 3 * kGroupSlotsPerLane * nt + 2 * nt * (16 + 8 + 2); }
 
-template <bool ISO, bool MONO, int NT>
-unsigned group_grid_query()
+template <bool ISO, bool SAN, int MODE, int NT, bool MONO> Pick<HdrTileFn> groups_pick()
 {
-    int dev = 0, bpc = 0, cus = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, k_keff_groups_pipe<ISO, false, 1, NT, MONO>, NT,
-                                                       group_lds(NT));
-    unsigned g = (unsigned)((bpc > 0 ? bpc : 1) * (cus > 0 ? cus : 1));
-    return g < 8u ? 8u : g - g % 8u;  // whole XCD groups
+    static const std::string name = kernel_name("k_keff_groups_pipe", ISO, SAN, MODE, NT, MONO);
+    return {k_keff_groups_pipe<ISO, SAN, MODE, NT, MONO>, name.c_str()};
 }
 
-template <bool ISO, bool SAN, int MODE, bool MONO, int NT>
-void launch_groups_m(const DevSys &s, const float *x, const PcgArgs &pa, hipStream_t st, hipEvent_t e0,
-                     hipEvent_t e1)
+HdrTilePick pick_groups(const DevSys &s, bool pcg, bool sanitize)
 {
-    constexpr uint32_t lds = (uint32_t)group_lds(NT);
-    if (e0 && e1)
-        hipExtLaunchKernelGGL(k_keff_groups_pipe<ISO, SAN, MODE, NT, MONO>, dim3(s.t.pipe_grid), dim3(NT), lds, st,
-                              e0, e1, 0, s, x, pa, s.t.hdr);
-    else
-        k_keff_groups_pipe<ISO, SAN, MODE, NT, MONO><<<s.t.pipe_grid, NT, lds, st>>>(s, x, pa, s.t.hdr);
+    const int nt = s.t.pipe_nt == 256 ? 256 : 128;
+    return {with_bools(
+                [](auto iso, auto pc, auto san, auto wide, auto mono) {
+                    return groups_pick<iso(), !pc() && san(), pc() ? 1 : 0, wide() ? 256 : 128, mono()>();
+                },
+                s.iso != 0, pcg, sanitize, nt == 256, s.M == 1),
+            nt, group_lds(nt)};
 }
 
-template <bool ISO, bool SAN, int MODE>
-void launch_groups(const DevSys &s, const float *x, const PcgArgs &pa, hipStream_t st, hipEvent_t e0, hipEvent_t e1)
+// t.grp, t.hex or t.pipe
+HdrTilePick pick_hdr_tiles(const DevSys &s, bool pcg, bool sanitize)
 {
-    if (s.t.pipe_nt == 256)
-        s.M == 1 ? launch_groups_m<ISO, SAN, MODE, true, 256>(s, x, pa, st, e0, e1)
-                 : launch_groups_m<ISO, SAN, MODE, false, 256>(s, x, pa, st, e0, e1);
-    else
-        s.M == 1 ? launch_groups_m<ISO, SAN, MODE, true, 128>(s, x, pa, st, e0, e1)
-                 : launch_groups_m<ISO, SAN, MODE, false, 128>(s, x, pa, st, e0, e1);
+    return s.t.grp ? pick_groups(s, pcg, sanitize) : s.t.hex ? pick_hex(s, pcg, sanitize) : pick_pipe(s, pcg, sanitize);
 }
 
-template <bool ISO, bool MONO>
-unsigned group_grid(int nt)
-{
-    return nt == 256 ? group_grid_query<ISO, MONO, 256>() : group_grid_query<ISO, MONO, 128>();
-}
-
-// e0/e1 (optional): hipExtLaunchKernel stamps them from the dispatch packet itself, so the timed
-// interval is the kernel's own execution (what rocprofv3 --kernel-trace reports), not marker latency
-template <bool ISO, bool SAN, int MODE>
-void launch_tiles(const DevSys &s, const float *x, const PcgArgs &pa, int nt, hipStream_t st,
+// the element pass of a FAST handle with tiles: the PCG loop's (pcg) or the apply path's
+void launch_tiles(const DevSys &s, const float *x, const PcgArgs &pa, bool pcg, bool sanitize, hipStream_t st,
                   hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr)
 {
-    if (s.t.lat)
+    const DevTiles &t = s.t;
+    if (t.lat && t.llayers)
+        launch_kernel(pick_lattice_layered(s, pcg, sanitize).fn, t.lnwork, kLatNT, 0, st, e0, e1, s, x, pa, t.lcoef,
+                      t.lplane, lattice_layers(t));
+    else if (t.lat)
+        launch_kernel(pick_lattice(s, pcg, sanitize).fn, t.lnwork, kLatNT, 0, st, e0, e1, s, x, pa, t.lcoef, t.lplane);
+    else if (t.grp || t.hex || t.pipe)
     {
-        launch_lattice<MODE, SAN>(s, x, pa, st, e0, e1);
-        return;
+        const HdrTilePick p = pick_hdr_tiles(s, pcg, sanitize);
+        launch_kernel(p.k.fn, t.pipe_grid, p.nt, p.lds, st, e0, e1, s, x, pa, t.hdr);
     }
-    if (s.t.grp)
-    {
-        launch_groups<ISO, SAN, MODE>(s, x, pa, st, e0, e1);
-        return;
-    }
-    if (s.t.hex)
-    {
-        launch_hex<ISO, SAN, MODE>(s, x, pa, st, e0, e1);
-        return;
-    }
-    if (s.t.pipe)
-    {
-        if (s.t.pipe_nt == 128)
-            launch_pipe<ISO, SAN, MODE, 128>(s, x, pa, st, e0, e1);
-        else
-            launch_pipe<ISO, SAN, MODE, 256>(s, x, pa, st, e0, e1);
-        return;
-    }
-    if (e0)
-        (void)hipEventRecord(e0, st);
-    if (s.t.geo)
-        launch_tiles_g<ISO, SAN, MODE, true>(s, x, pa, nt, st);
     else
-        launch_tiles_g<ISO, SAN, MODE, false>(s, x, pa, nt, st);
-    if (e1)
-        (void)hipEventRecord(e1, st);
+    {
+        if (e0)
+            (void)hipEventRecord(e0, st);
+        launch_kernel(pick_tiles(s, pcg, sanitize).fn, t.ntiles, 256, tiles_lds(s), st, nullptr, nullptr, s, x, pa);
+        if (e1)
+            (void)hipEventRecord(e1, st);
+    }
 }
 }  // namespace
 
@@ -1826,31 +1802,26 @@ unsigned fast_tile_blocks(const DevSys &s)
 
 unsigned fast_pipe_grid(const DevSys &s)
 {
-    if (s.t.grp)
-    {
-        const int nt = s.t.pipe_nt;
-        const unsigned g = s.iso ? (s.M == 1 ? group_grid<true, true>(nt) : group_grid<true, false>(nt))
-                                 : (s.M == 1 ? group_grid<false, true>(nt) : group_grid<false, false>(nt));
-        const unsigned need = ((s.t.ntiles + 7u) / 8u) * 8u;
-        return g < need ? g : (need ? need : 8u);
-    }
-    if (s.t.hex)
-        return s.iso ? hex_grid_query<true>(s) : hex_grid_query<false>(s);
-    if (s.t.pipe_nt == 128)
-        return s.iso ? pipe_grid_query<true, 128>(s) : pipe_grid_query<false, 128>(s);
-    return s.iso ? pipe_grid_query<true, 256>(s) : pipe_grid_query<false, 256>(s);
+    const HdrTilePick p = pick_hdr_tiles(s, true, false);
+    return xcd_grid(p.k.fn, p.nt, p.lds, s.t.ntiles);
 }
+
+// the PCG loop's instantiation of the two-kernel element pass, by name (cwf_hip_system_keff_kernel)
+const char *fast_tiles_kernel_name(const DevSys &s)
+{
+    const DevTiles &t = s.t;
+    return t.lat && t.llayers         ? pick_lattice_layered(s, true, false).name
+           : t.lat                    ? pick_lattice(s, true, false).name
+           : t.grp || t.hex || t.pipe ? pick_hdr_tiles(s, true, false).k.name
+                                      : pick_tiles(s, true, false).name;
+}
+
 // the update pass is grid-stride: at most one resident wave of workgroups (occupancy x CUs), so no
 // workgroup waits for a slot behind the others' whole node ranges
 template <int U, bool XF>
 unsigned update_resident()
 {
-    int dev = 0, bpc = 0, cus = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, k_pcg_update_tiles<U, XF, false>, kUpdThreads, 0);
-    const unsigned r = (unsigned)((bpc > 0 ? bpc : 1) * (cus > 0 ? cus : 1));
-    return r < kMaxUpdateBlocks ? r : kMaxUpdateBlocks;
+    return std::min(resident_blocks(k_pcg_update_tiles<U, XF, false>, kUpdThreads, 0), kMaxUpdateBlocks);
 }
 
 // flush: the grid of the lazy-x instantiation (its own occupancy); the consumers of the update's r.r / r.z
@@ -1864,26 +1835,11 @@ unsigned fast_update_blocks(const DevSys &s, bool flush)
     return g < res ? (g ? g : 1u) : res;
 }
 
-// workgroup size of the one-tile-per-workgroup per-tet kernel (k_keff_tiles)
-static int tile_threads() { return 256; }
-
-void fast_keff_ds(const DevSys &s, const float *x, float *y, bool sanitize, const Ctl *ctl, double *part,
-                  hipStream_t st)
+void fast_keff_ds(const DevSys &s, const float *x, float *y, bool sanitize, hipStream_t st)
 {
-    (void)ctl;
-    (void)part;
     if (s.N == 0)
         return;
-    if (s.t.ntiles)
-    {
-        PcgArgs none{};
-        const int nt = tile_threads();
-        if (s.iso)
-            sanitize ? launch_tiles<true, true, 0>(s, x, none, nt, st) : launch_tiles<true, false, 0>(s, x, none, nt, st);
-        else
-            sanitize ? launch_tiles<false, true, 0>(s, x, none, nt, st)
-                     : launch_tiles<false, false, 0>(s, x, none, nt, st);
-    }
+    fast_keff_partials_ds(s, x, sanitize, st);
     const unsigned g = grid_for(s.N, 256);
     if (sanitize)
         k_keff_finalize<true><<<g, 256, 0, st>>>(s, x, y);
@@ -1895,12 +1851,7 @@ void fast_keff_partials_ds(const DevSys &s, const float *x, bool sanitize, hipSt
 {
     if (s.N == 0 || !s.t.ntiles)
         return;
-    PcgArgs none{};
-    const int nt = tile_threads();
-    if (s.iso)
-        sanitize ? launch_tiles<true, true, 0>(s, x, none, nt, st) : launch_tiles<true, false, 0>(s, x, none, nt, st);
-    else
-        sanitize ? launch_tiles<false, true, 0>(s, x, none, nt, st) : launch_tiles<false, false, 0>(s, x, none, nt, st);
+    launch_tiles(s, x, PcgArgs{}, false, sanitize, st);
 }
 
 // FAST search directions rotate over four buffers: p_j (iteration j's) lives in {p, p2, p3, p4}[(j + 1) % 4],
@@ -1980,10 +1931,7 @@ void fast_tiles_pcg(cwf_hip_system *h, unsigned it, hipStream_t st, hipEvent_t e
                                fast_p_new(h, it)}
                      : PcgArgs{pz, h->ctl, h->part0, h->g_rrz, h->g_rrz + 1,
                                (unsigned)h->nranks, 2u, it, h->hist, abl, fast_p_new(h, it)};
-    if (s.iso)
-        launch_tiles<true, false, 1>(s, fast_p_old(h, it), pa, tile_threads(), st, e0, e1);
-    else
-        launch_tiles<false, false, 1>(s, fast_p_old(h, it), pa, tile_threads(), st, e0, e1);
+    launch_tiles(s, fast_p_old(h, it), pa, true, false, st, e0, e1);
 }
 
 void fast_update_pcg(cwf_hip_system *h, const float *rhs, unsigned it, hipStream_t st)
@@ -2017,13 +1965,15 @@ void fast_tiles_pcg_dry(cwf_hip_system *h, unsigned abl, int reps, hipStream_t s
     PcgArgs pa{s.t.lzr ? h->r : h->z, h->ctl, h->part0, h->g_rrz, h->g_rrz + 1, (unsigned)h->nranks, 2u, 1u,
                h->hist, abl | 32u};
     for (int i = 0; i < reps; ++i)
-        launch_tiles<true, false, 1>(s, h->p, pa, tile_threads(), st);
+        launch_tiles(s, h->p, pa, true, false, st);
 }
 
 // ---- the fused lattice iteration (lattice_fused.inc) --------------------------------------------------------
 unsigned pcg_lattice_resident_count(const DevSys &s) { return lattice_resident_count(s); }
 
 unsigned pcg_lattice_launch_grid(const DevSys &s, unsigned cap) { return pcg_lattice_grid(s, cap); }
+
+const char *pcg_lattice_kernel_name(const DevSys &s, unsigned grid) { return pick_pcg_lattice(s, grid < s.t.lnwork).name; }
 
 namespace
 {

@@ -109,6 +109,29 @@ def test_create_host_pieces(tmp_path):
     assert out.stdout.strip() == "ok"
 
 
+def test_keff_kernel_names(tmp_path):
+    """tests/cpp/keff_kernel_names_test.cpp: cwf_hip_system_keff_kernel on fabricated handles, one line per combination
+    of the facts the kernel pickers read (keff_pick.hpp), against tests/golden/keff_kernel_names.txt. The golden file is
+    the output of the same program against the library before the pickers, except for the lines whose name that library
+    did not take from the launch: the hex-tile, pipelined per-tet and record kernels (reported bare) and PARITY strips
+    with a reduction block other than 256 (reported with the fused dot the launch does not use). No GPU call."""
+    import subprocess
+    import os
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    libdir = os.path.join(root, "civiwave-fem_amd", "lib")
+    exe = str(tmp_path / "keff_kernel_names_test")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
+                    "-I" + os.path.join(root, "civiwave-fem_amd", "csrc"),
+                    os.path.join(root, "tests", "cpp", "keff_kernel_names_test.cpp"), "-o", exe, f"-L{libdir}",
+                    "-lcwf_hip", f"-Wl,-rpath,{libdir}"], check=True)
+    env = {k: v for k, v in os.environ.items() if not k.startswith("CWF_")}
+    out = subprocess.run([exe], env=env, check=True, capture_output=True, text=True)
+    with open(os.path.join(root, "tests", "golden", "keff_kernel_names.txt")) as f:
+        want = f.read()
+    assert out.stdout.splitlines() == want.splitlines()
+
+
 def test_cpp_mirror_header_compiles_and_links(tmp_path):
     """include/cwf_hip.hpp (C++ mirror of cwf::gpu::pcg / Stepper) builds with the image's g++."""
     assert _build_cpp_test(tmp_path)
