@@ -44,6 +44,8 @@ int hip_fail(cwf_hip_system *h, hipError_t e, const char *what)
 
 }  // namespace cwf
 
+cwf_hip_system::~cwf_hip_system() = default;  // here, not in the header: cwf_internal.hpp
+
 using namespace cwf;
 
 #include "abi_internal.hpp"
@@ -952,10 +954,8 @@ void cwf_hip_system_destroy(cwf_hip_system *h)
         h->comm->members[h->rank] = nullptr;
         h->stream = h->own_stream;
     }
-    for (void *p : h->owned)
-        (void)hipFree(p);
-    if (h->hist)
-        (void)hipFree(h->hist);
+    h->mem.clear();
+    h->hist.reset();
     if (h->ctl_host)
         (void)hipHostFree(h->ctl_host);
     for (hipEvent_t e : h->ev)
@@ -1106,10 +1106,8 @@ int cwf_hip_keff_timed(cwf_hip_system *h, const float *x, float *y, int reps, do
     {
         if (dry && h->mode == CWF_MODE_FAST && h->ds.iso)
             fast_tiles_pcg_dry(h, (unsigned)atoi(dry), 1, h->stream);
-        else if (h->mode == CWF_MODE_FAST)
-            fast_keff(h, x, y, false, nullptr, h->part0, h->stream);
         else
-            parity_keff(h, x, y, false, nullptr, h->stream);
+            keff_apply_ds(h, h->ds, x, y, false, h->stream);
     }
     HIPTRY(h, hipEventRecord(b, h->stream));
     HIPTRY(h, hipEventSynchronize(b));
@@ -1129,10 +1127,10 @@ int cwf_hip_bandwidth_probe(int device, uint64_t bytes, int reps, double *gbs)
     if (e != hipSuccess)
         return hip_fail(nullptr, e, "hipSetDevice");
     bytes &= ~(uint64_t)15;
-    void *a = nullptr, *b = nullptr;
+    DevicePtr<char> a, b;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     float ms = 0.f;
-    if ((e = hipMalloc(&a, bytes)) == hipSuccess && (e = hipMalloc(&b, bytes)) == hipSuccess &&
+    if ((e = a.alloc(bytes)) == hipSuccess && (e = b.alloc(bytes)) == hipSuccess &&
         (e = hipMemset(a, 0, bytes)) == hipSuccess && (e = hipEventCreate(&e0)) == hipSuccess &&
         (e = hipEventCreate(&e1)) == hipSuccess)
     {
@@ -1149,8 +1147,6 @@ int cwf_hip_bandwidth_probe(int device, uint64_t bytes, int reps, double *gbs)
         (void)hipEventDestroy(e0);
     if (e1)
         (void)hipEventDestroy(e1);
-    (void)hipFree(a);
-    (void)hipFree(b);
     if (e != hipSuccess)
         return hip_fail(nullptr, e, "bandwidth probe");
     *gbs = 2.0 * (double)bytes * reps / ((double)ms * 1e-3) / 1e9;  // read + write
@@ -1161,7 +1157,7 @@ int cwf_hip_system_memory(const cwf_hip_system *h, uint64_t *bytes)
 {
     if (!h || !bytes)
         return set_error(nullptr, CWF_ERR_ARGUMENT, "null pointer");
-    *bytes = h->bytes;
+    *bytes = h->mem.total();
     return 0;
 }
 
@@ -1270,9 +1266,10 @@ int cwf_hip_derived_fields(cwf_hip_system *h, const float *u, uint64_t n, int u_
     float *de = elements, *dn = nodes;
     if (out_kind != CWF_PTR_DEVICE || h->perm)  // stage through one scratch allocation
     {
-        float *scratch = nullptr;
-        HIPTRY(h, hipMalloc(reinterpret_cast<void **>(&scratch), (ne + nn + 1) * sizeof(float)));
-        de = elements ? scratch : nullptr;
+        DevicePtr<float> scratch;
+        if (hipError_t e = scratch.alloc(ne + nn + 1); e != hipSuccess)
+            return hip_fail(h, e, "derived fields");
+        de = elements ? scratch.get() : nullptr;
         dn = nodes ? scratch + ne : nullptr;
         derived_fields(h, uin, de, dn, h->stream);
         hipError_t e1 = hipGetLastError();
@@ -1288,7 +1285,6 @@ int cwf_hip_derived_fields(cwf_hip_system *h, const float *u, uint64_t n, int u_
         }
         if (e1 == hipSuccess)
             e1 = hipStreamSynchronize(h->stream);
-        (void)hipFree(scratch);
         if (e1 != hipSuccess)
             return hip_fail(h, e1, "derived fields");
         return 0;

@@ -11,14 +11,13 @@
 
 using namespace cwf;
 
-struct cwf_hip_explicit
+// u, v, f, bcv, the load pattern and the arena: the shared state core (abi_transient.cpp)
+struct cwf_hip_explicit : TransientState
 {
-    cwf_hip_system *sys = nullptr;
     double alpha = 0.0, beta = 0.0, dt = 0.0, lambda_max = 0.0, critical_dt = 0.0;
     uint64_t steps = 0;
     bool input_stale = true;  // beta_R != 0: w has to be formed from u and v before the next step
-    float *u = nullptr, *v = nullptr, *w = nullptr, *y = nullptr, *f = nullptr, *bcv = nullptr;
-    double *lbase = nullptr, *lpat = nullptr;  // set_load_pattern: f64 [3N] each (internal order)
+    float *w = nullptr, *y = nullptr;
     uint32_t *non_finite = nullptr;
     std::vector<double> ctimes, cvalues;  // set_load_curve
     double last_scale = 0.0;              // c(t) of the last step taken (get_state 4 with a pattern)
@@ -27,20 +26,11 @@ struct cwf_hip_explicit
     std::vector<uint32_t> dash_ids;
     std::vector<double> dash_C;
     uint32_t *dslot = nullptr;
-    double *dpq = nullptr;
-    std::vector<void *> owned;
+    DevicePtr<double> dpq;
 };
 
 namespace
 {
-int ex_alloc(cwf_hip_explicit *t, void **p, size_t bytes)
-{
-    if (hipMalloc(p, std::max<size_t>(bytes, 16)) != hipSuccess)
-        return set_error(t->sys, CWF_ERR_ALLOC, "failed to allocate explicit stepper buffers");
-    t->owned.push_back(*p);
-    return 0;
-}
-
 std::string num(double v)
 {
     char b[40];
@@ -57,15 +47,6 @@ double lerp_ref(double a, double b, double t)
         return b;
     const double x = a + t * (b - a);
     return ((t > 1) == (b > a)) ? (b < x ? x : b) : (b > x ? x : b);
-}
-
-// the handle's operator at scalars (1, 0), the handle itself untouched (abi_stepper.cpp's stiffness-only system)
-DevSys stiffness_only(const cwf_hip_system *h)
-{
-    DevSys s = h->ds;
-    s.sK = 1.0;
-    s.sM = 0.0;
-    return s;
 }
 
 int refuse_unfit(cwf_hip_system *h)
@@ -85,20 +66,18 @@ int power_iteration(cwf_hip_system *h, uint32_t iterations, double *lambda_max, 
 {
     const DevSys s = stiffness_only(h);
     hipStream_t st = h->stream;
-    const size_t bytes = std::max<size_t>((size_t)s.D, 4) * sizeof(float);
-    void *buf = nullptr;
-    if (hipMalloc(&buf, 3 * bytes) != hipSuccess)
-        return set_error(h, CWF_ERR_ALLOC, "failed to allocate device buffer", "bytes=" + std::to_string(3 * bytes));
-    float *x = static_cast<float *>(buf), *y = x + bytes / sizeof(float), *z = y + bytes / sizeof(float);
+    const size_t len = std::max<size_t>((size_t)s.D, 4);
+    DevicePtr<float> buf;
+    if (buf.alloc(3 * len) != hipSuccess)
+        return set_error(h, CWF_ERR_ALLOC, "failed to allocate device buffer",
+                         "bytes=" + std::to_string(3 * len * sizeof(float)));
+    float *x = buf, *y = x + len, *z = y + len;
     const uint32_t nb = fast_dot_blocks(s.D);
     (void)hipMemsetAsync(h->scal, 0, 4 * sizeof(double), st);
     explicit_power_start(s.N, s.mask, x, st);
     for (uint32_t it = 0; it < iterations; ++it)
     {
-        if (h->mode == CWF_MODE_FAST)
-            fast_keff_ds(s, x, y, true, st);
-        else
-            parity_keff_ds(s, x, y, true, nullptr, st);
+        keff_apply_ds(h, s, x, y, true, st);
         explicit_power_z(s.N, s.mass, s.mask, y, z, st);
         fast_dot(y, z, x, s.D, h->part0, h->part1, st);
         fast_fold(h->part0, nb, h->scal + 0, st);
@@ -111,7 +90,6 @@ int power_iteration(cwf_hip_system *h, uint32_t iterations, double *lambda_max, 
         e = hipMemcpyAsync(lam, h->scal + 2, sizeof lam, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess)
         e = hipStreamSynchronize(st);
-    (void)hipFree(buf);
     if (e != hipSuccess)
         return hip_fail(h, e, "power iteration");
     const double last = lam[(iterations - 1) & 1u], prev = lam[iterations & 1u];
@@ -186,11 +164,7 @@ void cwf_hip_explicit_destroy(cwf_hip_explicit *t)
 {
     if (!t)
         return;
-    (void)hipSetDevice(t->sys->device);
-    (void)hipStreamSynchronize(t->sys->stream);
-    for (void *p : t->owned)
-        (void)hipFree(p);
-    (void)hipFree(t->dpq);
+    transient_quiesce(*t);
     delete t;
 }
 
@@ -222,13 +196,12 @@ int cwf_hip_explicit_create(cwf_hip_system *h, const cwf_explicit_desc *desc, cw
     if (!t)
         return set_error(h, CWF_ERR_ALLOC, "host allocation failed");
     t->sys = h;
+    t->alloc_error = "failed to allocate explicit stepper buffers";
     t->alpha = desc->rayleigh_alpha;
     t->beta = desc->rayleigh_beta;
     t->dt = dt;
     t->lambda_max = lam;
     t->critical_dt = crit;
-    const uint64_t D = h->ds.D;
-    const size_t vb = std::max<uint64_t>(D, 4) * sizeof(float);
     std::vector<float **> bufs = {&t->u, &t->v, &t->f, &t->bcv};
     if (t->beta != 0.0)
         bufs.push_back(&t->w);
@@ -236,28 +209,15 @@ int cwf_hip_explicit_create(cwf_hip_system *h, const cwf_explicit_desc *desc, cw
         bufs.push_back(&t->y);
     int st = 0;
     for (float **p : bufs)
-        if (!st)
-            st = ex_alloc(t, reinterpret_cast<void **>(p), vb);
+        st = st ? st : t->alloc_vector(p);
+    st = st ? st : t->alloc(&t->non_finite, 1);
     if (!st)
-        st = ex_alloc(t, reinterpret_cast<void **>(&t->non_finite), sizeof(uint32_t));
-    if (st)
     {
-        cwf_hip_explicit_destroy(t);
-        return st;
+        if (!t->w)
+            t->w = t->u;
+        (void)hipMemsetAsync(t->non_finite, 0, sizeof(uint32_t), h->stream);
+        st = transient_start(*t, desc->external_force, desc->bc_value, "explicit stepper create");
     }
-    if (!t->w)
-        t->w = t->u;
-    hipStream_t s = h->stream;
-    for (float *p : {t->u, t->v, t->f, t->bcv})
-        (void)hipMemsetAsync(p, 0, vb, s);
-    (void)hipMemsetAsync(t->non_finite, 0, sizeof(uint32_t), s);
-    if (desc->external_force)
-        st = vec_in(h, desc->external_force, t->f, CWF_PTR_HOST, 3);
-    if (!st && desc->bc_value)
-        st = vec_in(h, desc->bc_value, t->bcv, CWF_PTR_HOST, 3);
-    hipError_t e = hipStreamSynchronize(s);
-    if (!st && e != hipSuccess)
-        st = hip_fail(h, e, "explicit stepper create");
     if (st)
     {
         cwf_hip_explicit_destroy(t);
@@ -300,7 +260,7 @@ int cwf_hip_explicit_advance(cwf_hip_explicit *t, uint64_t n_steps, cwf_explicit
     a.non_finite = t->non_finite;
     const bool dash = !t->dash_ids.empty();
     a.dslot = dash ? t->dslot : nullptr;
-    a.dpq = dash ? t->dpq : nullptr;
+    a.dpq = dash ? t->dpq.get() : nullptr;
     for (uint64_t i = 0; i < n_steps; ++i)
     {
         if (pattern)
@@ -333,24 +293,10 @@ int cwf_hip_explicit_get_state(cwf_hip_explicit *t, int which, float *out, uint6
 {
     if (!t || !out)
         return set_error(nullptr, CWF_ERR_ARGUMENT, "null pointer");
-    cwf_hip_system *h = t->sys;
-    if (int st = check_ready(h))
-        return st;
-    if (n != h->ds.D)
-        return set_error(h, CWF_ERR_SIZE, "state span size mismatch");
     const float *src = which == 0 ? t->u : which == 1 ? t->v : which == 4 ? t->f : nullptr;
-    if (!src)
-        return set_error(h, CWF_ERR_ARGUMENT, "unknown state field");
-    if (which == 4 && t->lbase && !t->ctimes.empty() && t->steps)
-    {
-        // the update pass formed f_n in registers: the same rounding, on request
-        stepper_scaled_load(h->ds.D, t->lbase, t->lpat, t->last_scale, t->f, h->stream);
-        HIPTRY(h, hipGetLastError());
-    }
-    if (int st = vec_out(h, src, out, kind, 3))
-        return st;
-    HIPTRY(h, hipStreamSynchronize(h->stream));
-    return 0;
+    // the update pass formed f_n in registers: the same rounding, on request
+    const bool reform = which == 4 && t->lbase && !t->ctimes.empty() && t->steps;
+    return transient_get(*t, src, out, n, kind, reform ? &t->last_scale : nullptr);
 }
 
 int cwf_hip_explicit_set_state(cwf_hip_explicit *t, int which, const float *in, uint64_t n, int kind)
@@ -358,14 +304,8 @@ int cwf_hip_explicit_set_state(cwf_hip_explicit *t, int which, const float *in, 
     if (!t || !in)
         return set_error(nullptr, CWF_ERR_ARGUMENT, "null pointer");
     cwf_hip_system *h = t->sys;
-    if (int st = check_ready(h))
-        return st;
-    if (n != h->ds.D)
-        return set_error(h, CWF_ERR_SIZE, "state span size mismatch");
-    float *dst = which == 0 ? t->u : which == 1 ? t->v : nullptr;
-    if (!dst)
-        return set_error(h, CWF_ERR_ARGUMENT, "unknown state field");
-    if (int st = vec_in(h, in, dst, kind, 3))
+    float *dst = which == 0 ? t->u : which == 1 ? t->v : nullptr;  // f (4) is set through set_external_force
+    if (int st = transient_set(*t, "state", dst, in, n, kind, false))
         return st;
     t->input_stale = true;
     HIPTRY(h, hipMemsetAsync(t->non_finite, 0, sizeof(uint32_t), h->stream));
@@ -377,43 +317,14 @@ int cwf_hip_explicit_set_external_force(cwf_hip_explicit *t, const float *f, uin
 {
     if (!t || !f)
         return set_error(nullptr, CWF_ERR_ARGUMENT, "null pointer");
-    cwf_hip_system *h = t->sys;
-    if (int st = check_ready(h))
-        return st;
-    if (n != h->ds.D)
-        return set_error(h, CWF_ERR_SIZE, "external force span size mismatch");
-    if (int st = vec_in(h, f, t->f, kind, 3))
-        return st;
-    HIPTRY(h, hipStreamSynchronize(h->stream));
-    return 0;
+    return transient_set(*t, "external force", t->f, f, n, kind);
 }
 
 int cwf_hip_explicit_set_load_pattern(cwf_hip_explicit *t, const double *base, const double *pattern, uint64_t n)
 {
     if (!t || !base || !pattern)
         return set_error(nullptr, CWF_ERR_ARGUMENT, "null pointer");
-    cwf_hip_system *h = t->sys;
-    if (int st = check_ready(h))
-        return st;
-    if (n != h->ds.D)
-        return set_error(h, CWF_ERR_SIZE, "load pattern span size mismatch",
-                         "input=" + std::to_string(n) + "\ndofs=" + std::to_string(h->ds.D));
-    if (!t->lbase)
-    {
-        void *q = nullptr;
-        if (int st = ex_alloc(t, &q, std::max<uint64_t>(2 * n, 2) * sizeof(double)))
-            return st;
-        t->lbase = static_cast<double *>(q);
-        t->lpat = t->lbase + n;
-    }
-    // a node's 3 f64 = 6 floats: the node-order conversion moves them as 6-float records
-    if (int st = vec_in(h, reinterpret_cast<const float *>(base), reinterpret_cast<float *>(t->lbase), CWF_PTR_HOST, 6))
-        return st;
-    if (int st = vec_in(h, reinterpret_cast<const float *>(pattern), reinterpret_cast<float *>(t->lpat), CWF_PTR_HOST,
-                        6))
-        return st;
-    HIPTRY(h, hipStreamSynchronize(h->stream));
-    return 0;
+    return transient_set_load_pattern(*t, base, pattern, n);
 }
 
 int cwf_hip_explicit_set_load_curve(cwf_hip_explicit *t, const double *times, const double *values, uint64_t count)
@@ -454,8 +365,7 @@ int cwf_hip_explicit_set_dashpots(cwf_hip_explicit *t, uint64_t count, const uin
     if (count == 0)
     {
         HIPTRY(h, hipStreamSynchronize(s));
-        (void)hipFree(t->dpq);
-        t->dpq = nullptr;
+        t->dpq.reset();
         t->dash_ids.clear();
         t->dash_C.clear();
         return 0;
@@ -481,19 +391,12 @@ int cwf_hip_explicit_set_dashpots(cwf_hip_explicit *t, uint64_t count, const uin
         if (const char *why = dashpot_update(C + 9 * i, (double)mass[node_ids[i]], t->alpha, t->dt, &pq[18 * i],
                                              &pq[18 * i + 9]))
             return set_error(h, CWF_ERR_ARGUMENT, why, "index=" + std::to_string(i));
-    void *rec = nullptr;
-    if (hipMalloc(&rec, pq.size() * sizeof(double)) != hipSuccess)
-        return set_error(h, CWF_ERR_ALLOC, "failed to allocate explicit stepper buffers");
+    DevicePtr<double> rec;  // the new set's records: the stepper's once everything else went well
+    if (rec.alloc(pq.size()) != hipSuccess)
+        return set_error(h, CWF_ERR_ALLOC, t->alloc_error);
     if (!t->dslot)
-    {
-        void *q = nullptr;
-        if (int st = ex_alloc(t, &q, slot.size() * sizeof(uint32_t)))
-        {
-            (void)hipFree(rec);
+        if (int st = t->alloc(&t->dslot, slot.size()))
             return st;
-        }
-        t->dslot = static_cast<uint32_t *>(q);
-    }
     hipError_t e = hipMemcpyAsync(rec, pq.data(), pq.size() * sizeof(double), hipMemcpyHostToDevice, s);
     int st = 0;
     if (e == hipSuccess)  // the slots move to the internal order as a one-word node vector (bit copies)
@@ -504,13 +407,11 @@ int cwf_hip_explicit_set_dashpots(cwf_hip_explicit *t, uint64_t count, const uin
     if (e != hipSuccess || st)
     {
         (void)hipStreamSynchronize(s);
-        (void)hipFree(rec);
         t->dash_ids.clear();  // the slot array may be half written: no dashpots until the next set
         t->dash_C.clear();
         return st ? st : hip_fail(h, e, "explicit set_dashpots");
     }
-    (void)hipFree(t->dpq);
-    t->dpq = static_cast<double *>(rec);
+    t->dpq = std::move(rec);
     t->dash_ids.assign(node_ids, node_ids + count);
     t->dash_C.assign(C, C + 9 * count);
     return 0;
@@ -532,11 +433,7 @@ int cwf_hip_explicit_time(const cwf_hip_explicit *t, double *current_time, doubl
 {
     if (!t)
         return set_error(nullptr, CWF_ERR_ARGUMENT, "null handle");
-    if (current_time)
-        *current_time = (double)t->steps * t->dt;
-    if (time_step)
-        *time_step = t->dt;
-    return 0;
+    return transient_time((double)t->steps * t->dt, t->dt, current_time, time_step);
 }
 
 }  // extern "C"

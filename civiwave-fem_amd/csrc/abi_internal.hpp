@@ -1,7 +1,10 @@
 // abi_internal.hpp -- what the C-ABI translation units (abi.cpp: handles, abi_pcg.cpp: apply_keff / block
-// Jacobi / dot / solve_pcg, abi_stepper.cpp: the Stepper) share: the HIP error macro, device allocation and
-// upload, vector staging between the caller's layout and the handle's, the PCG driver, and the host-only pieces
-// of cwf_hip_system_create (abi.cpp, tiles.cpp, lattice.cpp; tests/cpp/create_host_test.cpp calls them).
+// Jacobi / dot / solve_pcg, abi_stepper.cpp: the Stepper, abi_explicit.cpp: the explicit stepper, comm.cpp, modal.cpp,
+// refine.cpp) share: the HIP error macro, device allocation and upload from the handle's arena (devmem.hpp: dalloc,
+// upload, Uploader), the operator apply by the handle's mode (keff_apply, keff_apply_ds, stiffness_only), the scope
+// guard of the operator scalars (ScalarScope), vector staging between the caller's layout and the handle's, the PCG
+// driver, the steppers' state core (TransientState, abi_transient.cpp), and the host-only pieces of
+// cwf_hip_system_create (abi.cpp, tiles.cpp, lattice.cpp; tests/cpp/create_host_test.cpp calls them).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -27,17 +30,51 @@ namespace cwf
 
 template <class T> inline int dalloc(cwf_hip_system *h, T **p, size_t count)
 {
-    void *q = nullptr;
-    const size_t bytes = std::max<size_t>(count * sizeof(T), 16);
-    hipError_t e = hipMalloc(&q, bytes);
-    if (e != hipSuccess)
+    *p = h->mem.alloc<T>(count);
+    if (!*p)
         return set_error(h, CWF_ERR_ALLOC, "failed to allocate device buffer",
-                         "bytes=" + std::to_string(bytes));
-    h->owned.push_back(q);
-    h->bytes += bytes;
-    *p = static_cast<T *>(q);
+                         "bytes=" + std::to_string(device_bytes<T>(count)));
     return 0;
 }
+
+// The handle's operator on device vectors, FAST or PARITY by its mode: with the scalars of s (the handle's DevSys or
+// a copy of it), and with the handle's own
+inline void keff_apply_ds(const cwf_hip_system *h, const DevSys &s, const float *x, float *y, bool sanitize,
+                          hipStream_t st)
+{
+    h->mode == CWF_MODE_FAST ? fast_keff_ds(s, x, y, sanitize, st) : parity_keff_ds(s, x, y, sanitize, nullptr, st);
+}
+inline void keff_apply(const cwf_hip_system *h, const float *x, float *y, hipStream_t st)
+{
+    keff_apply_ds(h, h->ds, x, y, true, st);
+}
+
+// the handle's operator at scalars (1, 0), the handle itself untouched (newmark_stepper.cpp:1051-1053)
+inline DevSys stiffness_only(const cwf_hip_system *h)
+{
+    DevSys s = h->ds;
+    s.sK = 1.0;
+    s.sM = 0.0;
+    return s;
+}
+
+// the handle's operator scalars for one scope: the caller's come back on every path out of it
+struct ScalarScope
+{
+    cwf_hip_system *const h;
+    const double sK, sM;  // the caller's
+    ScalarScope(cwf_hip_system *h, double k, double m) : h(h), sK(h->ds.sK), sM(h->ds.sM)
+    {
+        h->ds.sK = k;
+        h->ds.sM = m;
+    }
+    ~ScalarScope()
+    {
+        h->ds.sK = sK;
+        h->ds.sM = sM;
+    }
+    ScalarScope(const ScalarScope &) = delete;
+};
 
 // a hipEvent pair on the handle's stream whose elapsed times add up into *ms
 struct Stopwatch
@@ -207,5 +244,34 @@ std::string pcg_error_message(int code, int iter, PcgSchedule sch, std::string *
 int run_pcg_group(const std::vector<cwf_hip_system *> &g, const std::vector<const float *> &rhs,
                   const cwf_pcg_settings &set, cwf_pcg_telemetry *tel);
 int run_pcg(cwf_hip_system *h, const float *rhs_dev, const cwf_pcg_settings &set, cwf_pcg_telemetry *tel);
+
+// abi_transient.cpp: the state core of the two time steppers (cwf_hip_stepper and cwf_hip_explicit derive from it).
+// Its buffers live in its own arena: freed with the stepper, not counted by cwf_hip_system_memory.
+struct TransientState
+{
+    cwf_hip_system *sys = nullptr;
+    const char *alloc_error = "";  // the stepper's message of a failed allocation
+    DeviceArena mem;
+    float *u = nullptr, *v = nullptr, *f = nullptr, *bcv = nullptr;  // f32 [D], the handle's node order
+    double *lbase = nullptr, *lpat = nullptr;  // set_load_pattern: f64 [D] each, allocated at the first set
+    template <class T> int alloc(T **p, size_t count)
+    {
+        *p = mem.alloc<T>(count);
+        return *p ? 0 : set_error(sys, CWF_ERR_ALLOC, alloc_error);
+    }
+    int alloc_vector(float **p) { return alloc(p, sys->ds.D); }
+};
+void transient_quiesce(const TransientState &c);  // before the stepper is deleted: its device, its stream drained
+// the create tail: u, v, f, bcv zeroed, the desc's external_force and bc_value (either may be NULL) in, one sync
+int transient_start(TransientState &c, const float *external_force, const float *bc_value, const char *what);
+int transient_form_load(TransientState &c, double scale);  // f = base + scale pattern (stepper_scaled_load)
+// an internal vector out / a caller's vector in, after the span check; src / dst NULL: "unknown state field".
+// load_scale: f is formed from the pattern at *load_scale first; what: the span's name in the size message
+int transient_get(TransientState &c, const float *src, float *out, uint64_t n, int kind,
+                  const double *load_scale = nullptr);
+int transient_set(TransientState &c, const char *what, float *dst, const float *in, uint64_t n, int kind,
+                  bool sync = true);
+int transient_set_load_pattern(TransientState &c, const double *base, const double *pattern, uint64_t n);
+int transient_time(double now, double dt, double *current_time, double *time_step);
 
 }  // namespace cwf

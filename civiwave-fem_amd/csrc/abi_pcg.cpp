@@ -218,11 +218,8 @@ int run_pcg_group(const std::vector<cwf_hip_system *> &g, const std::vector<cons
     for (cwf_hip_system *m : g)
         if (m->hist_cap < set.max_iterations + 1)
         {
-            if (m->hist)
-                (void)hipFree(m->hist);
-            m->hist = nullptr;
             const uint64_t cap = std::max<uint64_t>(set.max_iterations + 1, 1024);
-            if (hipMalloc(reinterpret_cast<void **>(&m->hist), cap * sizeof(double)) != hipSuccess)
+            if (m->hist.alloc(cap) != hipSuccess)
                 return set_error(m, CWF_ERR_ALLOC, "failed to grow matrix-free workspace buffers",
                                  "history=" + std::to_string(cap));
             m->hist_cap = cap;
@@ -340,10 +337,7 @@ int cwf_hip_apply_keff(cwf_hip_system *h, const float *x, float *y, uint64_t n, 
     if (int st = stage_vec(h, x, h->tmp, kind, 3, &xin))
         return st;
     float *yout = kind == CWF_PTR_DEVICE && !h->perm ? y : h->Ap;
-    if (h->mode == CWF_MODE_FAST)
-        fast_keff(h, xin, yout, true, nullptr, nullptr, h->stream);
-    else
-        parity_keff(h, xin, yout, true, nullptr, h->stream);
+    keff_apply(h, xin, yout, h->stream);
     HIPTRY(h, hipGetLastError());
     if (int st = vec_out(h, yout, y, kind, 3))
         return st;

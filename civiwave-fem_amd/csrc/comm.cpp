@@ -20,7 +20,7 @@
 #include <string>
 #include <vector>
 
-#include "cwf_internal.hpp"
+#include "abi_internal.hpp"
 
 namespace cwf
 {
@@ -106,14 +106,6 @@ int nccl_fail(cwf_hip_system *h, ncclResult_t e, const char *what)
         ncclResult_t e__ = (expr);                                                                             \
         if (e__ != ncclSuccess)                                                                                \
             return nccl_fail((h), e__, #expr);                                                                 \
-    } while (0)
-
-#define HIPTRY(h, expr)                                                                                        \
-    do                                                                                                         \
-    {                                                                                                          \
-        hipError_t e__ = (expr);                                                                               \
-        if (e__ != hipSuccess)                                                                                 \
-            return hip_fail((h), e__, #expr);                                                                  \
     } while (0)
 
 }  // namespace
@@ -448,24 +440,14 @@ int parity_setup(const std::vector<cwf_hip_system *> &g)
         // (re)size the slot block: an attach resets pstride, so a re-attached handle reuses its block when it is
         // large enough and frees it otherwise (repeated attach / solve cycles do not grow device memory)
         const size_t bytes = 2 * (size_t)n * stride * sizeof(double);
-        if (h->gp0 && h->gp_bytes < bytes)
+        if (h->gp0 && h->mem.size_of(h->gp0) < bytes)
         {
-            (void)hipFree(h->gp0);
-            h->owned.erase(std::remove(h->owned.begin(), h->owned.end(), static_cast<void *>(h->gp0)), h->owned.end());
-            h->bytes -= h->gp_bytes;
+            h->mem.free(h->gp0);
             h->gp0 = h->gp1 = nullptr;
-            h->gp_bytes = 0;
         }
         if (!h->gp0)
-        {
-            void *q = nullptr;
-            if (hipMalloc(&q, bytes) != hipSuccess)
-                return set_error(h, CWF_ERR_ALLOC, "failed to allocate device buffer", "bytes=" + std::to_string(bytes));
-            h->owned.push_back(q);
-            h->bytes += bytes;
-            h->gp0 = static_cast<double *>(q);
-            h->gp_bytes = bytes;
-        }
+            if (int st = dalloc(h, &h->gp0, 2 * (size_t)n * stride))
+                return st;
         h->gp1 = h->gp0 + (size_t)n * stride;
         HIPTRY(h, hipMemset(h->gp0, 0, bytes));  // the +0.0 padding of every slot
         h->pstride = (uint32_t)stride;
@@ -703,30 +685,18 @@ int cwf_hip_system_attach(cwf_hip_system *h, cwf_hip_comm *cm, int32_t rank, con
     if (int st = hipSetDevice(h->device); st != hipSuccess)
         return hip_fail(h, (hipError_t)st, "hipSetDevice");
     const int n = cm->nranks;
-    auto alloc = [&](void **p, size_t bytes) -> int {
-        hipError_t e = hipMalloc(p, std::max<size_t>(bytes, 16));
-        if (e != hipSuccess)
-            return set_error(h, CWF_ERR_ALLOC, "failed to allocate device buffer", "bytes=" + std::to_string(bytes));
-        h->owned.push_back(*p);
-        h->bytes += std::max<size_t>(bytes, 16);
-        return 0;
-    };
-    void *p = nullptr;
-    if (int st = alloc(&p, 6 * (size_t)n * sizeof(double)))
+    if (int st = dalloc(h, &h->g_pap, 6 * (size_t)n))
         return st;
-    h->g_pap = static_cast<double *>(p);
     h->g_rrz = h->g_pap + n;
     h->g_init = h->g_rrz + 2 * n;
     h->g_rz0 = h->g_init + 2 * n;
     HIPTRY(h, hipMemset(h->g_pap, 0, 6 * (size_t)n * sizeof(double)));
-    if (int st = alloc(&p, nsend * sizeof(uint32_t)))
+    if (int st = dalloc(h, &h->send_idx, nsend))
         return st;
-    h->send_idx = static_cast<uint32_t *>(p);
     if (nsend)
         HIPTRY(h, hipMemcpy(h->send_idx, plan->send_nodes, nsend * sizeof(uint32_t), hipMemcpyHostToDevice));
-    if (int st = alloc(&p, 3 * kMaxHaloVecs * nsend * sizeof(float)))  // one segment per halo vector of a step
+    if (int st = dalloc(h, &h->sendbuf, 3 * kMaxHaloVecs * nsend))  // one segment per halo vector of a step
         return st;
-    h->sendbuf = static_cast<float *>(p);
     h->nsend = nsend;
     h->nbr.assign(plan->neighbor_ranks, plan->neighbor_ranks + K);
     h->send_off.assign(plan->send_offsets, plan->send_offsets + K + 1);
@@ -764,13 +734,10 @@ int cwf_hip_system_attach(cwf_hip_system *h, cwf_hip_comm *cm, int32_t rank, con
         lattice_plan(t);
         if (h->fsh)  // the fused iteration's shares for the shard's work items, its gathered rank totals
         {
-            void *p = nullptr;
-            if (int st = alloc(&p, 2ull * 5 * std::max<uint32_t>(t.lnwork, 1u) * sizeof(double)))
+            if (int st = dalloc(h, &h->fsh, 2ull * 5 * std::max<uint32_t>(t.lnwork, 1u)))
                 return broken(st);
-            h->fsh = static_cast<double *>(p);
-            if (int st = alloc(&p, (size_t)kFusedSlotHost * n * sizeof(double)))
+            if (int st = dalloc(h, &h->g_fsh, (size_t)kFusedSlotHost * n))
                 return broken(st);
-            h->g_fsh = static_cast<double *>(p);
             if (hipError_t e = hipMemset(h->g_fsh, 0, (size_t)kFusedSlotHost * n * sizeof(double)); e != hipSuccess)
                 return broken(hip_fail(h, e, "hipMemset"));
         }

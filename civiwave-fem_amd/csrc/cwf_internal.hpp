@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/cwf_hip.h"
+#include "devmem.hpp"
 #include "knobs.hpp"
 
 namespace cwf
@@ -368,12 +369,6 @@ struct ResidentPlan
     uint64_t ghost_total = 0;   // a shard: ghost halo entries over every box (one Ap granule read each per phase)
 };
 
-struct DevBuf
-{
-    void *p = nullptr;
-    size_t bytes = 0;
-};
-
 
 // ---- absorbing.cpp ----
 // cwf_explicit_dashpot_update without the error record: 0, or why C, mass, alpha or dt is refused
@@ -383,15 +378,19 @@ const char *dashpot_update(const double C[9], double mass, double alpha, double 
 
 struct cwf_hip_system
 {
+    // The destructor (abi.cpp) frees what `mem` and `hist` still hold; it is the library's, so a host program that
+    // fabricates a handle from these headers needs nothing of the HIP runtime at link time
+    cwf_hip_system() = default;
+    cwf_hip_system(cwf_hip_system &&) = default;
+    ~cwf_hip_system();
     int device = 0;
     hipStream_t stream = nullptr;
     int mode = CWF_MODE_PARITY;
     cwf::DevSys ds{};
     uint64_t reduction_block = 256;
     uint64_t reduction_partials = 1;
-    // owned HBM
-    std::vector<void *> owned;
-    uint64_t bytes = 0;
+    // owned HBM: every counted device buffer of the handle (devmem.hpp); its total is cwf_hip_system_memory
+    cwf::DeviceArena mem;
     // solver scratch (f32 dofs) and partials
     // Ap is scratch (apply_keff staging, PARITY's K p, the prologues' K x); FAST PCG never reads it
     float *x = nullptr, *r = nullptr, *p = nullptr, *z = nullptr, *Ap = nullptr, *rhs = nullptr, *tmp = nullptr;
@@ -429,13 +428,13 @@ struct cwf_hip_system
     cwf::Ctl *ctl = nullptr;       // device
     cwf::Ctl *ctl_host = nullptr;  // pinned
     double *scal = nullptr;        // device scalar scratch
-    double *hist = nullptr;        // device residual history
+    cwf::DevicePtr<double> hist;   // device residual history (regrown per solve, not counted)
     uint64_t hist_cap = 0;
     uint64_t hist_count = 0;
     std::vector<uint32_t> lat_plane;  // structured block: host copy of ds.t.lplane (attach derives the owned planes)
     uint64_t last_iters = 0, prev_iters = 0;  // iterations of the last two solves on this handle (first batch size)
     std::string err, ctx;
-    // modal analysis workspace (modal.cpp), allocated at the first block call and kept in `owned`: three blocks of
+    // modal analysis workspace (modal.cpp), allocated at the first block call and kept in `mem`: three blocks of
     // mo_cols columns [3][mo_cols][D], the Gram chunk partials followed by two q x q results and one rotation (fp64),
     // and, on a renumbered handle, the lumped mass and mask in the caller's node order (the public block calls weight
     // caller-order vectors in place)
@@ -444,7 +443,7 @@ struct cwf_hip_system
     double *mo_f64 = nullptr;
     float *mo_mass = nullptr;
     uint32_t *mo_mask = nullptr;
-    // refined solve workspace (refine.cpp), allocated at the first refined call and kept in `owned`: fp64 x, b, r and
+    // refined solve workspace (refine.cpp), allocated at the first refined call and kept in `mem`: fp64 x, b, r and
     // the previous iterate [D] in the internal node order, the nodes' shares of |r|^2 [N], and the norm's chunk
     // partials followed by its two results
     double *rf_x = nullptr, *rf_b = nullptr, *rf_r = nullptr, *rf_xp = nullptr, *rf_share = nullptr, *rf_part = nullptr;
@@ -470,8 +469,7 @@ struct cwf_hip_system
     // sharded PARITY: every rank's 256-DOF chunk partials all-gathered into slot [r * pstride, (r+1) * pstride)
     // (zero-padded past the rank's own chunk count) and folded in that order on every rank = the global chunk
     // order of pcg.cpp:170-207, since the owned node ranges are ascending by rank and aligned to whole chunks
-    double *gp0 = nullptr, *gp1 = nullptr;
-    size_t gp_bytes = 0;  // the slot block gp0 starts (gp1 = gp0 + nranks * pstride)
+    double *gp0 = nullptr, *gp1 = nullptr;  // one slot block, gp0 its start (gp1 = gp0 + nranks * pstride)
     uint32_t pstride = 0;
     uint64_t gbegin = 0;            // global id of the first owned node (cwf_hip_system_attach)
     std::vector<uint64_t> node_gid;  // the plan's global id of every local node (when given): the halo check
@@ -718,10 +716,5 @@ void explicit_operator_input(uint32_t N, const float *u, const float *v, double 
 void explicit_power_start(uint32_t N, const uint32_t *mask, float *x, hipStream_t st);
 void explicit_power_z(uint32_t N, const float *mass, const uint32_t *mask, const float *y, float *z, hipStream_t st);
 void explicit_power_scale(uint32_t D, const float *z, const double *num_den, float *x, double *lam, hipStream_t st);
-
-
-// ---- absorbing.cpp ----
-// cwf_explicit_dashpot_update without the error record: 0, or why C, mass, alpha or dt is refused
-const char *dashpot_update(const double C[9], double mass, double alpha, double dt, double P[9], double Q[9]);
 
 }  // namespace cwf

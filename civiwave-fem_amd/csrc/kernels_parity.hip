@@ -1502,15 +1502,11 @@ void parity_pcg_init(cwf_hip_system *h, const float *rhs, double rel_tol, hipStr
     if (!h->fgran && h->reduction_block == 256 && !knob_off("CWF_PARITY_STREAM"))
     {
         // the streamed folds' granules: 2 per chunk, tag 0 (the first streamed launch's tag is 1)
-        void *q = nullptr;
-        const size_t bytes = 32ull * chunks + 64u;
-        if (hipMalloc(&q, bytes) == hipSuccess)
+        const size_t count = 4ull * chunks + 8u;  // doubles: 32 B per chunk and 64 B
+        if ((h->fgran = h->mem.alloc<double>(count)) != nullptr)
         {
-            h->owned.push_back(q);
-            h->bytes += bytes;
-            h->fgran = static_cast<double *>(q);
             h->fgran_tag = 0;
-            (void)hipMemsetAsync(q, 0, bytes, st);
+            (void)hipMemsetAsync(h->fgran, 0, count * sizeof(double), st);
         }
     }
     parity_block_jacobi(h, h->inv, st);

@@ -15,17 +15,10 @@ namespace
 
 constexpr size_t kQQ = (size_t)kModalMaxBlock * kModalMaxBlock;
 
-template <class T> int regrow(cwf_hip_system *h, T **p, size_t old_count, size_t count)
+template <class T> int regrow(cwf_hip_system *h, T **p, size_t count)
 {
-    if (*p)
-    {
-        auto it = std::find(h->owned.begin(), h->owned.end(), static_cast<void *>(*p));
-        if (it != h->owned.end())
-            h->owned.erase(it);
-        (void)hipFree(*p);
-        h->bytes -= std::max<size_t>(old_count * sizeof(T), 16);
-        *p = nullptr;
-    }
+    h->mem.free(*p);
+    *p = nullptr;
     return dalloc(h, p, count);
 }
 
@@ -36,9 +29,8 @@ int modal_workspace(cwf_hip_system *h, uint32_t q, bool caller_weights)
     const size_t D = h->ds.D;
     if (h->mo_cols < q)
     {
-        const size_t old = 3 * (size_t)h->mo_cols * D;
         h->mo_cols = 0;
-        if (int st = regrow(h, &h->mo_blk, old, 3 * (size_t)q * D))
+        if (int st = regrow(h, &h->mo_blk, 3 * (size_t)q * D))
             return st;
         h->mo_cols = q;
     }
@@ -122,10 +114,7 @@ int modal_iterate(cwf_hip_system *h, const ModalPlan &mp, double *eigenvalues, f
         double kx = 0.0, mx = 0.0;
         sw.start(st);
         HIPTRY(h, hipMemcpyAsync(h->tmp, probe, (size_t)D * sizeof(float), hipMemcpyDeviceToDevice, st));
-        if (h->mode == CWF_MODE_FAST)
-            fast_keff(h, h->tmp, h->Ap, true, nullptr, nullptr, st);
-        else
-            parity_keff(h, h->tmp, h->Ap, true, nullptr, st);
+        keff_apply(h, h->tmp, h->Ap, st);
         modal_gram(h->tmp, 1, h->Ap, 1, D, nullptr, nullptr, gram_part(h), Kd, st);
         modal_gram(h->tmp, 1, h->tmp, 1, D, h->ds.mass, h->ds.mask, gram_part(h), Md, st);
         HIPTRY(h, hipGetLastError());
@@ -182,10 +171,7 @@ int modal_iterate(cwf_hip_system *h, const ModalPlan &mp, double *eigenvalues, f
             {
                 const size_t bytes = (size_t)D * sizeof(float);  // staged as cwf_hip_apply_keff stages: tmp -> Ap
                 HIPTRY(h, hipMemcpyAsync(h->tmp, Xb + (size_t)j * D, bytes, hipMemcpyDeviceToDevice, st));
-                if (h->mode == CWF_MODE_FAST)
-                    fast_keff(h, h->tmp, h->Ap, true, nullptr, nullptr, st);
-                else
-                    parity_keff(h, h->tmp, h->Ap, true, nullptr, st);
+                keff_apply(h, h->tmp, h->Ap, st);
                 HIPTRY(h, hipMemcpyAsync(X + (size_t)j * D, h->Ap, bytes, hipMemcpyDeviceToDevice, st));
             }
             HIPTRY(h, hipGetLastError());
@@ -370,21 +356,15 @@ int cwf_hip_modal_solve(cwf_hip_system *h, const cwf_modal_settings *s, double *
         mp.pcg.max_iterations = 20000;
     tel->block = mp.q;
     // the operator of the iteration is K + sigma M; the caller's scalars return on every path out of modal_iterate
-    const double sK = h->ds.sK, sM = h->ds.sM;
-    h->ds.sK = 1.0;
-    h->ds.sM = mp.sigma;
-    int st;
+    const ScalarScope modal_scalars(h, 1.0, mp.sigma);
     try
     {
-        st = modal_iterate(h, mp, eigenvalues, modes_out, kind, tel);
+        return modal_iterate(h, mp, eigenvalues, modes_out, kind, tel);
     }
     catch (const std::bad_alloc &)
     {
-        st = set_error(h, CWF_ERR_ALLOC, "host allocation failed");
+        return set_error(h, CWF_ERR_ALLOC, "host allocation failed");
     }
-    h->ds.sK = sK;
-    h->ds.sM = sM;
-    return st;
 }
 
 int cwf_hip_block_gram(cwf_hip_system *h, const float *A, uint32_t qa, const float *B, uint32_t qb, int mass_weighted,

@@ -14,6 +14,7 @@ import numpy as np
 from . import _lib
 from .pcg import Expected, MatrixFreeSystem
 from .physics import Curve, RayleighCoefficients, SolverSettings, TimeSettings
+from .transient import TransientState
 
 
 @dataclass
@@ -60,12 +61,14 @@ def curve_value(curve, t: float) -> float:
     return float(_lib.load().cwf_explicit_curve_value(_lib.ptr(times), _lib.ptr(values), len(pts), float(t)))
 
 
-class ExplicitStepper:
+class ExplicitStepper(TransientState):
     """ExplicitStepper(packing, materials, rayleigh, solver_settings, time_settings, ...): the constructor shape of
     cwf.stepper.Stepper. solver_settings is unused (there is no solve) and time_settings.initial_dt is the
-    implicit scheme's step, so neither sets the explicit step: ``dt`` does (0: safety x the estimated limit)."""
+    implicit scheme's step, so neither sets the explicit step: ``dt`` does (0: safety x the estimated limit).
+    State, external force, load pattern, times and close(): cwf.transient.TransientState."""
 
     DISPLACEMENT, VELOCITY, ACCELERATION, EXTERNAL_FORCE = 0, 1, 2, 4
+    _PREFIX, _HANDLE = "cwf_hip_explicit", "_ex"
 
     def __init__(self, packing, materials, rayleigh: RayleighCoefficients,
                  solver_settings: SolverSettings | None = None, time_settings: TimeSettings | None = None,
@@ -87,10 +90,6 @@ class ExplicitStepper:
         self.dof_count = packing.dof_count
         self.node_count = packing.node_count
 
-    def _check(self, rc):
-        if rc:
-            raise RuntimeError(_lib.last_error(self.system._h))
-
     def advance(self, n_steps: int) -> Expected:
         t = _lib.ExplicitTelemetryC()
         rc = _lib.load().cwf_hip_explicit_advance(self._ex, int(n_steps), C.byref(t))
@@ -106,45 +105,10 @@ class ExplicitStepper:
             raise RuntimeError(f"{r.error().message} {r.error().context}")
         return r.value()
 
-    def _times(self):
-        ct, dt = C.c_double(), C.c_double()
-        _lib.load().cwf_hip_explicit_time(self._ex, C.byref(ct), C.byref(dt))
-        return ct.value, dt.value
-
-    def current_time(self) -> float:
-        return self._times()[0]
-
-    def time_step(self) -> float:
-        return self._times()[1]
-
     def get_state(self, which: int, out=None):
-        if out is None:
-            out = np.zeros(self.dof_count, np.float32)
         if which == self.ACCELERATION:  # the scheme keeps none; the frame writers ask for the Newmark triple
-            return out
-        kind = _lib.PTR_HOST if isinstance(out, np.ndarray) else _lib.PTR_DEVICE
-        self._check(_lib.load().cwf_hip_explicit_get_state(self._ex, which, _lib.ptr(out), self.dof_count, kind))
-        return out
-
-    def set_state(self, which: int, values):
-        kind = _lib.PTR_HOST if isinstance(values, np.ndarray) else _lib.PTR_DEVICE
-        if isinstance(values, np.ndarray):
-            values = np.ascontiguousarray(values, np.float32)
-        self._check(_lib.load().cwf_hip_explicit_set_state(self._ex, which, _lib.ptr(values), self.dof_count, kind))
-
-    def set_external_force(self, force):
-        kind = _lib.PTR_HOST if isinstance(force, np.ndarray) else _lib.PTR_DEVICE
-        if isinstance(force, np.ndarray):
-            force = np.ascontiguousarray(force, np.float32)
-        self._check(_lib.load().cwf_hip_explicit_set_external_force(self._ex, _lib.ptr(force), self.dof_count, kind))
-
-    def set_load_pattern(self, base: np.ndarray, pattern: np.ndarray):
-        """f64 [3N] base and pattern as Stepper.set_load_pattern; with set_load_curve the update pass forms
-        f32(base + curve(t_n) * pattern) itself at every step."""
-        base = np.ascontiguousarray(base, np.float64)
-        pattern = np.ascontiguousarray(pattern, np.float64)
-        self._check(_lib.load().cwf_hip_explicit_set_load_pattern(self._ex, _lib.ptr(base), _lib.ptr(pattern),
-                                                                  self.dof_count))
+            return np.zeros(self.dof_count, np.float32) if out is None else out
+        return super().get_state(which, out)
 
     def set_load_curve(self, curve):
         """curve: a Curve, a sequence of (time, value), or None to remove it."""
@@ -174,14 +138,3 @@ class ExplicitStepper:
 
     def clear_dashpots(self):
         self._check(_lib.load().cwf_hip_explicit_set_dashpots(self._ex, 0, None, None))
-
-    def close(self):
-        if getattr(self, "_ex", None) is not None:
-            _lib.load().cwf_hip_explicit_destroy(self._ex)
-            self._ex = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

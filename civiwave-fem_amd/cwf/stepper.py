@@ -14,6 +14,7 @@ import numpy as np
 from . import _lib
 from .pcg import Expected, MatrixFreeSystem, PcgTelemetry
 from .physics import RayleighCoefficients, SolverSettings, TimeSettings
+from .transient import TransientState
 
 
 @dataclass
@@ -42,10 +43,12 @@ class StepTelemetry:
     pcg: PcgTelemetry
 
 
-class Stepper:
-    """Stepper(packing, materials, rayleigh, solver_settings, time_settings, adaptive_policy)."""
+class Stepper(TransientState):
+    """Stepper(packing, materials, rayleigh, solver_settings, time_settings, adaptive_policy). State, external force,
+    load pattern, times and close(): cwf.transient.TransientState."""
 
     DISPLACEMENT, VELOCITY, ACCELERATION, SOLUTION, EXTERNAL_FORCE = 0, 1, 2, 3, 4
+    _PREFIX, _HANDLE = "cwf_hip_stepper", "_st"
 
     def __init__(self, packing, materials, rayleigh: RayleighCoefficients, solver_settings: SolverSettings,
                  time_settings: TimeSettings, adaptive_policy: AdaptivePolicy | None = None,
@@ -80,68 +83,9 @@ class Stepper:
                                       bool(t.dt_increased), bool(t.dt_decreased), bool(t.dt_clamped_min),
                                       bool(t.dt_clamped_max), PcgTelemetry.from_c(t.pcg)))
 
-    def _times(self):
-        ct, dt = C.c_double(), C.c_double()
-        _lib.load().cwf_hip_stepper_time(self._st, C.byref(ct), C.byref(dt))
-        return ct.value, dt.value
-
-    def current_time(self) -> float:
-        return self._times()[0]
-
-    def time_step(self) -> float:
-        return self._times()[1]
-
     def set_warm_start(self, enabled: bool):
         _lib.load().cwf_hip_stepper_set_warm_start(self._st, int(enabled))
 
-    def get_state(self, which: int, out=None):
-        if out is None:
-            out = np.zeros(self.dof_count, np.float32)
-        kind = _lib.PTR_HOST if isinstance(out, np.ndarray) else _lib.PTR_DEVICE
-        rc = _lib.load().cwf_hip_stepper_get_state(self._st, which, _lib.ptr(out), self.dof_count, kind)
-        if rc:
-            raise RuntimeError(_lib.last_error(self.system._h))
-        return out
-
-    def set_state(self, which: int, values):
-        kind = _lib.PTR_HOST if isinstance(values, np.ndarray) else _lib.PTR_DEVICE
-        if isinstance(values, np.ndarray):
-            values = np.ascontiguousarray(values, np.float32)
-        rc = _lib.load().cwf_hip_stepper_set_state(self._st, which, _lib.ptr(values), self.dof_count, kind)
-        if rc:
-            raise RuntimeError(_lib.last_error(self.system._h))
-
-    def set_external_force(self, force):
-        """Rewrite nodes.external_force between steps (the viewer does this, viewer.cpp:262-266)."""
-        kind = _lib.PTR_HOST if isinstance(force, np.ndarray) else _lib.PTR_DEVICE
-        if isinstance(force, np.ndarray):
-            force = np.ascontiguousarray(force, np.float32)
-        rc = _lib.load().cwf_hip_stepper_set_external_force(self._st, _lib.ptr(force), self.dof_count, kind)
-        if rc:
-            raise RuntimeError(_lib.last_error(self.system._h))
-
-    def set_load_pattern(self, base: np.ndarray, pattern: np.ndarray):
-        """Device-side time-varying load (cwf_hip_stepper_set_load_pattern): f64 [3N] loads no curve scales and
-        the point-load values one curve scales; set_load_scale(c) then packs f32(base + c * pattern)."""
-        self._lbase = np.ascontiguousarray(base, np.float64)
-        self._lpat = np.ascontiguousarray(pattern, np.float64)
-        rc = _lib.load().cwf_hip_stepper_set_load_pattern(self._st, _lib.ptr(self._lbase), _lib.ptr(self._lpat),
-                                                          self.dof_count)
-        if rc:
-            raise RuntimeError(_lib.last_error(self.system._h))
-
     def set_load_scale(self, scale: float):
-        rc = _lib.load().cwf_hip_stepper_set_load_scale(self._st, float(scale))
-        if rc:
-            raise RuntimeError(_lib.last_error(self.system._h))
-
-    def close(self):
-        if getattr(self, "_st", None) is not None:
-            _lib.load().cwf_hip_stepper_destroy(self._st)
-            self._st = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        """f = f32(base + scale * pattern) of set_load_pattern, ordered before the next step."""
+        self._check(_lib.load().cwf_hip_stepper_set_load_scale(self._st, float(scale)))

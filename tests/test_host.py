@@ -132,6 +132,21 @@ def test_keff_kernel_names(tmp_path):
     assert out.stdout.splitlines() == want.splitlines()
 
 
+def test_device_ledger(tmp_path):
+    """tests/cpp/devmem_test.cpp: DeviceLedger of csrc/devmem.hpp (the bookkeeping under every DeviceArena, and so
+    under cwf_hip_system_memory) on made-up pointers. Plain g++, linked against nothing: no GPU call."""
+    import subprocess
+    import os
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "devmem_test")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
+                    "-I" + os.path.join(root, "civiwave-fem_amd", "csrc"),
+                    os.path.join(root, "tests", "cpp", "devmem_test.cpp"), "-o", exe], check=True)
+    out = subprocess.run([exe], check=True, capture_output=True, text=True)
+    assert out.stdout.strip() == "ok"
+
+
 def test_cpp_mirror_header_compiles_and_links(tmp_path):
     """include/cwf_hip.hpp (C++ mirror of cwf::gpu::pcg / Stepper) builds with the image's g++."""
     assert _build_cpp_test(tmp_path)
