@@ -367,6 +367,12 @@ struct ResidentPlan
     bool shard = false;         // a PEER slab shard: ghost records in the mailbox, rank totals across ranks
     uint64_t remote_sends = 0;  // a shard: Ap granules stored into the neighbours' mailboxes per phase
     uint64_t ghost_total = 0;   // a shard: ghost halo entries over every box (one Ap granule read each per phase)
+    // the reducer role (resident.hip): workgroup G of a G + 1 grid folds the shares and decides for every box
+    unsigned capacity = 0;      // workgroups the device holds at once (occupancy x CUs): the role needs G + 1 <= capacity
+    uint32_t dec_off = 0;       // byte offset in pub of the two 128-B-spaced decision granules (0: pub has no room)
+    // diagnostic (CWF_RESIDENT_TRACE): this handle's stamp rows, 8 per workgroup, on this handle's device
+    DevicePtr<uint64_t> trace;
+    unsigned trace_n = 0;
 };
 
 

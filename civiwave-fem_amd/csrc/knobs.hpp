@@ -44,7 +44,10 @@ inline constexpr Knob kKnobs[] = {
                            "appended (tools/resident_trace.py)"},
     {"CWF_RESIDENT_REREAD", "1: every phase of the resident solve takes its first ring vote as failed once, so every ring "
                             "granule is requested and formed twice (tests/test_gpu_resident_handoff.py: same bits)"},
-    {"CWF_FUSED_TRACE_IT", "n: the iteration whose launch CWF_FUSED_TRACE records (default 50)"},
+    {"CWF_RESIDENT_REDUCER", "0|1, read at every launch: the resident solve's share fold and decision by one extra workgroup on a "
+                             "spare CU, never / wherever the plan is eligible (unsharded, >= 2 boxes, one more workgroup "
+                             "co-resident); default: eligible and at least kResReducerMinBoxes boxes (resident.hip)"},
+    {"CWF_FUSED_TRACE_IT","n: the iteration whose launch CWF_FUSED_TRACE records (default 50)"},
     {"CWF_FUSED_MAXWG", "n: cap on the fused launch's grid (default 1024 workgroups; a grid below the work items walks them persistently)"},
     {"CWF_XLAG", "1..4: iterations per lazy x update (tests/test_gpu_parity.py compares 4 with 1)"},
     // multi-GPU (comm.cpp)

@@ -124,9 +124,9 @@ enum
 };
 
 // pcg.cpp:840-895 from the folded shares v of the launch (or resident phase) before j: alpha_(j-1), beta_j and the
-// convergence of r_(j-1); block 0's thread 0 records them (and the history). Every caller holds the same v, so every
-// workgroup takes the same decision. Returns false when the solve is over.
-__device__ __forceinline__ bool fused_decide(Ctl *ctl, double *hist, unsigned j, const CtlPre &pre,
+// convergence of r_(j-1); the one thread of the grid the caller names as `writer` records them (and the history).
+// Every caller holds the same v, so every workgroup takes the same decision. Returns false when the solve is over.
+__device__ __forceinline__ bool fused_decide(Ctl *ctl, double *hist, unsigned j, const CtlPre &pre, bool writer,
                                              const double v[kFusedShares], float *alpha_out, float *beta_out)
 {
     const unsigned it = j - 1u;  // the completed updates r_(j-1) carries (launch 0 made none)
@@ -139,7 +139,7 @@ __device__ __forceinline__ bool fused_decide(Ctl *ctl, double *hist, unsigned j,
     const double alpha = (conv || derr || rerr) ? 0.0 : rho / denom;
     const double rho_next = rho - 2.0 * alpha * v[kFZA] + alpha * alpha * v[kFAMA];
     const double beta = (conv || derr || rerr) ? 0.0 : rho_next / rho;
-    if (blockIdx.x == 0 && threadIdx.x == 0)
+    if (writer)
     {
         if (it > 0)
         {

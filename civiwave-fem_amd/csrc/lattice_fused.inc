@@ -175,7 +175,7 @@ __device__ __forceinline__ bool fused_scalars(const FusedArgs &fa, const CtlPre 
     fold_k<NT, kFusedShares>(fa.sin, fa.nin, fa.sin_stride, red, v, fa.sis);
     if (!pre.active)
         return false;
-    return fused_decide(fa.ctl, fa.hist, fa.j, pre, v, alpha_out, beta_out);
+    return fused_decide(fa.ctl, fa.hist, fa.j, pre, blockIdx.x == 0 && threadIdx.x == 0, v, alpha_out, beta_out);
 }
 
 // one LDS entry's raw values: r, Ap, p_old of iteration j - 1 and the class byte; the own column's entry also x

@@ -268,7 +268,8 @@ bool plan_resident(cwf_hip_system *h, bool shard)
     const unsigned own_stride = (small ? 3u : 4u) * kResThreads, halo_stride = (small ? 2u : 3u) * kResThreads;
     const size_t lds = max_slots * 16;
     // one workgroup per CU at least (the grid waits for all of them every phase)
-    if (resident_blocks_per_cu(h->ds, npt, nph, lds, shard) < 1)
+    const int bpc = resident_blocks_per_cu(h->ds, npt, nph, lds, shard);
+    if (bpc < 1)
         return false;
     std::vector<uint4> own((size_t)G * own_stride, uint4{kNone, 0u, kNone, kNone}),
         halo((size_t)G * halo_stride, uint4{kNone, 0u, kNone, 0u});
@@ -361,6 +362,12 @@ bool plan_resident(cwf_hip_system *h, bool shard)
     rp.shard = shard;
     rp.remote_sends = remote_sends;
     rp.ghost_total = ghost_total;
+    // the reducer role's two decision granules (resident.hip): 128 B apart in the part of pub the kernel leaves unused
+    // (96 B are allocated per published node, 32 B used: one 16-B granule per parity), past the Ap granules; zeroed
+    // with them above
+    rp.capacity = (unsigned)bpc * G0;
+    const uint64_t dec = (32ull * rp.npub + 127u) / 128u * 128u;
+    rp.dec_off = dec + 256u <= 96ull * rp.npub && dec + 256u < 0xFFFFFF00ull ? (uint32_t)dec : 0u;
     if (knob("CWF_VERBOSE"))
         fprintf(stderr, "[cwf] resident plan: %u boxes (%u x %u x %u), max_own %u, max_halo %u, %u published nodes\n", G,
                 bg[0], bg[1], bg[2], max_own, max_halo, npub);

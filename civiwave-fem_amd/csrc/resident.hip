@@ -24,6 +24,20 @@
 //     alpha and beta (every workgroup folds the same shares in the same order, fused_decide), so both sides hold the
 //     same r_j and p_j bit for bit and neither ever has to be sent. A shard's ghost entries are ring entries like any
 //     other: only the source of their Ap granule differs (the PEER mailbox, system scope);
+//   - who folds the shares is decided per launch (launch_pcg_resident, CWF_RESIDENT_REDUCER):
+//     * the reducer role (an unsharded plan of >= kResReducerMinBoxes boxes that leaves a CU spare: C2's 245 boxes on
+//       256 CUs): the grid is G + 1 workgroups and workgroup G owns no box (resident_reduce). Per phase its thread
+//       t < G polls box t's five shares (each wave on its own), it folds them with block_sum_lds in the boxes' order,
+//       runs fused_decide ONCE, records ctl and the history, and stores one decision granule {alpha f32, beta f32,
+//       state, tag0 + j} (two of them, by phase parity, 128 B apart in the part of pub behind the Ap granules). A box
+//       polls that one granule (every lane the same address, under the workgroup's vote) and meanwhile requests its
+//       ring's Ap granules, each until it carries the tag; it takes alpha and beta from the granule and neither sweeps
+//       the G x 5 shares nor folds nor decides. state: continue / stop (write x, r) / failed (the reducer gave up:
+//       leave without writing). The decision granule needs no ordering against any other granule: alpha, beta, state
+//       and tag travel in the one 16-B store, and the Ap granules a box reads beside it carry their own tags. Same
+//       bits as the other path: the same shares, the same fold, the same fused_decide, and the float alpha and beta
+//       every box would have computed (tests/test_gpu_resident_reducer.py);
+//     * otherwise (and always on a PEER shard) every box polls the G x 5 shares itself, as below;
 //   - a phase polls (sc1 loads, served past the non-coherent L1 / per-XCD L2) the G x 5 shares until all carry phase
 //     j - 1's tag, requests its ring's Ap granules, folds the shares, forms its own nodes, then checks each ring
 //     granule's tag under a workgroup vote; granules that had not landed are requested again. The vote can fail, so
@@ -35,8 +49,11 @@
 //     tag travel in one granule, so no ordering between granules is needed): observed on gfx950 for the dwordx4
 //     buffer accesses used here, not an architectural guarantee (DESIGN.md section 7 states the same for the mailboxes).
 // Every wait is bounded (kResMaxRounds poll rounds, then give_up): a workgroup that is never scheduled (the grid must be
-// co-resident, one per CU; resident_blocks_per_cu checks the occupancy) ends the solve with CWF_ERR_HIP instead of
-// hanging the GPU.
+// co-resident, one per CU; resident_blocks_per_cu checks the occupancy, and the reducer role runs only where G + 1
+// workgroups fit) ends the solve with CWF_ERR_HIP instead of hanging the GPU. With the role a reducer that gives up
+// publishes "failed", so every box leaves at its next poll; a box that gives up stores no shares, so the reducer gives
+// up one bound later and releases the rest. Every exit is workgroup-uniform (the votes; the reducer's timeout flag is
+// read behind its fold's barrier).
 //
 // Results: the per-node arithmetic is lattice_fused.inc's; only the grouping of the fp64 dot sums differs (boxes
 // instead of bricks), so alpha / beta differ in their last bits and the solve is tolerance-equal, not bit-equal, to the
@@ -59,6 +76,8 @@ constexpr uint32_t kResMaxRounds = 4000000u;  // poll rounds before a phase give
 constexpr uint32_t kResNone = 0xFFFFFFFFu;
 constexpr uint32_t kResOob = 0xFFFFFF00u;  // a byte offset past every range-checked buffer here, +32 included (no wrap)
 constexpr uint32_t kResGhost = 0x80000000u;  // a halo entry's source: a shard's ghost record (resident.cpp)
+// boxes from which the reducer role runs by default (the same-box A/B by box count)
+constexpr unsigned kResReducerMinBoxes = 56;
 constexpr int kResTypes = 12;  // boundary types one box's own nodes touch, at most (resident.cpp kResTypesHost)
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
@@ -83,6 +102,9 @@ struct ResArgs
     uint64_t *trace;    // diagnostic (CWF_RESIDENT_TRACE): per workgroup 8 s_memrealtime stamps of phase trace_j
     uint32_t trace_j;
     uint32_t reread;    // test (CWF_RESIDENT_REREAD): every phase j > 0 takes its first ring vote as failed once
+    uint32_t G;         // the plan's boxes (the grid has one workgroup more when the reducer role is on)
+    uint32_t reducer;   // 1: workgroup G is the reducer, the boxes poll its decision granule (never with MR)
+    uint32_t dec_off;   // byte offset in pub of the decision granules {alpha, beta, state, tag}, 128 B apart by phase parity
     // a PEER slab shard (nranks > 1): the send planes' Ap_(j-1) granules stored into the neighbours' mailboxes too (a
     // ghost is a ring entry like any other, only its granule's source differs), the ghosts' granules read from this
     // rank's, the rank totals stored to every rank and polled from this rank's
@@ -144,6 +166,109 @@ __device__ __forceinline__ void block_sum_lds(double v[K], double *red)
     }
 }
 
+// the decision granule's state word
+constexpr uint32_t kDecGo = 1u, kDecStop = 2u, kDecFailed = 3u;  // continue; stop and write x, r; leave without writing
+
+// The reducer role: workgroup G of a G + 1 grid owns no box. Per phase j >= 1 thread t < G polls workgroup t's five
+// share granules of phase j - 1 (each wave on its own: it runs its wave_sum as soon as its 64 workgroups' tags match;
+// the workgroup meets once, at block_sum_lds' barrier), the shares are folded in block_sum_lds' order, fused_decide
+// runs once, and one lane stores the decision granule every box polls. Thread 0 records ctl and the history. `red2` is
+// two fold buffers by phase parity (a wave may poll phase j + 1 while another still reads phase j's wave sums: the
+// reducer has no other barrier in its phase); `flag` three words by phase mod 3, a wave's timeout of that phase.
+__device__ __forceinline__ void resident_reduce(const ResArgs &ra, double *red2, int *flag)
+{
+    const uint32_t G = ra.G, tid = threadIdx.x;
+    const __amdgpu_buffer_rsrc_t rsh = sized_rsrc(ra.sh, 160u * G),
+                                 rdec = sized_rsrc(reinterpret_cast<const char *>(ra.pub) + ra.dec_off, 256u);
+    const CtlPre pre = ctl_prefetch(ra.ctl, 1u);
+    const bool tr = ra.trace != nullptr;
+    if (tid == 0)
+        flag[1] = 0;
+    lds_sync();
+    if (pre.active == 0)
+        return;
+    for (unsigned j = 1;; ++j)
+    {
+        const uint32_t par = (j - 1u) & 1u, want = ra.tag0 + j;
+        const bool st = tr && j == ra.trace_j;
+        uint64_t t0 = 0;
+        if (st)
+            t0 = __builtin_amdgcn_s_memrealtime();
+        if (tid == 0)
+            flag[(j + 1u) % 3u] = 0;
+        u32x4 g[kFusedShares];
+        uint32_t rounds = 0;
+        for (;; ++rounds)
+        {
+#pragma unroll
+            for (int q = 0; q < kFusedShares; ++q)
+                g[q] = ld4_sc1(rsh, tid < G ? 16u * ((par * G + tid) * kFusedShares + (uint32_t)q) : kResOob);
+            bool ok = true;
+#pragma unroll
+            for (int q = 0; q < kFusedShares; ++q)
+                ok = ok && (tid >= G || g[q].z == want);
+            if (__builtin_amdgcn_ballot_w64(!ok) == 0ull)
+                break;
+            if (rounds >= kResMaxRounds)
+            {
+                flag[j % 3u] = 1;
+                break;
+            }
+            __builtin_amdgcn_s_sleep(1);
+        }
+        double *red = red2 + (j & 1u) * (kFusedShares * (kResNT / 64));
+        if (st && (tid & 63u) == 0u)  // when this wave had seen its shares: the latest of the eight is stamp 1
+            reinterpret_cast<uint64_t *>(red2 + 2 * kFusedShares * (kResNT / 64))[tid >> 6] = __builtin_amdgcn_s_memrealtime();
+        double v[kFusedShares];
+#pragma unroll
+        for (int q = 0; q < kFusedShares; ++q)
+            v[q] = tid < G ? __hiloint2double((int)g[q].y, (int)g[q].x) : 0.0;
+        block_sum_lds<kResNT, kFusedShares>(v, red);  // the boxes' fold: the same totals, bit for bit
+        const bool failed = flag[j % 3u] != 0;
+        uint64_t t2 = 0;
+        if (st)
+            t2 = __builtin_amdgcn_s_memrealtime();
+        float alpha = 0.f, beta = 0.f;
+        bool go = false;
+        if (failed)
+        {
+            if (tid == 0)
+            {
+                ra.ctl->error = CWF_ERR_HIP;
+                ra.ctl->error_iter = (int)j;
+                ra.ctl->active = 0;
+            }
+        }
+        else
+        {
+            go = fused_decide(ra.ctl, ra.hist, j, pre, tid == 0, v, &alpha, &beta);
+            if (go && j - 1u == ra.max_it)  // max_iterations updates made
+                go = false;
+        }
+        // the publishing lane is wave 1's first: wave 0 has thread 0's ctl and history stores in front of it
+        if (tid == 64u)
+            st4_sc1(rdec, 128u * (j & 1u),
+                    u32x4{__float_as_uint(alpha), __float_as_uint(beta), failed ? kDecFailed : go ? kDecGo : kDecStop, want});
+        if (st && tid == 64u)
+            __hip_atomic_store(ra.trace + 8ull * G + 3, __builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+        if (st && tid == 0)
+        {
+            const uint64_t *ws = reinterpret_cast<const uint64_t *>(red2 + 2 * kFusedShares * (kResNT / 64));
+            uint64_t t1 = 0;
+            for (int w = 0; w < kResNT / 64; ++w)
+                t1 = ws[w] > t1 ? ws[w] : t1;
+            uint64_t *row = ra.trace + 8ull * G;
+            __hip_atomic_store(row + 0, t0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(row + 1, t1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(row + 2, t2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(row + 4, __builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        if (!go)
+            return;
+    }
+}
+
 template <bool SYM, class E, int NPT, int NPH, bool MR>
 __global__ __launch_bounds__(kResNT) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_pcg_resident(DevSys s, ResArgs ra, const float *__restrict__ coef)
 {
@@ -168,7 +293,13 @@ __global__ __launch_bounds__(kResNT) __attribute__((amdgpu_waves_per_eu(2, 2))) 
             return sreg[u][q];
     };
     const DevTiles &T = s.t;
-    const uint32_t G = gridDim.x, b = blockIdx.x, tid = threadIdx.x;
+    const uint32_t G = ra.G, b = blockIdx.x, tid = threadIdx.x;
+    if constexpr (!MR)
+        if (ra.reducer != 0u && b == G)  // the reducer: no box, no image; its fold buffers in the stencil table's LDS
+        {
+            resident_reduce(ra, reinterpret_cast<double *>(tcf), vote);
+            return;
+        }
     const uint4 hd = ra.hdr[b];
     const int PX = (int)hd.z, PXY = (int)hd.w;
     // diagnostic phase stamps (a uniform branch; no store unless CWF_RESIDENT_TRACE asked for them)
@@ -242,8 +373,8 @@ __global__ __launch_bounds__(kResNT) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         soff[o] = E::off[o][0] + E::off[o][1] * PX + E::off[o][2] * PXY;
     // halo entry h's Ap granule of the phase of parity par: another box's (pub), or a ghost's in the mailbox (a
     // shard; the out-of-range load of the other source returns 0, so the two combine by OR)
-    const auto request = [&](int h, uint32_t par, u32x4 &c) {
-        const bool gh = (hpub[h] & kResGhost) != 0u, v = hn[h] != kResNone;
+    const auto request = [&](int h, uint32_t par, u32x4 &c, bool need = true) {
+        const bool gh = (hpub[h] & kResGhost) != 0u, v = need && hn[h] != kResNone;
         c = ld4_sc1(rpub, v && !gh ? 16u * (par * ra.npub + hpub[h]) : kResOob);
         if constexpr (multi)
         {
@@ -292,6 +423,54 @@ __global__ __launch_bounds__(kResNT) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 #pragma unroll
                 for (int c = 0; c < 3; ++c)
                     ha[h][c] = 0.f;
+            }
+        }
+        else if (!MR && ra.reducer != 0u)
+        {
+            stamp(j, 0);
+            // the reducer's decision of phase j (it folded phase j - 1's shares of every workgroup): one granule
+            // {alpha, beta, state, tag}, every lane loading the same address, polled until it carries this phase's
+            // tag under the workgroup's vote (so the exit stays uniform). Bounded like every wait here
+            const __amdgpu_buffer_rsrc_t rdec = sized_rsrc(reinterpret_cast<const char *>(ra.pub) + ra.dec_off, 256u);
+            // Every round also requests the ring's Ap granules that have not landed yet (a lane whose granule carries
+            // the tag asks for nothing more): their owners stored them in their rows, before their shares, so they
+            // are here by the time the decision is, and the ring vote below passes without a load in its way
+            u32x4 dg;
+#pragma unroll
+            for (int h = 0; h < NPH; ++h)
+                w1[h] = u32x4{0u, 0u, 0u, ~want};
+            for (;; ++round)
+            {
+#pragma unroll
+                for (int h = 0; h < NPH; ++h)
+                {
+                    const bool need = w1[h].w != want;
+                    u32x4 c;
+                    request(h, par, c, need);
+                    w1[h] = need ? c : w1[h];
+                }
+                dg = ld4_sc1(rdec, 128u * (j & 1u));
+                if (all_ok(dg.w == want))
+                    break;
+                if (round >= kResMaxRounds)
+                {
+                    give_up();
+                    return;
+                }
+                __builtin_amdgcn_s_sleep(2);
+            }
+            stamp(j, 1);  // "decision seen": no fold and no decide span on a box (stamps 7 and 2 keep the old layout)
+            stamp(j, 7);
+            stamp(j, 2);
+            const uint32_t state = __builtin_amdgcn_readfirstlane(dg.z);
+            if (state == kDecFailed)  // the reducer gave up (it recorded the error): x, r are not written
+                return;
+            alpha = __uint_as_float(__builtin_amdgcn_readfirstlane(dg.x));
+            beta = __uint_as_float(__builtin_amdgcn_readfirstlane(dg.y));
+            if (state != kDecGo)
+            {
+                go = false;
+                break;
             }
         }
         else
@@ -375,7 +554,7 @@ __global__ __launch_bounds__(kResNT) __attribute__((amdgpu_waves_per_eu(2, 2))) 
                 }
             }
             stamp(j, 7);
-            go = fused_decide(ra.ctl, ra.hist, j, pre, v, &alpha, &beta);
+            go = fused_decide(ra.ctl, ra.hist, j, pre, b == 0 && tid == 0, v, &alpha, &beta);
             if (go && j - 1u == ra.max_it)  // max_iterations updates made (the host loop's last launch)
                 go = false;
             if (!go)
@@ -648,7 +827,7 @@ const char *resident_kernel_name(const DevSys &s, const ResidentPlan &rp)
 
 void launch_pcg_resident(cwf_hip_system *h, uint32_t max_it, hipStream_t st, hipEvent_t e0, hipEvent_t e1)
 {
-    const ResidentPlan &rp = h->res;
+    ResidentPlan &rp = h->res;
     ResArgs ra{};
     ra.ctl = h->ctl;
     ra.hist = h->hist;
@@ -669,37 +848,41 @@ void launch_pcg_resident(cwf_hip_system *h, uint32_t max_it, hipStream_t st, hip
         peer_resident_args(h, ra.pa);
     else
         ra.pa = ResPeerArgs{};
-    static uint64_t *trace = nullptr;  // diagnostic: CWF_RESIDENT_TRACE=path appends phase CWF_FUSED_TRACE_IT's stamps
-    static unsigned trace_n = 0;
+    // the reducer role: CWF_RESIDENT_REDUCER 0 never, 1 wherever eligible, unset from kResReducerMinBoxes boxes
+    const bool eligible = !rp.shard && rp.G >= 2u && rp.G + 1u <= rp.capacity && rp.dec_off != 0u;
+    const char *rdk = knob("CWF_RESIDENT_REDUCER");
+    ra.G = rp.G;
+    ra.reducer = eligible && (rdk ? rdk[0] == '1' : rp.G >= kResReducerMinBoxes) ? 1u : 0u;
+    ra.dec_off = rp.dec_off;
+    const unsigned grid = rp.G + ra.reducer;
+    // diagnostic: CWF_RESIDENT_TRACE=path appends phase CWF_FUSED_TRACE_IT's stamps, one row per workgroup (the
+    // reducer's last); the buffer is the handle's, on the handle's device
     const char *tp = knob("CWF_RESIDENT_TRACE");
-    if (tp && trace_n < rp.G)
-    {
-        if (trace)
-            (void)hipFree(trace);
-        trace = nullptr;
-        trace_n = hipMalloc(reinterpret_cast<void **>(&trace), 64ull * rp.G) == hipSuccess ? rp.G : 0u;
-    }
-    if (tp && trace)
+    if (tp && rp.trace_n < grid)
+        rp.trace_n = rp.trace.alloc(8ull * grid) == hipSuccess ? grid : 0u;
+    uint64_t *trace = tp && rp.trace_n >= grid ? rp.trace.get() : nullptr;
+    if (trace)
     {
         const char *at = knob("CWF_FUSED_TRACE_IT");
         ra.trace = trace;
         ra.trace_j = at ? (uint32_t)atoi(at) : 50u;
-        (void)hipMemsetAsync(trace, 0, 64ull * rp.G, st);
+        (void)hipMemsetAsync(trace, 0, 64ull * grid, st);
     }
     const char *rk = knob("CWF_RESIDENT_REREAD");  // tests/test_gpu_resident_handoff.py
     ra.reread = rk && rk[0] == '1' ? 1u : 0u;
-    launch_kernel(pick_resident(h->ds, resident_small(rp.npt, rp.nph), rp.shard).fn, rp.G, kResNT, rp.lds, st, e0, e1,
+    launch_kernel(pick_resident(h->ds, resident_small(rp.npt, rp.nph), rp.shard).fn, grid, kResNT, rp.lds, st, e0, e1,
                   h->ds, ra, h->ds.t.lcoef);
-    if (tp && trace)
+    if (trace)
     {
-        std::vector<uint64_t> v(8ull * rp.G);
+        std::vector<uint64_t> v(8ull * grid);
         if (hipStreamSynchronize(st) == hipSuccess &&
             hipMemcpy(v.data(), trace, v.size() * sizeof(uint64_t), hipMemcpyDeviceToHost) == hipSuccess)
             if (FILE *f = std::fopen(tp, "a"))
             {
-                std::fprintf(f, "# resident phase %u grid %u boxes %ux%ux%u\n", ra.trace_j, rp.G, rp.dims[0], rp.dims[1],
-                             rp.dims[2]);
-                for (unsigned b = 0; b < rp.G; ++b)
+                // ("reducer 1": the last row is the reducer's five stamps, the boxes' stamps 1, 7, 2 "decision seen")
+                std::fprintf(f, "# resident phase %u grid %u reducer %u boxes %ux%ux%u\n", ra.trace_j, grid, ra.reducer,
+                             rp.dims[0], rp.dims[1], rp.dims[2]);
+                for (unsigned b = 0; b < grid; ++b)
                 {
                     std::fprintf(f, "%u", b);
                     for (int i = 0; i < 8; ++i)
