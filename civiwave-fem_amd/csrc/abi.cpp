@@ -671,7 +671,7 @@ static int upload_incidence(cwf_hip_system *h, const cwf_system_desc *d)
     return up.st;
 }
 
-// structured Kuhn block: the stencil blocks, the plane table and one row value per node (lattice.inc); the
+// structured Kuhn block: the stencil blocks, the plane table and one row value per node (lattice.hip); the
 // per-class preconditioner tables when the lumped mass is a function of the boundary type
 static int layout_lattice(cwf_hip_system *h, const cwf_system_desc *d, Lattice &lat)
 {
@@ -882,7 +882,7 @@ static int alloc_scratch(cwf_hip_system *h, const cwf_system_desc *d, const std:
     Uploader up{h};
     for (float **v : {&h->x, &h->r, &h->p, &h->p2, &h->p3, &h->p4, &h->z, &h->Ap, &h->rhs, &h->tmp})
         *v = up.alloc<float>(D);
-    if (s.t.lat && s.t.lcls)  // the fused lattice iteration's second r / Ap and its shares (lattice_fused.inc)
+    if (s.t.lat && s.t.lcls)  // the fused lattice iteration's second r / Ap and its shares (lattice_fused.hip)
     {
         h->r2 = up.alloc<float>(D);
         h->ap2 = up.alloc<float>(D);
@@ -1185,7 +1185,7 @@ int cwf_hip_system_keff_traffic(const cwf_hip_system *h, uint64_t *layout_bytes,
             return 0;
         }
         if (sch == PcgSchedule::Fused || sch == PcgSchedule::FusedPeer)
-        {  // the fused iteration (lattice_fused.inc): per owned node r_(j-1), Ap_(j-1), p_(j-1), the class byte and x
+        {  // the fused iteration (lattice_fused.hip): per owned node r_(j-1), Ap_(j-1), p_(j-1), the class byte and x
            // read, r_j, p_j, Ap_j and x written; the mass of the shell's nodes (the strict interior's is one value when lmu)
             *layout_bytes = (uint64_t)s.Nown * (4 * 12 + 1 + 4 * 12) + 4ull * (s.t.lmu ? s.t.lnshell : s.Nown);
             return 0;

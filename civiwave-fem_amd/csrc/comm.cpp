@@ -284,7 +284,7 @@ int fast_pcg_iteration_group(const std::vector<cwf_hip_system *> &g, const std::
     return comm_exchange(g, {Gather{&cwf_hip_system::g_rrz, 2}}, g[0]->sharded() ? &cwf_hip_system::z : nullptr);
 }
 
-// ---- the sharded fused iteration (lattice_fused.inc on slab shards) ---------------------------------------------
+// ---- the sharded fused iteration (lattice_fused.hip on slab shards) ---------------------------------------------
 // One launch and one exchange step per PCG iteration: launch j forms r_j, z_j, p_j, x_j for its owned rows and (from
 // the received Ap_(j-1) rows and its own stored r_(j-1), p_(j-1)) the same r_j, p_j its neighbours form for its ghost
 // rows, so only Ap_j's ghost rows and the five rank totals cross ranks: {rank totals} all-gather + Ap halo, ONE RCCL

@@ -89,7 +89,7 @@ struct DevTiles
     // MALL (abi.cpp: < 4M tets)
     int wt_part = 0;
     float *part = nullptr;                    // [3*total] tile-node partial sums, node-major (scratch)
-    // structured Kuhn block (lattice.cpp, lattice.inc): k_keff_lattice; part is one row value per node
+    // structured Kuhn block (lattice.cpp, lattice.hip): k_keff_lattice; part is one row value per node
     // (node_part_off[n] = n), ntiles = lnwork
     int lat = 0;
     uint32_t lnx = 0, lny = 0, lnz = 0;  // lattice nodes per axis (a shard: its local planes)
@@ -126,7 +126,7 @@ struct DevTiles
     uint4 *lcinv6 = nullptr;         // [kLatClasses]
     float *lcinv9 = nullptr;         // [9 kLatClasses]
     float4 *lcz = nullptr;           // [2 kLatClasses] the same inverse unpacked, {a00 a01 a02 a11} {a12 a22 0 0}:
-                                     // loaded unconditionally in the K_eff prologue (lattice.inc, ZR)
+                                     // loaded unconditionally in the K_eff prologue (lattice.hip, ZR)
 };
 static_assert(sizeof(DevTiles) == 352, "llayers fills padding: the K_eff kernels' argument layout is unchanged");
 // lattice work items for planes [lk0, lk1) (lattice.cpp): sets lnbx, lnby, lL, lnwork, ntiles
@@ -184,7 +184,7 @@ struct GroupTiles
 int build_group_tiles(const cwf_system_desc *d, GroupTiles &out, uint32_t nt, uint32_t max_nodes,
                       uint32_t slot_budget, bool order_lanes = true);
 
-// Structured Kuhn blocks (lattice.cpp, lattice.inc): the 15 node-pair offsets of a Kuhn node's row (the node,
+// Structured Kuhn blocks (lattice.cpp, lattice.hip): the 15 node-pair offsets of a Kuhn node's row (the node,
 // +-x, +-y, +-z, +-(1,1,0), +-(1,0,1), +-(0,1,1), +-(1,1,1)) and the 46 corner pairs (c, c') of one cell that share
 // a tet, with the offset index of c' - c
 constexpr int kLatOffsets = 15, kLatPairs = 46;
@@ -321,7 +321,7 @@ struct Ctl
     int error;       // cwf_status (0 = none)
     int error_iter;  // iteration index for the error context
     double rho2[2];  // FAST: rho by iteration parity (written by one kernel, read by the next)
-    double alpha_h[kXLag];  // FAST: alpha of iteration j at [j % kXLag] (the lazy x update, spmv_tiles.hip)
+    double alpha_h[kXLag];  // FAST: alpha of iteration j at [j % kXLag] (the lazy x update, pcg_update.hip)
 };
 
 // The schedule of a PCG solve (schedule.cpp decides it, once per handle; DESIGN.md section 3 "Which schedule runs")
@@ -329,7 +329,7 @@ enum class PcgSchedule
 {
     Parity,     // the reference's kernel sequence, fold orders included
     TwoKernel,  // FAST: a K_eff pass and an update pass per iteration
-    Fused,      // one launch per iteration (lattice_fused.inc); shards: one exchange step after each launch
+    Fused,      // one launch per iteration (lattice_fused.hip); shards: one exchange step after each launch
     FusedPeer,  // ... whose launches exchange through the PEER mailboxes themselves
     Resident,   // one launch per solve (resident.hip)
 };
@@ -401,7 +401,7 @@ struct cwf_hip_system
     // Ap is scratch (apply_keff staging, PARITY's K p, the prologues' K x); FAST PCG never reads it
     float *x = nullptr, *r = nullptr, *p = nullptr, *z = nullptr, *Ap = nullptr, *rhs = nullptr, *tmp = nullptr;
     float *p2 = nullptr, *p3 = nullptr, *p4 = nullptr;  // FAST: p_j lives in {p, p2, p3, p4}[(j + 1) % 4]
-    // the fused lattice iteration (lattice_fused.inc): r and Ap by launch parity (r_j in {r2, r}[j & 1], Ap_j in
+    // the fused lattice iteration (lattice_fused.hip): r and Ap by launch parity (r_j in {r2, r}[j & 1], Ap_j in
     // {Ap, ap2}[j & 1]) and the launches' five shares per workgroup, [2][5][lnwork]
     float *r2 = nullptr, *ap2 = nullptr;
     double *fsh = nullptr;
@@ -565,7 +565,7 @@ void fast_update_pcg(cwf_hip_system *h, const float *rhs, unsigned it, hipStream
 void fast_check_pcg(cwf_hip_system *h, unsigned it, hipStream_t st);
 void fast_flush_x(cwf_hip_system *h, const float *rhs, hipStream_t st);  // the lazy x terms still pending
 void fast_tiles_pcg_dry(cwf_hip_system *h, unsigned abl, int reps, hipStream_t st);
-// the fused lattice iteration (lattice_fused.inc): one launch per PCG iteration on a structured block
+// the fused lattice iteration (lattice_fused.hip): one launch per PCG iteration on a structured block
 unsigned pcg_lattice_launch_grid(const DevSys &s, unsigned cap);  // its grid, of at most cap workgroups
 void fast_fused_init(cwf_hip_system *h, const float *rhs, double rel_tol, hipStream_t st, bool launch0 = true);
 void fast_fused_iteration(cwf_hip_system *h, unsigned it, hipStream_t st, hipEvent_t e0 = nullptr,
@@ -578,7 +578,7 @@ void fast_fused_rank_totals(cwf_hip_system *h, unsigned j, hipStream_t st);
 const double *fast_fused_shares(const cwf_hip_system *h, unsigned j, unsigned *stride, unsigned *count);
 void fast_fused_cls_out(cwf_hip_system *h, hipStream_t st);  // owned class bytes -> tmp (x components)
 void fast_fused_cls_in(cwf_hip_system *h, hipStream_t st);   // ghost class bytes <- tmp
-constexpr size_t kFusedSlotHost = 8;  // doubles per rank of the gathered fused totals (lattice_fused.inc kFusedSlot)
+constexpr size_t kFusedSlotHost = 8;  // doubles per rank of the gathered fused totals (lattice_fused.hip kFusedSlot)
 // comm.cpp: the sharded fused iteration (one launch + one exchange: the rank totals and the Ap halo; sch FusedPeer: the
 // launches exchange themselves)
 int sharded_fused_init(const std::vector<cwf_hip_system *> &g, const std::vector<const float *> &rhs, double rel_tol,
@@ -597,11 +597,61 @@ uint64_t resident_offchip_bytes(const cwf_hip_system *h);  // per phase: halo re
 int sharded_resident_init(const std::vector<cwf_hip_system *> &g, const std::vector<const float *> &rhs, double rel_tol);
 int sharded_fused_end(const std::vector<cwf_hip_system *> &g, PcgSchedule sch);  // after the last launch (FusedPeer: the epochs)
 
+// ---- the FAST element passes: one kernel family per unit (spmv_tiles.hip: the tet tiles; tiles_groups.hip, tiles_hex.hip,
+// lattice.hip), each with its picker next to its kernels; fast_dispatch.hip chooses the family of a handle ----
+// the PCG-mode arguments of an element pass (all zero on the apply path)
+struct PcgPassArgs
+{
+    const float *z;           // z (PCG); x holds p_old
+    Ctl *ctl;
+    double *part_dot;         // out: per-tile p.Ap share
+    const double *prr, *prz;  // in: folded {r.r, r.z} of the previous update (per rank)
+    unsigned nupd;
+    unsigned stride;
+    unsigned it;
+    double *hist;
+    unsigned abl;  // diagnostic ablation bits (ablate(); the dry-run bit 32), 0 in solves
+    float *pnew;   // out (PCG): the owner slot of every tile node stores the new p = z + beta p_old here
+};
+// per family: the launch of the handle's instantiation (pcg: the PCG loop's, else the apply path's, sanitised or not),
+// the PCG loop's instantiation by name, and (persistent tile kernels) its XCD-aware grid over the handle's tiles
+void launch_tet_tiles(const DevSys &s, const float *x, const PcgPassArgs &pa, bool pcg, bool sanitize, hipStream_t st,
+                      hipEvent_t e0, hipEvent_t e1);  // t.pipe: k_keff_tiles_pipe, else k_keff_tiles
+const char *tet_tiles_kernel_name(const DevSys &s);
+unsigned tet_tiles_pipe_grid(const DevSys &s);
+void launch_groups(const DevSys &s, const float *x, const PcgPassArgs &pa, bool pcg, bool sanitize, hipStream_t st,
+                   hipEvent_t e0, hipEvent_t e1);
+const char *groups_kernel_name(const DevSys &s);
+unsigned groups_pipe_grid(const DevSys &s);
+void launch_hex_tiles(const DevSys &s, const float *x, const PcgPassArgs &pa, bool pcg, bool sanitize, hipStream_t st,
+                      hipEvent_t e0, hipEvent_t e1);
+const char *hex_tiles_kernel_name(const DevSys &s);
+unsigned hex_tiles_pipe_grid(const DevSys &s);
+void launch_lattice(const DevSys &s, const float *x, const PcgPassArgs &pa, bool pcg, bool sanitize, hipStream_t st,
+                    hipEvent_t e0, hipEvent_t e1);  // t.llayers: k_keff_lattice_layered, else k_keff_lattice
+const char *lattice_kernel_name(const DevSys &s);
+
+inline unsigned grid_for(uint32_t n, uint32_t b) { return (n + b - 1) / b; }
+
+// FAST search directions rotate over four buffers: p_j (iteration j's) lives in {p, p2, p3, p4}[(j + 1) % 4],
+// so iteration `it` reads p_old from [it % 4] (the prologue's p is in p) and writes the new p to
+// [(it + 1) % 4], and the last kXLag directions stay readable for the lazy x update
+inline float *fast_p_buf(cwf_hip_system *h, unsigned k)
+{
+    float *const b[4] = {h->p, h->p2, h->p3, h->p4};
+    return b[k % 4u];
+}
+inline float *fast_p_old(cwf_hip_system *h, unsigned it) { return fast_p_buf(h, it); }
+inline float *fast_p_new(cwf_hip_system *h, unsigned it) { return fast_p_buf(h, it + 1u); }
+static_assert(kXLag <= 4, "p_(it - lag + 1) .. p_it must still be in the four rotating buffers");
+
 unsigned fast_tile_blocks(const DevSys &s);
 unsigned fast_pipe_grid(const DevSys &s);
-unsigned fast_update_blocks(const DevSys &s, bool flush);
-unsigned fast_rrz_shares(const DevSys &s, unsigned it);  // the {r.r, r.z} shares iteration it's update pass writes  // grid of update pass (lazy-x iteration or not)
-// sharded FAST PCG (comm.cpp orchestrates, spmv_tiles.hip / kernels_fast.hip launch)
+// pcg_update.hip
+unsigned fast_update_blocks(const DevSys &s, bool flush);  // grid of the update pass (lazy-x iteration or not)
+unsigned fast_rrz_shares(const DevSys &s, unsigned it);  // the {r.r, r.z} shares iteration it's update pass writes
+bool x_flush_iter(unsigned j);  // iteration j's update applies the lazy x terms
+// sharded FAST PCG (comm.cpp orchestrates; fast_dispatch.hip, pcg_update.hip and kernels_fast.hip launch)
 // post.hip: derived fields (derived_fields.cpp:139-211) -> f32 [13 E] / [13 N] (either may be NULL)
 void derived_fields(cwf_hip_system *h, const float *u, float *elem_out, float *node_out, hipStream_t st);
 bool fast_direct_fold(const cwf_hip_system *h);  // unsharded: consumers fold per-workgroup shares
@@ -637,7 +687,7 @@ struct PeerFold
 int peer_exchange(cwf_hip_system *h, std::initializer_list<Gather> gathers, const std::vector<float *> &vecs,
                   const PeerFold *fold = nullptr);
 void peer_release(cwf_hip_comm *cm);
-// The fused lattice iteration's exchange inside its own launch (PEER only; lattice_fused.inc): launch j of a solve
+// The fused lattice iteration's exchange inside its own launch (PEER only; lattice_fused.hip): launch j of a solve
 // pushes its Ap send rows (whole owned planes) straight into the neighbours' receive areas and, from its last
 // workgroup, the rank totals into every rank's gather area and epoch ebase + j + 1 into every peer's flag; launch
 // j + 1 waits for every peer's epoch ebase + j in its prologue. Launch arguments (this launch's parities):

@@ -8,7 +8,6 @@ namespace cwf
 namespace
 {
 constexpr int kBlock = 256;
-inline unsigned grid_for(uint32_t n) { return (n + kBlock - 1) / kBlock; }
 
 // a node's three f32: one 12-B access (4-B aligned)
 struct alignas(4) F3
@@ -32,7 +31,7 @@ __device__ __forceinline__ float safe_cast(double v)
 }
 
 // One step of the scheme per node. FOLD: the node's row of y = K w is folded here from the partials the FAST tile
-// launch left in s.t.part, in k_keff_finalize's order and arithmetic (spmv_tiles.hip; s carries the scalars (1, 0)),
+// launch left in s.t.part, in k_keff_finalize's order and arithmetic (fast_dispatch.hip; s carries the scalars (1, 0)),
 // so the bits are cwf_hip_apply_keff's and no finalize pass runs; else y holds the rows (PARITY). PATTERN: f_n from
 // the f64 load pattern. DAMP: beta_R != 0, the operator's next input is its own buffer.
 // Traffic per node, FOLD, no pattern, undamped: u v f read and u v written (5 x 12 B), the partial run (12 B on a
@@ -234,14 +233,14 @@ void launch_update(const DevSys &s, const ExplicitPass &a, hipStream_t st)
     if (a.dslot)
     {
         if (a.w != a.u)
-            k_explicit_update<FOLD, PATTERN, true, true><<<grid_for(s.N), kBlock, 0, st>>>(s, a);
+            k_explicit_update<FOLD, PATTERN, true, true><<<grid_for(s.N, kBlock), kBlock, 0, st>>>(s, a);
         else
-            k_explicit_update<FOLD, PATTERN, false, true><<<grid_for(s.N), kBlock, 0, st>>>(s, a);
+            k_explicit_update<FOLD, PATTERN, false, true><<<grid_for(s.N, kBlock), kBlock, 0, st>>>(s, a);
     }
     else if (a.w != a.u)
-        k_explicit_update<FOLD, PATTERN, true, false><<<grid_for(s.N), kBlock, 0, st>>>(s, a);
+        k_explicit_update<FOLD, PATTERN, true, false><<<grid_for(s.N, kBlock), kBlock, 0, st>>>(s, a);
     else
-        k_explicit_update<FOLD, PATTERN, false, false><<<grid_for(s.N), kBlock, 0, st>>>(s, a);
+        k_explicit_update<FOLD, PATTERN, false, false><<<grid_for(s.N, kBlock), kBlock, 0, st>>>(s, a);
 }
 }  // namespace
 
@@ -259,25 +258,25 @@ void explicit_update(const DevSys &s, const ExplicitPass &a, hipStream_t st)
 void explicit_operator_input(uint32_t N, const float *u, const float *v, double beta, float *w, hipStream_t st)
 {
     if (N)
-        k_explicit_input<<<grid_for(N), kBlock, 0, st>>>(N, u, v, beta, w);
+        k_explicit_input<<<grid_for(N, kBlock), kBlock, 0, st>>>(N, u, v, beta, w);
 }
 
 void explicit_power_start(uint32_t N, const uint32_t *mask, float *x, hipStream_t st)
 {
     if (N)
-        k_power_start<<<grid_for(N), kBlock, 0, st>>>(N, mask, x);
+        k_power_start<<<grid_for(N, kBlock), kBlock, 0, st>>>(N, mask, x);
 }
 
 void explicit_power_z(uint32_t N, const float *mass, const uint32_t *mask, const float *y, float *z, hipStream_t st)
 {
     if (N)
-        k_power_z<<<grid_for(N), kBlock, 0, st>>>(N, mass, mask, y, z);
+        k_power_z<<<grid_for(N, kBlock), kBlock, 0, st>>>(N, mass, mask, y, z);
 }
 
 void explicit_power_scale(uint32_t D, const float *z, const double *num_den, float *x, double *lam, hipStream_t st)
 {
     if (D)
-        k_power_scale<<<grid_for(D), kBlock, 0, st>>>(D, z, num_den, x, lam);
+        k_power_scale<<<grid_for(D, kBlock), kBlock, 0, st>>>(D, z, num_den, x, lam);
 }
 
 }  // namespace cwf

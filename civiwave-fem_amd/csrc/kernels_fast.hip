@@ -2,7 +2,7 @@
 // decomposition (one partial per 256-DOF block, fixed-order tree fold) so results are
 // deterministic run to run; tolerance-checked against the oracle instead of bit-checked.
 // The per-iteration kernels (K_eff tiles with fused p-update/alpha, and the fused x/r/z/p
-// update with beta) live in spmv_tiles.hip.
+// update with beta) live in the element-pass units (spmv_tiles.hip, tiles_*.hip, lattice.hip) and pcg_update.hip.
 #include "cwf_internal.hpp"
 
 namespace cwf
@@ -122,8 +122,6 @@ __global__ __launch_bounds__(kBlock) void k_fast_rho(Ctl *ctl, const double *__r
         ctl->active = 0;
     }
 }
-
-inline unsigned grid_for(uint32_t n, uint32_t b) { return (n + b - 1) / b; }
 
 }  // namespace
 

@@ -1345,8 +1345,6 @@ __global__ __launch_bounds__(kBlock) void k_p_update(DevSys s, const float *__re
     }
 }
 
-inline unsigned grid_for(uint32_t n, uint32_t b) { return (n + b - 1) / b; }
-
 inline bool knob_off(const char *name)
 {
     const char *v = knob(name);

@@ -35,10 +35,10 @@ inline constexpr Knob kKnobs[] = {
     {"CWF_RESIDENT", "0: a structured block that fits on chip runs the launch-per-iteration schedules instead of the "
                      "resident one-launch solve (resident.hip; also off whenever CWF_FUSED is set)"},
     {"CWF_FUSED", "0: structured blocks run the two-kernel iteration (k_keff_lattice + k_pcg_update_tiles) instead of "
-                  "the fused one-launch iteration (lattice_fused.inc); 2: fused also where the grid walks the work items "
+                  "the fused one-launch iteration (lattice_fused.hip); 2: fused also where the grid walks the work items "
                   "persistently (default: fused only where one round of workgroups covers them)"},
     {"CWF_PEER_FUSED", "0: a PEER shard's fused iteration exchanges through a k_peer_step launch after each fused launch "
-                       "instead of inside the launch (lattice_fused.inc fused_peer_wait / fused_peer_publish)"},
+                       "instead of inside the launch (lattice_fused.hip fused_peer_wait / fused_peer_publish)"},
     {"CWF_FUSED_TRACE", "path (ablation build only): per-workgroup phase stamps of one fused launch per solve, appended"},
     {"CWF_RESIDENT_TRACE", "path: per-workgroup phase stamps of one phase (CWF_FUSED_TRACE_IT) of every resident solve, "
                            "appended (tools/resident_trace.py)"},

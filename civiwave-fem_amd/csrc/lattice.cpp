@@ -9,7 +9,7 @@
 // by node pair, an interior node's row is 15 3x3 blocks (the Kuhn edges: +-x, +-y, +-z, +-(1,1,0), +-(1,0,1),
 // +-(0,1,1), +-(1,1,1), and the node itself):
 //   (K u)_n = sum_d S_d u_(n+d),  S_d = sum over the cell corners c with c + d a corner of Kc[c][c + d].
-// The kernel (lattice.inc) forms it in difference form, sum_(d != 0) S_d (u_(n+d) - u_n) (rigid translations
+// The kernel (lattice.hip) forms it in difference form, sum_(d != 0) S_d (u_(n+d) - u_n) (rigid translations
 // are in the null space of every row), so each fp32 term is strain-sized as in the element loop. A node on the
 // block's surface misses some of its 8 cells: its row is formed in the cell form instead, each existing cell's
 // blocks Kc[c][c'] on the same differences. The regrouping changes the fp32 summation order only (FAST's

@@ -1,6 +1,5 @@
-// lattice.inc -- k_keff_lattice, the FAST K_eff of a structured Kuhn block (lattice.cpp), included by
-// spmv_tiles.hip (it shares residual_step, block_sum, store3, pk_fma and the PcgArgs contract of the tiles
-// kernels).
+// lattice.hip -- k_keff_lattice and k_keff_lattice_layered, the FAST K_eff of a structured Kuhn block (lattice.cpp).
+// They share residual_step, block_sum, load3 and the PcgArgs contract of the tiles kernels (fast_common.hpp).
 //
 // Node-centric and HBM-streaming: every owned node's row is the Kuhn stencil of its neighbours, so no element
 // record, partial run or fold exists; per node the kernel reads z and p_old (PCG; x for apply_keff) and the mass,
@@ -34,6 +33,12 @@
 // move address past the end of a range-checked buffer descriptor instead: such a load returns 0 and such a store
 // is dropped, without memory traffic. coef and plane are restrict kernel arguments (scalar loads): a vector load
 // issued after the prefetch and consumed before it would drain it too (vmcnt retires in order).
+#include "fast_common.hpp"
+
+namespace cwf
+{
+namespace
+{
 // one plane of the brick's halo region in registers: entries e = threadIdx.x + kLatNT u (u = 0, 1; e < PLANE)
 struct LatFill
 {
@@ -340,3 +345,23 @@ Pick<LayeredFn> pick_lattice_layered(const DevSys &s, bool pcg, bool sanitize)
         },
         pcg, sanitize, s.t.lhex != 0, s.t.lpstride != 0);
 }
+}  // namespace
+
+void launch_lattice(const DevSys &s, const float *x, const PcgPassArgs &pa, bool pcg, bool sanitize, hipStream_t st,
+                    hipEvent_t e0, hipEvent_t e1)
+{
+    const DevTiles &t = s.t;
+    if (t.llayers)
+        launch_kernel(pick_lattice_layered(s, pcg, sanitize).fn, t.lnwork, kLatNT, 0, st, e0, e1, s, x, PcgArgs{pa},
+                      t.lcoef, t.lplane, lattice_layers(t));
+    else
+        launch_kernel(pick_lattice(s, pcg, sanitize).fn, t.lnwork, kLatNT, 0, st, e0, e1, s, x, PcgArgs{pa}, t.lcoef,
+                      t.lplane);
+}
+
+const char *lattice_kernel_name(const DevSys &s)
+{
+    return s.t.llayers ? pick_lattice_layered(s, true, false).name : pick_lattice(s, true, false).name;
+}
+
+}  // namespace cwf

@@ -1,4 +1,4 @@
-// lattice_body.inc -- the body of k_keff_lattice and of k_keff_lattice_layered (lattice.inc includes it once in each,
+// lattice_body.inc -- the body of k_keff_lattice and of k_keff_lattice_layered (lattice.hip includes it once in each,
 // so the one-material kernels compile from exactly the statements they always had). In scope: the kernel's
 // arguments s, x, pa, coef, plane and lay, and MODE, SANITIZE, SYM, E, MU, ZR, AFF, LAY as compile-time constants.
 // LAY (a layered block): the stencil blocks of a row are those of its plane's class: lay[k] & 0xFFFF times the table

@@ -1,4 +1,4 @@
-// lattice_common.hpp -- what the structured-block kernels share across translation units (spmv_tiles.hip: the
+// lattice_common.hpp -- what the structured-block kernels share across translation units (lattice.hip, lattice_fused.hip: the
 // K_eff / fused-iteration kernels; resident.hip: the resident solve): vector types, the control-block reads, the
 // lattice element kinds and their class-table preconditioner, and the fused iteration's per-node arithmetic and
 // scalar decision. Device code (and the names a picker needs of it), in an anonymous namespace per including unit.

@@ -1,5 +1,6 @@
-// lattice_fused.inc -- k_pcg_lattice: the FAST PCG iteration of a structured block in ONE launch (included by
-// spmv_tiles.hip after lattice.inc, whose brick machinery it shares).
+// lattice_fused.hip -- k_pcg_lattice: the FAST PCG iteration of a structured block in ONE launch (the brick scheme of
+// lattice.hip's k_keff_lattice), with its host driver (fast_fused_*, pcg_lattice_*), the diagnostic launch trace of the
+// ablation build and a shard's class-byte exchange.
 //
 // The reference's loop (pcg.cpp:840-901) has two dependent global reductions per iteration: p.Ap for alpha, then
 // r.z for beta, hence two kernels (k_keff_lattice, k_pcg_update_tiles) and two scalar hand-offs. Here launch j
@@ -28,7 +29,16 @@
 // Entry mapping: thread t forms the interior entry of its own column (the node whose row it computes) and threads
 // 0 .. 83 the 84 entries of the brick's one-node halo ring, so the thread that forms a node's z and class is the
 // one that needs them for the dots of its row (three planes of them in registers).
+#include <algorithm>
+#include <cstdio>
+#include <vector>
 
+#include "fast_common.hpp"
+
+namespace cwf
+{
+namespace
+{
 struct FusedArgs
 {
     Ctl *ctl;
@@ -852,3 +862,193 @@ void launch_pcg_lattice(const DevSys &s, const FusedArgs &fa, hipStream_t st, hi
     launch_kernel(pick_pcg_lattice(s, fa.grid < s.t.lnwork).fn, fa.grid, kLatNT, 0, st, e0, e1, s, fa, s.t.lcoef,
                   s.t.lplane);
 }
+}  // namespace
+
+// ---- the host driver ----------------------------------------------------------------------------------------
+unsigned pcg_lattice_resident_count(const DevSys &s) { return lattice_resident_count(s); }
+
+unsigned pcg_lattice_launch_grid(const DevSys &s, unsigned cap) { return pcg_lattice_grid(s, cap); }
+
+const char *pcg_lattice_kernel_name(const DevSys &s, unsigned grid) { return pick_pcg_lattice(s, grid < s.t.lnwork).name; }
+
+namespace
+{
+#if CWF_ABLATION
+// diagnostic (ablation build): CWF_FUSED_TRACE=path appends the stamps of one launch (CWF_FUSED_TRACE_IT, default
+// 50) of every solve: one line per workgroup "wg kind|planes<<8 hw_id xcc_id t0 t1 t2 t3 t4" (s_memrealtime, 100 MHz)
+uint64_t *g_ftrace = nullptr;
+unsigned g_ftrace_n = 0;
+uint64_t *fused_trace_buffer(const cwf_hip_system *h)
+{
+    if (!knob("CWF_FUSED_TRACE"))
+        return nullptr;
+    if (g_ftrace_n < h->sched.grid)
+    {
+        if (g_ftrace)
+            (void)hipFree(g_ftrace);
+        g_ftrace = nullptr;
+        if (hipMalloc(reinterpret_cast<void **>(&g_ftrace), 128ull * h->sched.grid) != hipSuccess)
+            return nullptr;
+        g_ftrace_n = h->sched.grid;
+    }
+    return g_ftrace;
+}
+void fused_trace_dump(cwf_hip_system *h, unsigned it, hipStream_t st)
+{
+    const char *path = knob("CWF_FUSED_TRACE"), *at = knob("CWF_FUSED_TRACE_IT");
+    if (!path || !g_ftrace || it != (unsigned)(at ? atoi(at) : 50))
+        return;
+    std::vector<uint64_t> v(16ull * h->sched.grid);
+    if (hipStreamSynchronize(st) != hipSuccess ||
+        hipMemcpy(v.data(), g_ftrace, v.size() * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess)
+        return;
+    if (FILE *f = std::fopen(path, "a"))
+    {
+        std::fprintf(f, "# launch %u grid %u\n", it + 1u, h->sched.grid);
+        for (unsigned b = 0; b < h->sched.grid; ++b)
+        {
+            const uint64_t *w = &v[16ull * b];
+            std::fprintf(f, "%u %llu %llu %llu %llu %llu %llu %llu %llu %llu %llu %llu %llu %llu %llu\n", b,
+                         (unsigned long long)w[5], (unsigned long long)w[6], (unsigned long long)w[7],
+                         (unsigned long long)w[0], (unsigned long long)w[1], (unsigned long long)w[2],
+                         (unsigned long long)w[3], (unsigned long long)w[4], (unsigned long long)w[8],
+                         (unsigned long long)w[9], (unsigned long long)w[10], (unsigned long long)w[11],
+                         (unsigned long long)w[12], (unsigned long long)w[13]);
+        }
+        std::fclose(f);
+    }
+}
+#endif
+// launch j of the fused iteration: r_j -> {r2, r}[j & 1], Ap_j -> {Ap, ap2}[j & 1], p_j -> p[(j + 1) % 4], shares
+// -> fsh[j & 1]; launch j reads launch j - 1's (launch 0 reads r from r and Ap from ap2, zeroed at init)
+FusedArgs fused_args(cwf_hip_system *h, unsigned j)
+{
+    const unsigned W = h->ds.t.lnwork;
+    float *const R[2] = {h->r2, h->r}, *const A[2] = {h->Ap, h->ap2};
+    FusedArgs fa{};
+    fa.ctl = h->ctl;
+    fa.sstride = W;
+    fa.grid = h->sched.grid;
+    if (h->sharded())  // every rank folds the all-gathered rank totals, in rank order
+    {
+        fa.sin = h->g_fsh;
+        if (h->sched.launch == PcgSchedule::FusedPeer)  // PEER in-kernel: the totals land in the mailbox's gather area (previous epoch)
+        {
+            const double *gp = nullptr;
+            peer_fused_args(h, j, fa.pe, &gp);
+            fa.px = 1;
+            fa.sin = gp;
+        }
+        fa.nin = (unsigned)h->nranks;
+        fa.sin_stride = 1;
+        fa.sis = kFusedSlot;
+    }
+    else
+    {
+        fa.sin = h->fsh + (size_t)((j + 1u) & 1u) * 5 * W;
+        fa.nin = h->sched.grid;
+        fa.sin_stride = W;
+        fa.sis = 1;
+    }
+    fa.sout = h->fsh + (size_t)(j & 1u) * 5 * W;
+    fa.j = j;
+    fa.hist = h->hist;
+    fa.rin = R[(j + 1u) & 1u];
+    fa.rout = R[j & 1u];
+    fa.ain = A[(j + 1u) & 1u];
+    fa.aout = A[j & 1u];
+    fa.pin = fast_p_buf(h, j);
+    fa.pout = fast_p_buf(h, j + 1u);
+    fa.x = h->x;
+    fa.trace = nullptr;
+#if CWF_ABLATION
+    fa.trace = fused_trace_buffer(h);
+#endif
+    return fa;
+}
+}  // namespace
+
+void fast_fused_init(cwf_hip_system *h, const float *rhs, double rel_tol, hipStream_t st, bool launch0)
+{
+    const DevSys &s = h->ds;
+    const uint32_t nbD = fast_dot_blocks(s.D);
+    fast_block_inverse(h, st);
+    fast_keff(h, h->x, h->Ap, true, nullptr, nullptr, st);
+    launch_init_residual(h, rhs, st);  // r_0 = rhs - A x (Dirichlet: x = rhs, r = 0) into h->r
+    fast_dot(rhs, rhs, nullptr, s.D, h->part0, nullptr, st);
+    fast_dot(h->r, h->r, nullptr, s.D, h->part1, nullptr, st);
+    fast_init_scalars_strided(h, h->part0, h->part1, nbD, 1u, rel_tol, st);
+    // launch 0 reads p_(-1) and Ap_(-1) (times beta = alpha = 0): zero, so no stale non-finite value enters
+    if (launch0)  // (the resident solve runs its phase 0 itself)
+        fast_fused_launch0(h, st);
+}
+
+void fast_fused_iteration(cwf_hip_system *h, unsigned it, hipStream_t st, hipEvent_t e0, hipEvent_t e1)
+{
+    launch_pcg_lattice(h->ds, fused_args(h, it + 1u), st, e0, e1);
+#if CWF_ABLATION
+    fused_trace_dump(h, it, st);
+#endif
+}
+
+void fast_fused_launch0(cwf_hip_system *h, hipStream_t st)
+{
+    (void)hipMemsetAsync(h->p, 0, sizeof(float) * h->ds.D, st);
+    (void)hipMemsetAsync(h->ap2, 0, sizeof(float) * h->ds.D, st);
+    launch_pcg_lattice(h->ds, fused_args(h, 0), st, nullptr, nullptr);
+}
+
+// a shard's ghost class bytes from their owners (once per handle, before its first fused solve): the owned classes
+// as floats in tmp's x components, a halo, and the ghosts' back into lcls (a ghost's local class is a boundary type
+// of the shard's sub-lattice; its owner's is the node's class in the whole block, the one its z_j is formed with)
+__global__ __launch_bounds__(256) void k_cls_out(const uint8_t *__restrict__ cls, uint32_t n, float *__restrict__ t)
+{
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u)
+        t[3u * i] = (float)cls[i];
+}
+__global__ __launch_bounds__(256) void k_cls_in(const float *__restrict__ t, uint32_t n0, uint32_t n1,
+                                                uint8_t *__restrict__ cls)
+{
+    for (uint32_t i = n0 + blockIdx.x * 256u + threadIdx.x; i < n1; i += gridDim.x * 256u)
+        cls[i] = (uint8_t)t[3u * i];
+}
+void fast_fused_cls_out(cwf_hip_system *h, hipStream_t st)
+{
+    if (h->ds.Nown)
+        k_cls_out<<<std::min<unsigned>(grid_for(h->ds.Nown, 256), 1024u), 256, 0, st>>>(h->ds.t.lcls, h->ds.Nown, h->tmp);
+}
+void fast_fused_cls_in(cwf_hip_system *h, hipStream_t st)
+{
+    if (h->ds.N > h->ds.Nown)
+        k_cls_in<<<std::min<unsigned>(grid_for(h->ds.N - h->ds.Nown, 256), 1024u), 256, 0, st>>>(
+            h->tmp, h->ds.Nown, h->ds.N, const_cast<uint8_t *>(h->ds.t.lcls));
+}
+
+// a shard's launch j: its Ap_j (the vector the exchange after it carries) and its rank totals into g_fsh[rank]
+float *fast_fused_ap(cwf_hip_system *h, unsigned j) { return (j & 1u) ? h->ap2 : h->Ap; }
+void fast_fused_rank_totals(cwf_hip_system *h, unsigned j, hipStream_t st)
+{
+    const unsigned W = h->ds.t.lnwork;
+    k_fused_rank_totals<<<1, 256, 0, st>>>(h->fsh + (size_t)(j & 1u) * 5 * W, h->sched.grid, W,
+                                           h->g_fsh + (size_t)kFusedSlot * h->rank);
+}
+const double *fast_fused_shares(const cwf_hip_system *h, unsigned j, unsigned *stride, unsigned *count)
+{
+    *stride = h->ds.t.lnwork;
+    *count = h->sched.grid;
+    return h->fsh + (size_t)(j & 1u) * 5 * h->ds.t.lnwork;
+}
+
+// the convergence of the batch's last launch (it iterations enqueued: launch it's r)
+void fast_fused_check(cwf_hip_system *h, unsigned it, hipStream_t st)
+{
+    k_fused_check<<<1, 256, 0, st>>>(fused_args(h, it + 1u));
+}
+
+void fast_fused_finish(cwf_hip_system *h, hipStream_t st)
+{
+    const uint32_t D = h->ds.D;
+    if (D)
+        k_fused_finish<<<std::min<unsigned>(grid_for(D, 256), 1024u), 256, 0, st>>>(h->ctl, h->r2, h->r, D);
+}
+}  // namespace cwf

@@ -14,7 +14,7 @@
 //           at system scope;
 //   unpack  its share of the received ghost rows and scalar slots into their vectors / slots (system-scope loads).
 //
-// The fused lattice iteration on PEER shards runs the same protocol inside its own launches instead (lattice_fused.inc
+// The fused lattice iteration on PEER shards runs the same protocol inside its own launches instead (lattice_fused.hip
 // fused_peer_wait / fused_peer_publish; peer_fused_* below set up their arguments): the launch's Ap send rows and
 // rank totals are pushed by the launch, the flags raised by its last workgroup, and the next launch's prologue waits.
 //
@@ -198,7 +198,7 @@ __global__ __launch_bounds__(kPeerThreads) void k_peer_step(PeerStep a)
     // its acquire. The ticket is acq_rel as well (the release formally orders the workgroup's
     // stores before its add, the acquire the last arriver's flag stores after every add): measured free here (8.3-9.0
     // us per step relaxed, 8.3-9.4 acq_rel, same round; profiles/r06s_ticket_acq_rel.txt), unlike the fused launch's
-    // ticket (lattice_fused.inc fused_peer_publish: +14 us per launch, kept relaxed)
+    // ticket (lattice_fused.hip fused_peer_publish: +14 us per launch, kept relaxed)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (threadIdx.x == 0)
@@ -435,7 +435,7 @@ int peer_exchange(cwf_hip_system *h, std::initializer_list<Gather> gathers, cons
     return e == hipSuccess ? 0 : hip_fail(h, e, "peer exchange launch");
 }
 
-// ---- the fused lattice iteration's in-kernel exchange (lattice_fused.inc: fused_peer_wait / fused_peer_publish) ----
+// ---- the fused lattice iteration's in-kernel exchange (lattice_fused.hip: fused_peer_wait / fused_peer_publish) ----
 bool peer_fused_eligible(cwf_hip_system *h)
 {
     cwf_hip_comm *cm = h->comm;

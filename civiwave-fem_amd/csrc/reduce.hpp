@@ -1,4 +1,4 @@
-// reduce.hpp -- fixed-order fp64 reductions shared by the consumer kernels (spmv_tiles.hip) and the PEER exchange
+// reduce.hpp -- fixed-order fp64 reductions shared by the consumer kernels (the FAST units: fast_common.hpp) and the PEER exchange
 // step (peer.hip): every workgroup that folds the same shares gets the same bits, and the PEER step's fold of a
 // rank's shares equals k_fold_pair's (the LOCAL / RCCL schedules') bit for bit.
 #pragma once
@@ -174,7 +174,7 @@ __device__ __forceinline__ void fold_all2(const double *__restrict__ pa, const d
 // K folds of fold_all's order in one pass: element i of array q is p[q stride + i istride] (i < count), thread t
 // sums its elements t, t + NT, ... in that order, 2K loads in flight per trip (two rows per array), then each
 // array's wave and block sums as block_sum. red: K NT / 64 doubles. The fused PCG iteration's five scalars
-// (lattice_fused.inc): a workgroup's shares (istride 1) or the all-gathered per-rank totals (stride 1, istride K).
+// (lattice_fused.hip): a workgroup's shares (istride 1) or the all-gathered per-rank totals (stride 1, istride K).
 // NTV < NT: the fold of an NTV-thread block, bitwise (threads >= NTV hold +0.0, and adding +0.0 to a sum from +0.0
 // changes nothing): the PEER step's 1024-thread workgroup folds a rank's shares as a 256-thread one does.
 template <int NT, int K, int NTV = NT>

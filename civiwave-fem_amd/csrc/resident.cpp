@@ -278,7 +278,7 @@ bool plan_resident(cwf_hip_system *h, bool shard)
         std::copy(ownl[b].begin(), ownl[b].end(), own.begin() + (size_t)b * own_stride);
         std::copy(halol[b].begin(), halol[b].end(), halo.begin() + (size_t)b * halo_stride);
     }
-    // the stencil of each boundary type (lattice.inc's shell cell form regrouped): per offset o >= 1, the sum of the
+    // the stencil of each boundary type (lattice.hip's shell cell form regrouped): per offset o >= 1, the sum of the
     // pair blocks (c, c') with c' - c = o over the cells that exist around a node of that type, in fp64, stored in the
     // rows' packed order {S00 S10 S01 S11} {S02 S12 S20 S21} {S22 - - -}
     const int npairs = t.lhex ? kLatHexPairs : kLatPairs;

@@ -1,7 +1,7 @@
 // resident.hip -- k_pcg_resident: a whole FAST PCG solve of a structured block in ONE launch, with every vector on chip
 // (lattice_common.hpp: the fused iteration's per-node arithmetic, run unchanged).
 //
-// Why: the fused one-launch iteration (lattice_fused.inc) is bound by a per-workgroup chain, not by bytes -- every
+// Why: the fused one-launch iteration (lattice_fused.hip) is bound by a per-workgroup chain, not by bytes -- every
 // launch re-reads r, Ap, p, x and the class of every node from L2 / MALL (97 B per node), every workgroup refolds the
 // previous launch's 436 x 5 shares, and a kernel boundary separates the iterations (C2: 18 us per iteration for 33 MB,
 // 0.23 of HBM; VERDICT r5 items 2 and the C3 / 8 strong-scaling bound). A block of up to ~0.5M nodes fits on chip:
@@ -9,7 +9,7 @@
 // one persistent launch of one 512-thread workgroup per CU, each owning a box of the lattice:
 //   - its nodes' r, Ap, p, x, class and mass live on chip (registers, or LDS in the 4-node instantiation) for the
 //     whole solve;
-//   - per iteration (phase j) it forms r_j, z_j, p_j, x_j exactly as lattice_fused.inc's launch j does (fused_form),
+//   - per iteration (phase j) it forms r_j, z_j, p_j, x_j exactly as lattice_fused.hip's launch j does (fused_form),
 //     writes p_j into an LDS image of the box plus its one-node ring, applies the stencil rows (interior nodes: the
 //     brick rows' difference form; block-surface nodes: the shell's cell form), and leaves the five fp64 dots.
 // The hand-off between boxes is tagged 16-B granules, one synchronisation per iteration, no counter:
@@ -55,7 +55,7 @@
 // up one bound later and releases the rest. Every exit is workgroup-uniform (the votes; the reducer's timeout flag is
 // read behind its fold's barrier).
 //
-// Results: the per-node arithmetic is lattice_fused.inc's; only the grouping of the fp64 dot sums differs (boxes
+// Results: the per-node arithmetic is lattice_fused.hip's; only the grouping of the fp64 dot sums differs (boxes
 // instead of bricks), so alpha / beta differ in their last bits and the solve is tolerance-equal, not bit-equal, to the
 // fused schedule (tests/test_gpu_resident.py). Deterministic run to run: no atomics touch a value, the folds' order is
 // fixed.
@@ -686,7 +686,7 @@ __global__ __launch_bounds__(kResNT) __attribute__((amdgpu_waves_per_eu(2, 2))) 
                 acc[1] = acc01.y;
                 acc[2] = acc2;
             }
-            else  // the brick rows' difference form (lattice_fused.inc rows1); the blocks as scalar loads (from LDS
+            else  // the brick rows' difference form (lattice_fused.hip rows1); the blocks as scalar loads (from LDS
             {     // as well: rows 3.5 -> 4.7 us per phase on C2)
                 int zoff;
                 asm volatile("s_mov_b32 %0, 0" : "=s"(zoff));

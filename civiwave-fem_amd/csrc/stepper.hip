@@ -8,7 +8,6 @@ namespace cwf
 namespace
 {
 constexpr int kBlock = 256;
-inline unsigned grid_for(uint32_t n) { return (n + kBlock - 1) / kBlock; }
 
 // write_predictor (:1245-1286): u~ = (u + dt v) + ((0.5-beta) dt^2) a ; v~ = v + ((1-gamma) dt) a
 __global__ __launch_bounds__(kBlock) void k_predictor(uint32_t D, const float *__restrict__ u,
@@ -124,7 +123,7 @@ void stepper_predictor(uint32_t D, const float *u, const float *v, const float *
     if (!D)
         return;
     const double dt_sq = dt * dt;
-    k_predictor<<<grid_for(D), kBlock, 0, st>>>(D, u, v, a, up, vp, dt, dt_sq, 0.5 - beta, 1.0 - gamma);
+    k_predictor<<<grid_for(D, kBlock), kBlock, 0, st>>>(D, u, v, a, up, vp, dt, dt_sq, 0.5 - beta, 1.0 - gamma);
 }
 
 void stepper_assemble_rhs(uint32_t N, const float *mass, const float *u, const float *v, const float *a,
@@ -132,33 +131,33 @@ void stepper_assemble_rhs(uint32_t N, const float *mass, const float *u, const f
 {
     if (!N)
         return;
-    k_assemble_rhs<<<grid_for(N), kBlock, 0, st>>>(N, mass, u, v, a, f, rhs, damp, c6[0], c6[1], c6[2], c6[3],
+    k_assemble_rhs<<<grid_for(N, kBlock), kBlock, 0, st>>>(N, mass, u, v, a, f, rhs, damp, c6[0], c6[1], c6[2], c6[3],
                                                    c6[4], c6[5], ralpha);
 }
 
 void stepper_rhs_damping(uint32_t D, float *rhs, const float *kd, float bf, hipStream_t st)
 {
     if (D)
-        k_rhs_damping<<<grid_for(D), kBlock, 0, st>>>(D, rhs, kd, bf);
+        k_rhs_damping<<<grid_for(D, kBlock), kBlock, 0, st>>>(D, rhs, kd, bf);
 }
 
 void stepper_clamp(uint32_t N, const uint32_t *mask, const float *bcv, const float *u, float *rhs, hipStream_t st)
 {
     if (N)
-        k_clamp<<<grid_for(N), kBlock, 0, st>>>(N, mask, bcv, u, rhs);
+        k_clamp<<<grid_for(N, kBlock), kBlock, 0, st>>>(N, mask, bcv, u, rhs);
 }
 
 void stepper_update(uint32_t D, const float *x, const float *up, const float *vp, float *u, float *v, float *a,
                     float ib, float gob, hipStream_t st)
 {
     if (D)
-        k_state_update<<<grid_for(D), kBlock, 0, st>>>(D, x, up, vp, u, v, a, ib, gob);
+        k_state_update<<<grid_for(D, kBlock), kBlock, 0, st>>>(D, x, up, vp, u, v, a, ib, gob);
 }
 
 void stepper_scaled_load(uint32_t D, const double *base, const double *pattern, double scale, float *f, hipStream_t st)
 {
     if (D)
-        k_scaled_load<<<grid_for(D), kBlock, 0, st>>>(D, base, pattern, scale, f);
+        k_scaled_load<<<grid_for(D, kBlock), kBlock, 0, st>>>(D, base, pattern, scale, f);
 }
 
 }  // namespace cwf

@@ -1,5 +1,5 @@
-// hex8_tiles.inc -- native trilinear hex8 K_eff, included by spmv_tiles.hip inside its
-// anonymous namespace (shares PcgArgs, residual_step, block_sum, gather_node, stress_f32, dsrc).
+// tiles_hex.hip -- k_keff_hex_tiles: the native trilinear hex8 K_eff on the tile machinery of the tet
+// kernels (fast_common.hpp: PcgArgs, residual_step, stress_f32, load3 / store3).
 //
 // PARITY UNPINNED: the reference rejects hex8 ("only tetrahedron elements supported in Phase 3",
 // src/mesh/preprocess.cpp:326-330). The element is the textbook isoparametric hex (Gmsh/VTK corner
@@ -18,6 +18,12 @@
 // The tile machinery is the tet kernel's push fold: each hex stores its 8 corner forces at their
 // local-CSR positions (epos8), every tile node sums its contiguous run in ascending element order and
 // stores one node-major partial; the update / finalize passes are shared with the tet path.
+#include "fast_common.hpp"
+
+namespace cwf
+{
+namespace
+{
 constexpr float kGa = 0.78867513459481288f;  // (1 + 1/sqrt 3) / 2
 constexpr float kGb = 0.21132486540518712f;  // (1 - 1/sqrt 3) / 2
 constexpr int kHexLex[8] = {0, 1, 3, 2, 4, 5, 7, 6};  // Gmsh corner a -> lexicographic corner (self-inverse)
@@ -280,9 +286,9 @@ __global__ __launch_bounds__(NT) void k_keff_hex_tiles(DevSys s, const float *__
         if (!pa.ctl->active)
             return;
     }
-    const uint32_t nxcd = 8u, xcd = blockIdx.x % nxcd, lb = blockIdx.x / nxcd, nbx = gridDim.x / nxcd;
-    const uint32_t t_end = (uint32_t)(((uint64_t)(xcd + 1) * T.ntiles) / nxcd);
-    uint32_t t = (uint32_t)(((uint64_t)xcd * T.ntiles) / nxcd) + lb;
+    const TileRange tr = xcd_tile_range(T.ntiles);
+    const uint32_t nbx = tr.nbx, t_end = tr.t_end;
+    uint32_t t = tr.t;
     const uint32_t nm = s.M < kMaxM ? s.M : kMaxM;
     for (uint32_t i = threadIdx.x; i < nm * kTab; i += NT)
         dtab[i] = (float)s.dmat[36u * (i / kTab) + dsrc(ISO, i % kTab)];
@@ -463,3 +469,21 @@ HdrTilePick pick_hex(const DevSys &s, bool pcg, bool sanitize)
                 s.iso != 0, pcg, sanitize, nt == 256, s.t.hex_all_affine != 0),
             nt, hex_lds(nt)};
 }
+}  // namespace
+
+void launch_hex_tiles(const DevSys &s, const float *x, const PcgPassArgs &pa, bool pcg, bool sanitize, hipStream_t st,
+                      hipEvent_t e0, hipEvent_t e1)
+{
+    const HdrTilePick p = pick_hex(s, pcg, sanitize);
+    launch_kernel(p.k.fn, s.t.pipe_grid, p.nt, p.lds, st, e0, e1, s, x, PcgArgs{pa}, s.t.hdr);
+}
+
+const char *hex_tiles_kernel_name(const DevSys &s) { return pick_hex(s, true, false).k.name; }
+
+unsigned hex_tiles_pipe_grid(const DevSys &s)
+{
+    const HdrTilePick p = pick_hex(s, true, false);
+    return xcd_grid(p.k.fn, p.nt, p.lds, s.t.ntiles);
+}
+
+}  // namespace cwf

@@ -12,7 +12,7 @@
  *   - N_a = (1 + xi xi_a)(1 + eta eta_a)(1 + zeta zeta_a) / 8, full 2x2x2 Gauss (points +-1/sqrt(3), w = 1);
  *   - B, D and the Voigt order (xx, yy, zz, xy, yz, xz; engineering shear) of the tet path
  *     (pcg.cpp:592-651): f_a = sum_gp |det J| B_a^T D B u * s_K.
- * The GPU kernel (spmv_tiles.hip, k_keff_hex_tiles) evaluates the same integrals with sum
+ * The GPU kernel (tiles_hex.hip, k_keff_hex_tiles) evaluates the same integrals with sum
  * factorisation in fp32; tests compare both and check the operator's physics (patch test, rigid
  * modes, symmetry, convergence towards the oracle Kuhn-tet solution).
  */

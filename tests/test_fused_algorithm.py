@@ -1,4 +1,4 @@
-"""The fused lattice iteration's algorithm (lattice_fused.inc) on the CPU, before any kernel: one global reduction
+"""The fused lattice iteration's algorithm (lattice_fused.hip) on the CPU, before any kernel: one global reduction
 per iteration (alpha from the direct rho_j = r_j.z_j and p_j.Ap_j; beta's numerator r_(j+1).z_(j+1) expanded through
 r_(j+1) = r_j - alpha_j Ap_j from the same launch's z_j.Ap_j and Ap_j.M^-1 Ap_j, re-based on the direct dots every
 iteration) against the reference loop (pcg.cpp:840-901), both emulated in FAST arithmetic (fp32 vectors, fp64 dot

@@ -1,4 +1,4 @@
-"""The structured-block FAST operator (lattice.cpp / lattice.inc, k_keff_lattice; lattice_fused.inc, k_pcg_lattice)
+"""The structured-block FAST operator (lattice.cpp / lattice.hip, k_keff_lattice; lattice_fused.hip, k_pcg_lattice)
 against the pinned oracle.
 
 A FAST handle whose mesh is a Kuhn-split box lattice (one gradient / volume set per Kuhn type) applies K_eff as
@@ -45,7 +45,7 @@ def _kernel(s):
 
 
 # the structured-block stencil: the resident one-launch solve (resident.hip, the default where the block fits on chip;
-# tests/test_gpu_resident.py), the fused one-launch iteration (lattice_fused.inc, where its grid is at most
+# tests/test_gpu_resident.py), the fused one-launch iteration (lattice_fused.hip, where its grid is at most
 # CWF_FUSED_MAXWG workgroups) or the two-kernel one (k_keff_lattice + the update pass)
 LATTICE = ("k_pcg_resident", "k_pcg_lattice", "k_keff_lattice")
 
@@ -245,7 +245,7 @@ def test_fast_solve_run_to_run_deterministic(mesh, monkeypatch):
 
 @pytest.mark.parametrize("name", ["33x9x5", "rollers", "c1", "rayleigh", "33x9x5-persistent", "hex", "hex-persistent"])
 def test_fused_iteration_matches_two_kernel_loop(name, monkeypatch):
-    """The fused one-launch iteration (lattice_fused.inc: r, z, p, x formed in the launch that applies K_eff; beta's
+    """The fused one-launch iteration (lattice_fused.hip: r, z, p, x formed in the launch that applies K_eff; beta's
     numerator r_(j+1).z_(j+1) expanded through r_(j+1) = r_j - alpha Ap_j from the launch's own dots) against the
     reference loop's two kernels on the same handle geometry: the same solution to 1e-4 of the oracle's and an
     iteration count within 5% (tools/cg_variants.py emulates both in FAST arithmetic on the CPU)."""

@@ -1,4 +1,4 @@
-"""Layered structured blocks on the GPU (lattice.inc, k_keff_lattice_layered): a Kuhn tet or native hex8 block
+"""Layered structured blocks on the GPU (lattice.hip, k_keff_lattice_layered): a Kuhn tet or native hex8 block
 whose material is constant within every k-layer of cells applies K_eff as a per-plane stencil table (one table per
 (material below, material above) pair) and, on its surface, each cell's pair blocks from its layer's table.
 

@@ -88,7 +88,7 @@ def _assemble(out, n):
 @pytest.mark.parametrize("nranks", [2, 3])
 def test_peer_lattice_slabs_equal_local(nranks, inkernel, element, monkeypatch):
     """in_kernel_exchange: the fused launches push their Ap send rows, rank totals and epoch flags themselves and
-    wait for the peers' in their prologue (lattice_fused.inc fused_peer_wait / fused_peer_publish: no exchange
+    wait for the peers' in their prologue (lattice_fused.hip fused_peer_wait / fused_peer_publish: no exchange
     launch); exchange_step (CWF_PEER_FUSED=0): one k_peer_step launch after each fused launch. Both equal the LOCAL
     solve bit for bit, and a second solve on the same communicator repeats the first (the epochs carry over).
     in_kernel_persistent: the same with an 8-workgroup grid walking the items (CWF_FUSED=2), in both the PEER

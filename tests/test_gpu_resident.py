@@ -1,7 +1,7 @@
 """The resident one-launch solve of a structured block (csrc/resident.hip, csrc/resident.cpp) against the pinned oracle
-and against the launch-per-iteration fused schedule (lattice_fused.inc) it replaces on blocks that fit on chip.
+and against the launch-per-iteration fused schedule (lattice_fused.hip) it replaces on blocks that fit on chip.
 
-The resident kernel runs lattice_fused.inc's per-node arithmetic (r, z, p, x formed by fused_form, the brick rows'
+The resident kernel runs lattice_fused.hip's per-node arithmetic (r, z, p, x formed by fused_form, the brick rows'
 difference form, the shell's cell form); only the grouping of its fp64 dot sums differs (boxes of the lattice instead of
 bricks), so it carries the FAST tolerance contract: solves at tol 1e-6 within 1e-4 (relative) of the oracle's solution in
 its iteration count +-10%, and within 1e-5 of the fused schedule's x after 1, 2, 3 and 20 fixed iterations. Covered: the

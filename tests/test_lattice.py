@@ -1,7 +1,7 @@
 """Host side of the structured-block FAST operator (lattice.cpp) on the CPU: the detection and the stencil blocks
 it derives, through the C-ABI introspection entry cwf_lattice_describe (no device needed).
 
-The blocks are applied here in numpy (fp64 over the f32 blocks), with the kernel's algorithm (lattice.inc): the 14
+The blocks are applied here in numpy (fp64 over the f32 blocks), with the kernel's algorithm (lattice.hip): the 14
 off-centre interior stencil blocks on the differences u_(n+d) - u_n for the nodes inside the block, and for the
 nodes on its surface each existing cell's blocks on the differences to the node's own value. That must reproduce the pinned oracle's apply_keff (the reference's element loop) to the f32 rounding of
 the blocks: 1e-6 of the operator scale (max |row|)."""
@@ -41,7 +41,7 @@ def fast_system(case):
 
 def lattice_apply(dims, coef, x3, sK):
     """K x (no mass, no Dirichlet) on an nx*ny*nz lattice in lexicographic order, the kernel's algorithm
-    (lattice.inc): interior nodes by the difference-form stencil sum_(d != 0) S_d (u_(n+d) - u_n), surface nodes by
+    (lattice.hip): interior nodes by the difference-form stencil sum_(d != 0) S_d (u_(n+d) - u_n), surface nodes by
     the cell form (each existing cell's blocks on the differences to the node's own value)."""
     nx, ny, nz = dims
     u = np.pad(x3.reshape(nz, ny, nx, 3), ((1, 1), (1, 1), (1, 1), (0, 0)), mode="edge")

@@ -2,7 +2,7 @@
 stencil tables it derives (lattice.cpp), through the C-ABI introspection entry cwf_lattice_describe_layers (no
 device needed).
 
-The tables are applied here in numpy (fp64 over the f32 tables) with the kernel's algorithm (lattice.inc,
+The tables are applied here in numpy (fp64 over the f32 tables) with the kernel's algorithm (lattice.hip,
 k_keff_lattice_layered): a strict-interior node of plane k takes the 14 off-centre stencil blocks of its plane's
 class, the (material below, material above) pair, on the differences u_(n+d) - u_n; a surface node takes each
 existing cell's pair blocks from the table of that cell's material. That must reproduce the pinned oracle's

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Summarise the per-workgroup stamps of one fused lattice launch (CWF_FUSED_TRACE, ablation build; lattice_fused.inc
+"""Summarise the per-workgroup stamps of one fused lattice launch (CWF_FUSED_TRACE, ablation build; lattice_fused.hip
 `stamp`). Phases per workgroup (s_memrealtime, 100 MHz = 10 ns ticks): dispatch offset from the launch's first
 workgroup, t1 - t0 prologue (plane loads issued, share fold), t2 - t1 the first two planes formed (bricks), t3 - t2
 the march (bricks) or the shell rows, t4 - t3 the block reduction and the share store; and how many workgroups each
