@@ -27,6 +27,27 @@ struct cwf_hip_explicit : TransientState
     std::vector<double> dash_C;
     uint32_t *dslot = nullptr;
     DevicePtr<double> dpq;
+    // set_monitors: the set in force, its device buffers (the stepper's arena) and the host's sample bookkeeping
+    struct Monitors
+    {
+        uint64_t rcount = 0, revery = 0, rcap = 0, rdropped = 0;
+        uint32_t *rnode = nullptr;             // [rcount] internal node of each receiver
+        float *ru = nullptr, *rv = nullptr;    // [rcap][rcount][3]
+        std::vector<uint64_t> rsteps;          // the step count of each row held
+        float *peak = nullptr;                 // [3][peak_stride]
+        uint64_t peak_stride = 0;
+        uint64_t eevery = 0, ecap = 0, edropped = 0;
+        double *ecum = nullptr, *ecur = nullptr, *erows = nullptr;  // [2 blocks], [2 blocks], [ecap][4]
+        std::vector<uint64_t> esteps;
+        void release(DeviceArena &mem)
+        {
+            for (void *p : {(void *)rnode, (void *)ru, (void *)rv, (void *)peak, (void *)ecum, (void *)ecur,
+                            (void *)erows})
+                mem.free(p);
+            *this = Monitors();
+        }
+    } mon;
+    double *dC = nullptr;  // the ledger's slot-indexed C array (arena), while a ledger and dashpots are both set
 };
 
 namespace
@@ -261,6 +282,16 @@ int cwf_hip_explicit_advance(cwf_hip_explicit *t, uint64_t n_steps, cwf_explicit
     const bool dash = !t->dash_ids.empty();
     a.dslot = dash ? t->dslot : nullptr;
     a.dpq = dash ? t->dpq.get() : nullptr;
+    // monitors: the host knows every step count, so which update is sampled and the row it lands in are launch
+    // arguments; there are no device counters
+    cwf_hip_explicit::Monitors &mon = t->mon;
+    a.peak = mon.peak;
+    a.peak_stride = mon.peak_stride;
+    a.ecum = mon.ecum;
+    a.ecur = mon.ecur;
+    a.dC = dash ? t->dC : nullptr;
+    a.alpha = t->alpha;
+    const uint32_t blocks = explicit_update_blocks(s.N);
     for (uint64_t i = 0; i < n_steps; ++i)
     {
         if (pattern)
@@ -269,8 +300,28 @@ int cwf_hip_explicit_advance(cwf_hip_explicit *t, uint64_t n_steps, cwf_explicit
             fast_keff_partials_ds(s, t->w, true, st);
         else
             parity_keff_ds(s, t->w, t->y, true, nullptr, st);
+        const bool edue = mon.eevery && (t->steps + 1) % mon.eevery == 0;
+        a.esample = edue && mon.esteps.size() < mon.ecap ? 1u : 0u;
         explicit_update(s, a, st);
         ++t->steps;
+        if (a.esample)
+        {
+            explicit_energy_fold(blocks, mon.ecum, mon.ecur, mon.erows + 4 * mon.esteps.size(), st);
+            mon.esteps.push_back(t->steps);
+        }
+        else if (edue)
+            ++mon.edropped;
+        if (mon.rcount && t->steps % mon.revery == 0)
+        {
+            if (mon.rsteps.size() < mon.rcap)
+            {
+                const size_t row = 3 * mon.rcount * mon.rsteps.size();
+                explicit_record((uint32_t)mon.rcount, mon.rnode, t->u, t->v, mon.ru + row, mon.rv + row, st);
+                mon.rsteps.push_back(t->steps);
+            }
+            else
+                ++mon.rdropped;
+        }
     }
     if (n_steps)
         t->input_stale = false;
@@ -366,6 +417,8 @@ int cwf_hip_explicit_set_dashpots(cwf_hip_explicit *t, uint64_t count, const uin
     {
         HIPTRY(h, hipStreamSynchronize(s));
         t->dpq.reset();
+        t->mem.free(t->dC);
+        t->dC = nullptr;
         t->dash_ids.clear();
         t->dash_C.clear();
         return 0;
@@ -397,7 +450,13 @@ int cwf_hip_explicit_set_dashpots(cwf_hip_explicit *t, uint64_t count, const uin
     if (!t->dslot)
         if (int st = t->alloc(&t->dslot, slot.size()))
             return st;
+    double *newC = nullptr;  // a ledger reads C as given: its slot-indexed array follows the set
+    if (t->mon.ecum)
+        if (int st = t->alloc(&newC, 9 * count))
+            return st;
     hipError_t e = hipMemcpyAsync(rec, pq.data(), pq.size() * sizeof(double), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && newC)
+        e = hipMemcpyAsync(newC, C, 9 * count * sizeof(double), hipMemcpyHostToDevice, s);
     int st = 0;
     if (e == hipSuccess)  // the slots move to the internal order as a one-word node vector (bit copies)
         st = vec_in(h, reinterpret_cast<const float *>(slot.data()), reinterpret_cast<float *>(t->dslot),
@@ -409,8 +468,11 @@ int cwf_hip_explicit_set_dashpots(cwf_hip_explicit *t, uint64_t count, const uin
         (void)hipStreamSynchronize(s);
         t->dash_ids.clear();  // the slot array may be half written: no dashpots until the next set
         t->dash_C.clear();
+        t->mem.free(newC);
         return st ? st : hip_fail(h, e, "explicit set_dashpots");
     }
+    t->mem.free(t->dC);
+    t->dC = newC;
     t->dpq = std::move(rec);
     t->dash_ids.assign(node_ids, node_ids + count);
     t->dash_C.assign(C, C + 9 * count);
@@ -426,6 +488,251 @@ int cwf_hip_explicit_get_dashpots(cwf_hip_explicit *t, uint64_t *count, uint32_t
         std::copy(t->dash_ids.begin(), t->dash_ids.end(), node_ids);
     if (C)
         std::copy(t->dash_C.begin(), t->dash_C.end(), C);
+    return 0;
+}
+
+int cwf_hip_explicit_set_monitors(cwf_hip_explicit *t, const cwf_explicit_monitor_desc *desc)
+{
+    if (!t)
+        return set_error(nullptr, CWF_ERR_ARGUMENT, "null handle");
+    cwf_hip_system *h = t->sys;
+    if (int st = check_ready(h))
+        return st;
+    hipStream_t s = h->stream;
+    const cwf_explicit_monitor_desc none{};
+    const cwf_explicit_monitor_desc &d = desc ? *desc : none;
+    const uint64_t N = h->ds.N;
+    // everything that can be refused, on the host, before anything changes
+    if (d.receiver_count && !d.receiver_nodes)
+        return set_error(h, CWF_ERR_ARGUMENT, "null pointer");
+    if (d.receiver_count && d.receiver_every < 1)
+        return set_error(h, CWF_ERR_ARGUMENT, "receiver_every must be at least 1");
+    if ((d.receiver_count && !d.receiver_capacity) || (d.energy_every && !d.energy_capacity))
+        return set_error(h, CWF_ERR_ARGUMENT, "monitor capacity must not be zero",
+                         "receiver_capacity=" + std::to_string(d.receiver_capacity) +
+                             "\nenergy_capacity=" + std::to_string(d.energy_capacity));
+    if (d.energy_every && t->beta != 0.0)
+        return set_error(h, CWF_ERR_UNSUPPORTED, "the energy ledger needs rayleigh_beta == 0",
+                         "rayleigh_beta=" + num(t->beta));
+    const uint32_t kNone = 0xFFFFFFFFu;
+    std::vector<uint32_t> slot(d.receiver_count ? std::max<uint64_t>(N, 4) : 0, kNone);
+    for (uint64_t i = 0; i < d.receiver_count; ++i)
+    {
+        const uint32_t node = d.receiver_nodes[i];
+        if (node >= N)
+            return set_error(h, CWF_ERR_ARGUMENT, "receiver node out of range",
+                             "index=" + std::to_string(i) + "\nnode=" + std::to_string(node));
+        if (slot[node] != kNone)
+            return set_error(h, CWF_ERR_ARGUMENT, "receiver node listed twice",
+                             "index=" + std::to_string(i) + "\nnode=" + std::to_string(node));
+        slot[node] = (uint32_t)i;
+    }
+    const uint64_t kMaxBytes = 1ull << 44;  // no device holds more: a product past it is an allocation failure
+    if (d.receiver_count && d.receiver_capacity > kMaxBytes / (12 * d.receiver_count))
+        return set_error(h, CWF_ERR_ALLOC, t->alloc_error);
+    if (d.energy_every && d.energy_capacity > kMaxBytes / 32)
+        return set_error(h, CWF_ERR_ALLOC, t->alloc_error);
+    HIPTRY(h, hipStreamSynchronize(s));
+    // the new set's buffers; the stepper's once everything went well
+    cwf_hip_explicit::Monitors m;
+    double *newC = nullptr;
+    DevicePtr<uint32_t> order;  // the receivers' slots in the internal node order
+    const uint32_t blocks = explicit_update_blocks((uint32_t)N);
+    int st = 0;
+    hipError_t e = hipSuccess;
+    if (d.receiver_count)
+    {
+        m.rcount = d.receiver_count;
+        m.revery = d.receiver_every;
+        m.rcap = d.receiver_capacity;
+        const size_t cells = (size_t)(3 * m.rcount * m.rcap);
+        st = st ? st : t->alloc(&m.rnode, m.rcount);
+        st = st ? st : t->alloc(&m.ru, cells);
+        st = st ? st : t->alloc(&m.rv, cells);
+        if (!st && order.alloc(slot.size()) != hipSuccess)
+            st = set_error(h, CWF_ERR_ALLOC, t->alloc_error);
+    }
+    if (d.peaks)
+    {
+        m.peak_stride = std::max<uint64_t>(N, 4);
+        st = st ? st : t->alloc(&m.peak, 3 * m.peak_stride);
+    }
+    if (d.energy_every)
+    {
+        m.eevery = d.energy_every;
+        m.ecap = d.energy_capacity;
+        st = st ? st : t->alloc(&m.ecum, 2 * (size_t)blocks);
+        st = st ? st : t->alloc(&m.ecur, 2 * (size_t)blocks);
+        st = st ? st : t->alloc(&m.erows, 4 * (size_t)m.ecap);
+        if (!st && !t->dash_ids.empty())
+            st = t->alloc(&newC, t->dash_C.size());
+    }
+    std::vector<uint32_t> rnode(m.rcount);
+    if (!st && m.rcount)
+    {
+        // the receivers' nodes in the internal order: the slots move as a one-word node vector (bit copies), as
+        // set_dashpots moves its own, and come back as a list
+        std::vector<uint32_t> back(slot.size());
+        st = vec_in(h, reinterpret_cast<const float *>(slot.data()), reinterpret_cast<float *>(order.get()),
+                    CWF_PTR_HOST, 1);
+        if (!st)
+            e = hipMemcpyAsync(back.data(), order.get(), N * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
+        if (!st && e == hipSuccess)
+            e = hipStreamSynchronize(s);
+        if (!st && e == hipSuccess)
+        {
+            for (uint64_t n = 0; n < N; ++n)
+                if (back[n] != kNone)
+                    rnode[back[n]] = (uint32_t)n;
+            e = hipMemcpyAsync(m.rnode, rnode.data(), m.rcount * sizeof(uint32_t), hipMemcpyHostToDevice, s);
+        }
+    }
+    if (!st && e == hipSuccess && m.peak)
+        e = hipMemsetAsync(m.peak, 0, 3 * m.peak_stride * sizeof(float), s);
+    if (!st && e == hipSuccess && m.ecum)
+        e = hipMemsetAsync(m.ecum, 0, 2 * (size_t)blocks * sizeof(double), s);
+    if (!st && e == hipSuccess && m.ecur)
+        e = hipMemsetAsync(m.ecur, 0, 2 * (size_t)blocks * sizeof(double), s);
+    if (!st && e == hipSuccess && newC)
+        e = hipMemcpyAsync(newC, t->dash_C.data(), t->dash_C.size() * sizeof(double), hipMemcpyHostToDevice, s);
+    if (!st && e == hipSuccess)
+        e = hipStreamSynchronize(s);
+    if (st || e != hipSuccess)
+    {
+        (void)hipStreamSynchronize(s);
+        m.release(t->mem);
+        t->mem.free(newC);
+        return st ? st : hip_fail(h, e, "explicit set_monitors");
+    }
+    m.rsteps.reserve((size_t)std::min<uint64_t>(m.rcap, 1u << 20));
+    m.esteps.reserve((size_t)std::min<uint64_t>(m.ecap, 1u << 20));
+    t->mon.release(t->mem);
+    t->mem.free(t->dC);
+    t->mon = std::move(m);
+    t->dC = newC;
+    return 0;
+}
+
+int cwf_hip_explicit_reset_monitors(cwf_hip_explicit *t)
+{
+    if (!t)
+        return set_error(nullptr, CWF_ERR_ARGUMENT, "null handle");
+    cwf_hip_system *h = t->sys;
+    if (int st = check_ready(h))
+        return st;
+    cwf_hip_explicit::Monitors &m = t->mon;
+    const size_t blocks = explicit_update_blocks(h->ds.N);
+    if (m.peak)
+        HIPTRY(h, hipMemsetAsync(m.peak, 0, 3 * m.peak_stride * sizeof(float), h->stream));
+    if (m.ecum)
+    {
+        HIPTRY(h, hipMemsetAsync(m.ecum, 0, 2 * blocks * sizeof(double), h->stream));
+        HIPTRY(h, hipMemsetAsync(m.ecur, 0, 2 * blocks * sizeof(double), h->stream));
+    }
+    HIPTRY(h, hipStreamSynchronize(h->stream));
+    m.rsteps.clear();
+    m.esteps.clear();
+    m.rdropped = m.edropped = 0;
+    return 0;
+}
+
+int cwf_hip_explicit_monitor_info(cwf_hip_explicit *t, cwf_explicit_monitor_info *info)
+{
+    if (!t || !info)
+        return set_error(nullptr, CWF_ERR_ARGUMENT, "null pointer");
+    const cwf_hip_explicit::Monitors &m = t->mon;
+    cwf_explicit_monitor_info I{};
+    I.receiver_count = m.rcount;
+    I.receiver_every = m.revery;
+    I.receiver_capacity = m.rcap;
+    I.receiver_samples = m.rsteps.size();
+    I.receiver_dropped = m.rdropped;
+    I.energy_every = m.eevery;
+    I.energy_capacity = m.ecap;
+    I.energy_samples = m.esteps.size();
+    I.energy_dropped = m.edropped;
+    I.peaks = m.peak ? 1u : 0u;
+    *info = I;
+    return 0;
+}
+
+namespace
+{
+int rows_in_range(cwf_hip_system *h, uint64_t first, uint64_t count, uint64_t held)
+{
+    if (first > held || count > held - first)
+        return set_error(h, CWF_ERR_ARGUMENT, "monitor rows out of range",
+                         "first=" + std::to_string(first) + "\ncount=" + std::to_string(count) +
+                             "\nheld=" + std::to_string(held));
+    return 0;
+}
+}  // namespace
+
+int cwf_hip_explicit_read_receivers(cwf_hip_explicit *t, uint64_t first, uint64_t count, uint64_t *steps, float *u,
+                                    float *v)
+{
+    if (!t)
+        return set_error(nullptr, CWF_ERR_ARGUMENT, "null handle");
+    cwf_hip_system *h = t->sys;
+    if (int st = check_ready(h))
+        return st;
+    const cwf_hip_explicit::Monitors &m = t->mon;
+    if (int st = rows_in_range(h, first, count, m.rsteps.size()))
+        return st;
+    if (!count)
+        return 0;
+    if (steps)
+        std::copy(m.rsteps.begin() + first, m.rsteps.begin() + first + count, steps);
+    const size_t off = (size_t)(3 * m.rcount * first), len = (size_t)(3 * m.rcount * count) * sizeof(float);
+    if (u)
+        HIPTRY(h, hipMemcpyAsync(u, m.ru + off, len, hipMemcpyDeviceToHost, h->stream));
+    if (v)
+        HIPTRY(h, hipMemcpyAsync(v, m.rv + off, len, hipMemcpyDeviceToHost, h->stream));
+    HIPTRY(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+int cwf_hip_explicit_read_peaks(cwf_hip_explicit *t, float *peak_u, float *peak_v, float *peak_a, uint64_t n, int kind)
+{
+    if (!t)
+        return set_error(nullptr, CWF_ERR_ARGUMENT, "null handle");
+    cwf_hip_system *h = t->sys;
+    if (int st = check_ready(h))
+        return st;
+    const cwf_hip_explicit::Monitors &m = t->mon;
+    if (!m.peak)
+        return set_error(h, CWF_ERR_ARGUMENT, "no peak maps are set");
+    if (n != h->ds.N)
+        return set_error(h, CWF_ERR_SIZE, "peak map span size mismatch",
+                         "span=" + std::to_string(n) + "\nnodes=" + std::to_string(h->ds.N));
+    float *out[3] = {peak_u, peak_v, peak_a};
+    for (int j = 0; j < 3; ++j)
+        if (out[j])
+            if (int st = vec_out(h, m.peak + j * m.peak_stride, out[j], kind, 1))
+                return st;
+    HIPTRY(h, hipGetLastError());
+    HIPTRY(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+int cwf_hip_explicit_read_energy(cwf_hip_explicit *t, uint64_t first, uint64_t count, uint64_t *steps, double *rows)
+{
+    if (!t)
+        return set_error(nullptr, CWF_ERR_ARGUMENT, "null handle");
+    cwf_hip_system *h = t->sys;
+    if (int st = check_ready(h))
+        return st;
+    const cwf_hip_explicit::Monitors &m = t->mon;
+    if (int st = rows_in_range(h, first, count, m.esteps.size()))
+        return st;
+    if (!count)
+        return 0;
+    if (steps)
+        std::copy(m.esteps.begin() + first, m.esteps.begin() + first + count, steps);
+    if (rows)
+        HIPTRY(h, hipMemcpyAsync(rows, m.erows + 4 * first, 4 * count * sizeof(double), hipMemcpyDeviceToHost,
+                                 h->stream));
+    HIPTRY(h, hipStreamSynchronize(h->stream));
     return 0;
 }
 

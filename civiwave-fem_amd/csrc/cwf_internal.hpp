@@ -763,9 +763,23 @@ struct ExplicitPass
     uint32_t *non_finite;      // raised when a stored value is not finite
     const uint32_t *dslot;     // dashpots (NULL: none): a node's record in dpq, kNoDashpot for a node without one
     const double *dpq;         // 18 f64 per dashpot node: P then Q, row-major (dashpot_update)
+    // monitors (cwf_hip_explicit_set_monitors). peak or ecum set: the MON instantiations run; both NULL: the plain ones
+    float *peak;               // peak maps (NULL: none): three arrays of peak_stride f32, |u|, |v|, |a| per node
+    uint64_t peak_stride;
+    double *ecum, *ecur;       // energy ledger (ecum NULL: none): per workgroup {work, dissipated} summed over the
+                               // steps and {kinetic, potential} of the last sampled step
+    const double *dC;          // the ledger's dashpot matrices as given, 9 f64 per slot (NULL: no dashpots)
+    double alpha;              // alpha_R, read by the ledger only
+    uint32_t esample;          // this step is sampled: ecur is written
 };
 constexpr uint32_t kNoDashpot = 0xFFFFFFFFu;
 void explicit_update(const DevSys &s, const ExplicitPass &a, hipStream_t st);
+inline uint32_t explicit_update_blocks(uint32_t N) { return (N + 255u) / 256u; }  // the update pass's workgroups
+// one sampled step's ledger row {kinetic, potential, work_cum, dissipated_cum} from the per-workgroup shares
+void explicit_energy_fold(uint32_t blocks, const double *ecum, const double *ecur, double *row, hipStream_t st);
+// u and v of the receiver nodes (internal ids) into one row [count][3] each
+void explicit_record(uint32_t count, const uint32_t *node, const float *u, const float *v, float *row_u, float *row_v,
+                     hipStream_t st);
 void explicit_operator_input(uint32_t N, const float *u, const float *v, double beta, float *w, hipStream_t st);
 // power iteration (cwf_hip_lambda_max): the start vector; z = M^-1 y over the free DOFs; x = z / (num / den),
 // the quotient stored in lam[0]

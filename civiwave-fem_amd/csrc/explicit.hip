@@ -40,12 +40,19 @@ __device__ __forceinline__ float safe_cast(double v)
 // (18 f64, 144 B, nine 16-B loads that depend on the slot) and takes the matrix form of the scheme, the others the
 // expression above. With dashpots on five faces of a 150^3-node block (3.3 % of the nodes) that is 84 + 0.033 x 144
 // = 88.8 B per node. The branch diverges only in waves that touch the boundary; it is not launched without dashpots.
-template <bool FOLD, bool PATTERN, bool DAMP, bool DASH>
+// MON: monitors (include/cwf_hip.h "Monitors"); which of the two is active is a launch-uniform test of a.peak and
+// a.ecum. The ledger's block reduction needs every lane of the tail workgroup at the barrier, so a lane past N is
+// carried through on node N - 1's loads, stores nothing and shares zeros. Peaks: three 4-B loads and up to three 4-B
+// stores per node (+24 B worst case; a peak that did not rise is not stored). Ledger: a dashpot node loads its C
+// (72 B); per workgroup 16 B read and written every step, 16 B more written on a sampled step.
+template <bool FOLD, bool PATTERN, bool DAMP, bool DASH, bool MON>
 __global__ __launch_bounds__(kBlock) void k_explicit_update(DevSys s, ExplicitPass a)
 {
-    const uint32_t n = blockIdx.x * kBlock + threadIdx.x;
-    if (n >= s.N)
+    const uint32_t gid = blockIdx.x * kBlock + threadIdx.x;
+    const bool live = gid < s.N;
+    if (!MON && !live)
         return;
+    const uint32_t n = MON && !live ? s.N - 1 : gid;
     const F3 u = load3(a.u, n), v = load3(a.v, n);
     const uint32_t mk = s.mask[n];
     const float mass = s.mass[n];
@@ -141,12 +148,152 @@ __global__ __launch_bounds__(kBlock) void k_explicit_update(DevSys s, ExplicitPa
         if constexpr (DAMP)
             wn.c[k] = (float)((double)un.c[k] + a.beta * (double)vn.c[k]);
     }
-    store3(a.u, n, un);
-    store3(a.v, n, vn);
-    if constexpr (DAMP)
-        store3(a.w, n, wn);
-    if (bad)
-        atomicOr(a.non_finite, 1u);
+    if (live)
+    {
+        store3(a.u, n, un);
+        store3(a.v, n, vn);
+        if constexpr (DAMP)
+            store3(a.w, n, wn);
+        if (bad)
+            atomicOr(a.non_finite, 1u);
+    }
+    if constexpr (MON)
+    {
+        if (a.peak && live)
+        {
+            const double a0 = ((double)vn.c[0] - (double)v.c[0]) / a.dt, a1 = ((double)vn.c[1] - (double)v.c[1]) / a.dt,
+                         a2 = ((double)vn.c[2] - (double)v.c[2]) / a.dt;
+            const float x[3] = {
+                (float)sqrt(((double)un.c[0] * un.c[0] + (double)un.c[1] * un.c[1]) + (double)un.c[2] * un.c[2]),
+                (float)sqrt(((double)vn.c[0] * vn.c[0] + (double)vn.c[1] * vn.c[1]) + (double)vn.c[2] * vn.c[2]),
+                (float)sqrt((a0 * a0 + a1 * a1) + a2 * a2)};
+#pragma unroll
+            for (int j = 0; j < 3; ++j)
+            {
+                float *p = a.peak + j * a.peak_stride + n;
+                if (x[j] > *p)
+                    *p = x[j];
+            }
+        }
+        if (a.ecum)
+        {
+            double vb[3], t[4][3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+                vb[k] = 0.5 * ((double)vn.c[k] + (double)v.c[k]);
+            const bool dashed = DASH && slot != kNoDashpot && a.dC;
+            double Cn[9];
+            if (dashed)
+#pragma unroll
+                for (int i = 0; i < 9; ++i)
+                    Cn[i] = a.dC[9ull * slot + i];
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+            {
+                const bool free_dof = live && !(mk & (1u << k));
+                double diss = a.dt * (a.alpha * (m * (vb[k] * vb[k])));
+                if (dashed)
+                    diss = diss + a.dt * (vb[k] * ((Cn[3 * k] * vb[0] + Cn[3 * k + 1] * vb[1]) + Cn[3 * k + 2] * vb[2]));
+                t[0][k] = free_dof ? 0.5 * (m * ((double)vn.c[k] * (double)vn.c[k])) : 0.0;
+                t[1][k] = free_dof ? 0.5 * ((double)un.c[k] * (double)y.c[k]) : 0.0;
+                t[2][k] = free_dof ? a.dt * (vb[k] * (double)f.c[k]) : 0.0;
+                t[3][k] = free_dof ? diss : 0.0;
+            }
+            // kinetic and potential only on a sampled step (launch-uniform)
+            __shared__ double part[4][kBlock / 64];
+            const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+            {
+                if (q < 2 && !a.esample)
+                    continue;
+                double x = (t[q][0] + t[q][1]) + t[q][2];
+#pragma unroll
+                for (int off = 32; off >= 1; off >>= 1)
+                    x = x + __shfl_down(x, off, 64);
+                if (lane == 0)
+                    part[q][wave] = x;
+            }
+            __syncthreads();
+            if (threadIdx.x == 0)
+            {
+                double sum[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    if (q >= 2 || a.esample)
+                        sum[q] = (part[q][0] + part[q][1]) + (part[q][2] + part[q][3]);
+                double *cum = a.ecum + 2ull * blockIdx.x;
+                cum[0] = cum[0] + sum[2];
+                cum[1] = cum[1] + sum[3];
+                if (a.esample)
+                {
+                    a.ecur[2ull * blockIdx.x] = sum[0];
+                    a.ecur[2ull * blockIdx.x + 1] = sum[1];
+                }
+            }
+        }
+    }
+}
+
+// A sampled step's ledger row from the workgroups' shares, in one workgroup: thread t adds workgroups t, t + 256, ...
+// in that order, then the 256 sums fold pairwise (stride 128 ... 1).
+__global__ __launch_bounds__(kBlock) void k_explicit_energy_fold(uint32_t blocks, const double *__restrict__ ecum,
+                                                                 const double *__restrict__ ecur,
+                                                                 double *__restrict__ row)
+{
+    __shared__ double sh[4][kBlock];
+    double x[4] = {0.0, 0.0, 0.0, 0.0};
+    // four workgroups' shares are loaded before they are added (16-B loads; both arrays are hipMalloc'd), so the
+    // loop waits for memory once per four; the additions keep the order t, t + 256, ...
+    const double2 *cur = reinterpret_cast<const double2 *>(ecur), *cum = reinterpret_cast<const double2 *>(ecum);
+    for (uint32_t b0 = threadIdx.x; b0 < blocks; b0 += 4 * kBlock)
+    {
+        double2 c[4], s[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+        {
+            const uint32_t b = b0 + j * kBlock;
+            c[j] = b < blocks ? cur[b] : make_double2(0.0, 0.0);
+            s[j] = b < blocks ? cum[b] : make_double2(0.0, 0.0);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (b0 + j * kBlock < blocks)
+            {
+                x[0] = x[0] + c[j].x;
+                x[1] = x[1] + c[j].y;
+                x[2] = x[2] + s[j].x;
+                x[3] = x[3] + s[j].y;
+            }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+        sh[q][threadIdx.x] = x[q];
+    __syncthreads();
+    for (uint32_t stride = kBlock / 2; stride >= 1; stride >>= 1)
+    {
+        if (threadIdx.x < stride)
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                sh[q][threadIdx.x] = sh[q][threadIdx.x] + sh[q][threadIdx.x + stride];
+        __syncthreads();
+    }
+    if (threadIdx.x < 4)
+        row[threadIdx.x] = sh[threadIdx.x][0];
+}
+
+// Receivers: u and v of receiver r's node into the sample's rows, one thread per receiver (a gather proportional to
+// the receivers; a per-node slot read in the update pass would cost every step 4 B per node)
+__global__ __launch_bounds__(kBlock) void k_explicit_record(uint32_t count, const uint32_t *__restrict__ node,
+                                                            const float *__restrict__ u, const float *__restrict__ v,
+                                                            float *__restrict__ row_u, float *__restrict__ row_v)
+{
+    const uint32_t r = blockIdx.x * kBlock + threadIdx.x;
+    if (r >= count)
+        return;
+    const uint32_t n = node[r];
+    store3(row_u, r, load3(u, n));
+    store3(row_v, r, load3(v, n));
 }
 
 // w = f32(u + beta_R v): the operator's input of the first step after create or set_state (later steps' passes
@@ -229,18 +376,33 @@ __global__ __launch_bounds__(kBlock) void k_power_scale(uint32_t D, const float 
 template <bool FOLD, bool PATTERN>
 void launch_update(const DevSys &s, const ExplicitPass &a, hipStream_t st)
 {
-    // a stepper without dashpots launches the instantiations it always did
-    if (a.dslot)
+    // a stepper without dashpots, and one without peak maps and ledger, launches the instantiations it always did
+    const uint32_t grid = explicit_update_blocks(s.N);
+    if (a.peak || a.ecum)
+    {
+        if (a.dslot)
+        {
+            if (a.w != a.u)
+                k_explicit_update<FOLD, PATTERN, true, true, true><<<grid, kBlock, 0, st>>>(s, a);
+            else
+                k_explicit_update<FOLD, PATTERN, false, true, true><<<grid, kBlock, 0, st>>>(s, a);
+        }
+        else if (a.w != a.u)
+            k_explicit_update<FOLD, PATTERN, true, false, true><<<grid, kBlock, 0, st>>>(s, a);
+        else
+            k_explicit_update<FOLD, PATTERN, false, false, true><<<grid, kBlock, 0, st>>>(s, a);
+    }
+    else if (a.dslot)
     {
         if (a.w != a.u)
-            k_explicit_update<FOLD, PATTERN, true, true><<<grid_for(s.N, kBlock), kBlock, 0, st>>>(s, a);
+            k_explicit_update<FOLD, PATTERN, true, true, false><<<grid, kBlock, 0, st>>>(s, a);
         else
-            k_explicit_update<FOLD, PATTERN, false, true><<<grid_for(s.N, kBlock), kBlock, 0, st>>>(s, a);
+            k_explicit_update<FOLD, PATTERN, false, true, false><<<grid, kBlock, 0, st>>>(s, a);
     }
     else if (a.w != a.u)
-        k_explicit_update<FOLD, PATTERN, true, false><<<grid_for(s.N, kBlock), kBlock, 0, st>>>(s, a);
+        k_explicit_update<FOLD, PATTERN, true, false, false><<<grid, kBlock, 0, st>>>(s, a);
     else
-        k_explicit_update<FOLD, PATTERN, false, false><<<grid_for(s.N, kBlock), kBlock, 0, st>>>(s, a);
+        k_explicit_update<FOLD, PATTERN, false, false, false><<<grid, kBlock, 0, st>>>(s, a);
 }
 }  // namespace
 
@@ -253,6 +415,18 @@ void explicit_update(const DevSys &s, const ExplicitPass &a, hipStream_t st)
         pattern ? launch_update<true, true>(s, a, st) : launch_update<true, false>(s, a, st);
     else
         pattern ? launch_update<false, true>(s, a, st) : launch_update<false, false>(s, a, st);
+}
+
+void explicit_energy_fold(uint32_t blocks, const double *ecum, const double *ecur, double *row, hipStream_t st)
+{
+    k_explicit_energy_fold<<<1, kBlock, 0, st>>>(blocks, ecum, ecur, row);
+}
+
+void explicit_record(uint32_t count, const uint32_t *node, const float *u, const float *v, float *row_u, float *row_v,
+                     hipStream_t st)
+{
+    if (count)
+        k_explicit_record<<<grid_for(count, kBlock), kBlock, 0, st>>>(count, node, u, v, row_u, row_v);
 }
 
 void explicit_operator_input(uint32_t N, const float *u, const float *v, double beta, float *w, hipStream_t st)

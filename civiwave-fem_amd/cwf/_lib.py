@@ -106,6 +106,19 @@ class ExplicitTelemetryC(C.Structure):
                 ("steps", C.c_uint64), ("finite", C.c_int32), ("reserved", C.c_int32)]
 
 
+class ExplicitMonitorDescC(C.Structure):
+    _fields_ = [("receiver_count", C.c_uint64), ("receiver_nodes", C.c_void_p), ("receiver_every", C.c_uint64),
+                ("receiver_capacity", C.c_uint64), ("energy_every", C.c_uint64), ("energy_capacity", C.c_uint64),
+                ("peaks", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class ExplicitMonitorInfoC(C.Structure):
+    _fields_ = [("receiver_count", C.c_uint64), ("receiver_every", C.c_uint64), ("receiver_capacity", C.c_uint64),
+                ("receiver_samples", C.c_uint64), ("receiver_dropped", C.c_uint64), ("energy_every", C.c_uint64),
+                ("energy_capacity", C.c_uint64), ("energy_samples", C.c_uint64), ("energy_dropped", C.c_uint64),
+                ("peaks", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class ShardInfoC(C.Structure):
     _fields_ = [
         ("owned_nodes", C.c_uint64), ("local_nodes", C.c_uint64), ("local_elements", C.c_uint64),
@@ -211,6 +224,12 @@ def load() -> C.CDLL:
         "cwf_hip_explicit_time": ([P, P, P], i32),
         "cwf_hip_explicit_set_dashpots": ([P, u64, P, P], i32),
         "cwf_hip_explicit_get_dashpots": ([P, P, P, P], i32),
+        "cwf_hip_explicit_set_monitors": ([P, P], i32),
+        "cwf_hip_explicit_reset_monitors": ([P], i32),
+        "cwf_hip_explicit_monitor_info": ([P, P], i32),
+        "cwf_hip_explicit_read_receivers": ([P, u64, u64, P, P, P], i32),
+        "cwf_hip_explicit_read_peaks": ([P, P, P, P, u64, i32], i32),
+        "cwf_hip_explicit_read_energy": ([P, u64, u64, P, P], i32),
         "cwf_explicit_dashpot_update": ([P, f64, f64, f64, P, P], i32),
         "cwf_absorbing_dashpots": ([u64, P, u64, C.c_uint32, P, P, u64, P, P, P, u64, C.c_uint32, P, P, P, P], i32),
         "cwf_hip_lambda_max": ([P, C.c_uint32, P, P], i32),

@@ -37,6 +37,56 @@ class ExplicitTelemetry:
         return cls(t.time, t.dt, t.lambda_max, t.critical_dt, int(t.steps), bool(t.finite))
 
 
+@dataclass
+class MonitorInfo:
+    receiver_count: int
+    receiver_every: int
+    receiver_capacity: int
+    receiver_samples: int
+    receiver_dropped: int
+    energy_every: int
+    energy_capacity: int
+    energy_samples: int
+    energy_dropped: int
+    peaks: bool
+
+
+@dataclass
+class ReceiverTraces:
+    """Rows of the receiver buffers: u_n and v_(n-1/2) at the step counts ``steps`` (time = steps x dt)."""
+    steps: np.ndarray   # u64 [samples]
+    time: np.ndarray    # f64 [samples]
+    u: np.ndarray       # f32 [samples, receivers, 3]
+    v: np.ndarray       # f32 [samples, receivers, 3]
+    dt: float
+    every: int
+
+    def acceleration(self) -> np.ndarray:
+        """The central acceleration (v_(n+1/2) - v_(n-1/2)) / dt at t_n of rows 0 .. samples - 2, f64
+        [samples - 1, receivers, 3]; needs every step recorded (receiver_every == 1)."""
+        if self.every != 1 or (self.steps.size > 1 and np.any(np.diff(self.steps.astype(np.int64)) != 1)):
+            raise ValueError("acceleration() needs receiver_every == 1")
+        return np.diff(self.v.astype(np.float64), axis=0) / self.dt
+
+
+@dataclass
+class EnergyLedger:
+    """The ledger's rows (include/cwf_hip.h "Monitors"): work and dissipated are cumulative since set or reset."""
+    steps: np.ndarray
+    time: np.ndarray
+    kinetic: np.ndarray
+    potential: np.ndarray
+    work: np.ndarray
+    dissipated: np.ndarray
+
+    def total(self) -> np.ndarray:
+        return self.kinetic + self.potential
+
+    def balance(self) -> np.ndarray:
+        """total - work + dissipated: constant along a run up to rounding."""
+        return self.total() - self.work + self.dissipated
+
+
 def lambda_max(system: MatrixFreeSystem, iterations: int = 60):
     """-> (estimate of the largest eigenvalue of M^-1 K over the free DOFs, the last iteration's relative change)."""
     lam, change = C.c_double(), C.c_double()
@@ -138,3 +188,53 @@ class ExplicitStepper(TransientState):
 
     def clear_dashpots(self):
         self._check(_lib.load().cwf_hip_explicit_set_dashpots(self._ex, 0, None, None))
+
+    # ---- monitors (include/cwf_hip.h "Monitors") ----
+    def set_monitors(self, receivers=None, receiver_every: int = 1, receiver_capacity: int = 0, peaks: bool = False,
+                     energy_every: int = 0, energy_capacity: int = 0):
+        """Receiver traces at the nodes ``receivers`` (distinct ids) every ``receiver_every`` steps, peak maps, and the
+        energy ledger every ``energy_every`` steps (0: none); capacities in samples. Replaces the previous set, which
+        stays in force if this one is refused (RuntimeError)."""
+        nodes = np.zeros(0, np.uint32) if receivers is None else np.ascontiguousarray(receivers, np.uint32).reshape(-1)
+        d = _lib.ExplicitMonitorDescC(nodes.size, _lib.ptr(nodes) if nodes.size else None,
+                                      int(receiver_every) if nodes.size else 0,
+                                      int(receiver_capacity) if nodes.size else 0, int(energy_every),
+                                      int(energy_capacity) if energy_every else 0, 1 if peaks else 0, 0)
+        self._check(_lib.load().cwf_hip_explicit_set_monitors(self._ex, C.byref(d)))
+
+    def clear_monitors(self):
+        self._check(_lib.load().cwf_hip_explicit_set_monitors(self._ex, None))
+
+    def reset_monitors(self):
+        """The same set: sample counts rewound, peaks and cumulative sums zeroed."""
+        self._check(_lib.load().cwf_hip_explicit_reset_monitors(self._ex))
+
+    def monitor_info(self) -> MonitorInfo:
+        i = _lib.ExplicitMonitorInfoC()
+        self._check(_lib.load().cwf_hip_explicit_monitor_info(self._ex, C.byref(i)))
+        return MonitorInfo(*(int(getattr(i, n)) for n, _ in _lib.ExplicitMonitorInfoC._fields_[:9]), bool(i.peaks))
+
+    def receiver_traces(self) -> ReceiverTraces:
+        i = self.monitor_info()
+        n, r = i.receiver_samples, i.receiver_count
+        steps = np.zeros(n, np.uint64)
+        u, v = np.zeros((n, r, 3), np.float32), np.zeros((n, r, 3), np.float32)
+        self._check(_lib.load().cwf_hip_explicit_read_receivers(self._ex, 0, n, _lib.ptr(steps), _lib.ptr(u),
+                                                                _lib.ptr(v)))
+        dt = self.time_step()
+        return ReceiverTraces(steps, steps.astype(np.float64) * dt, u, v, dt, i.receiver_every)
+
+    def peaks(self):
+        """-> (peak_u, peak_v, peak_a), f32 [N] each, the caller's node order."""
+        out = [np.zeros(self.node_count, np.float32) for _ in range(3)]
+        self._check(_lib.load().cwf_hip_explicit_read_peaks(self._ex, _lib.ptr(out[0]), _lib.ptr(out[1]),
+                                                            _lib.ptr(out[2]), self.node_count, _lib.PTR_HOST))
+        return tuple(out)
+
+    def energy(self) -> EnergyLedger:
+        n = self.monitor_info().energy_samples
+        steps = np.zeros(n, np.uint64)
+        rows = np.zeros((n, 4), np.float64)
+        self._check(_lib.load().cwf_hip_explicit_read_energy(self._ex, 0, n, _lib.ptr(steps), _lib.ptr(rows)))
+        return EnergyLedger(steps, steps.astype(np.float64) * self.time_step(), rows[:, 0].copy(), rows[:, 1].copy(),
+                            rows[:, 2].copy(), rows[:, 3].copy())

@@ -3,6 +3,7 @@
     python -m cwf.run scenario.yaml [--steps N] [--out DIR] [--mode parity|fast] [--paused]
                                     [--time-varying-loads] [--device K]
                                     [--integrator newmark|explicit] [--safety 0.9]
+                                    [--trace-every K] [--peaks] [--energy-every K] [--mass-damping-only]
 
 The reference has no such executable (SURVEY.md section 0.4: its only binary is the viewer demo);
 this wires its pieces in the order the viewer backend does (src/ui/viewer.cpp:200-277):
@@ -17,6 +18,10 @@ step instead: ``--steps`` still counts output frames, one every ceil(dt_scenario
 scenario's ``time.dt`` is the output interval), through the same VTU and probe writers; loads are those of t = 0.
 A scenario's ``absorbing:`` entries (explicit only) put viscous dashpots on their groups' faces; an entry's
 ``incident: {direction, velocity_curve}`` feeds that curve in through the dashpots as an incident wave.
+``--trace-every K``, ``--peaks`` and ``--energy-every K`` (explicit only) turn on the stepper's monitors: receiver
+traces at ``output.probes`` every K explicit steps (``probes/traces.csv``), the peak |u|, |v|, |a| maps
+(``monitors/peaks.npy``, [N,3]) and the energy ledger (``monitors/energy.csv``), written after the last frame. The
+ledger needs beta_R == 0, which no scenario's ``damping:`` gives: ``--mass-damping-only`` keeps alpha_R and drops beta_R.
 
 Mesh paths are resolved like the reference (relative to the working directory) and, failing that,
 relative to the YAML file's directory. One JSON line per step is printed; the last line is a summary.
@@ -106,16 +111,22 @@ def run_scenario(cfg_path: str, steps: int, out_dir: str | None, mode: int = _li
 
 
 def run_scenario_explicit(cfg_path: str, steps: int, out_dir: str | None, mode: int = _lib.MODE_PARITY,
-                          device: int = 0, safety: float = 0.9, log=print) -> dict:
-    """`steps` output frames of the explicit stepper, ceil(cfg.time.initial_dt / dt) explicit steps each."""
+                          device: int = 0, safety: float = 0.9, log=print, trace_every: int = 0, peaks: bool = False,
+                          energy_every: int = 0, mass_damping_only: bool = False) -> dict:
+    """`steps` output frames of the explicit stepper, ceil(cfg.time.initial_dt / dt) explicit steps each.
+    trace_every / peaks / energy_every: the stepper's monitors (receivers at cfg.output.probes), written under
+    out_dir after the last frame; their capacities follow from `steps`. mass_damping_only: the stepper gets the
+    scenario's alpha_R and beta_R = 0 (a scenario's damping always has beta_R > 0, which the energy ledger refuses)."""
     import math
 
     from .explicit import ExplicitStepper
 
     cfg, m, P, materials = load_scenario(cfg_path, allow_hex8=mode == _lib.MODE_FAST)
+    rayleigh = compute_rayleigh(cfg.damping)
+    if mass_damping_only:
+        rayleigh = type(rayleigh)(rayleigh.alpha, 0.0)
     try:
-        st = ExplicitStepper(P, materials, compute_rayleigh(cfg.damping), cfg.solver, cfg.time, safety=safety,
-                             mode=mode, device=device)
+        st = ExplicitStepper(P, materials, rayleigh, cfg.solver, cfg.time, safety=safety, mode=mode, device=device)
     except RuntimeError as e:
         raise ScenarioError(str(e)) from None
     om = post.OutputManager(out_dir, m, P, materials, cfg.output, stepper=st) if out_dir else None
@@ -124,6 +135,18 @@ def run_scenario_explicit(cfg_path: str, steps: int, out_dir: str | None, mode: 
         absorbing_nodes = set_absorbing(st, cfg, m, P)
         tel = st.telemetry()
         per_frame = max(1, math.ceil(cfg.time.initial_dt / tel.dt))
+        monitored = trace_every > 0 or peaks or energy_every > 0
+        if monitored:
+            total = steps * per_frame
+            if trace_every > 0 and not cfg.output.probes:
+                raise ScenarioError("--trace-every needs output.probes")
+            try:
+                st.set_monitors(receivers=list(cfg.output.probes) if trace_every > 0 else None,
+                                receiver_every=max(trace_every, 1), receiver_capacity=max(total // max(trace_every, 1), 1),
+                                peaks=peaks, energy_every=max(energy_every, 0),
+                                energy_capacity=max(total // max(energy_every, 1), 1))
+            except RuntimeError as e:
+                raise ScenarioError(str(e)) from None
         for frame in range(steps):
             r = st.advance(per_frame)
             if not r.has_value():
@@ -135,16 +158,51 @@ def run_scenario_explicit(cfg_path: str, steps: int, out_dir: str | None, mode: 
                     raise ScenarioError(f"output frame {frame}: {o.error().message} {o.error().context}")
             last = dict(frame=frame, time=tel.time, dt=tel.dt, steps=tel.steps)
             log(json.dumps(last))
+        written = write_monitors(st, out_dir, cfg.output.probes, trace_every > 0, peaks, energy_every > 0) \
+            if monitored and out_dir else {}
         wall = time.perf_counter() - wall0
         return dict(scenario=cfg_path, nodes=P.node_count, tets=P.element_count, dofs=P.dof_count, steps=steps,
                     integrator="explicit", explicit_steps=tel.steps, steps_per_frame=per_frame, dt=tel.dt,
                     critical_dt=tel.critical_dt, lambda_max=tel.lambda_max, wall_s=wall, final_time=tel.time,
-                    last=last, mode="fast" if mode == _lib.MODE_FAST else "parity", absorbing_nodes=absorbing_nodes)
+                    last=last, mode="fast" if mode == _lib.MODE_FAST else "parity", absorbing_nodes=absorbing_nodes,
+                    **written)
     finally:
         if om is not None:
             om.close()
         st.close()
         st.system.close()
+
+
+def write_monitors(st, out_dir, probes, traces: bool, peaks: bool, energy: bool) -> dict:
+    """The stepper's monitors as files under out_dir: probes/traces.csv (step,time,node,ux,uy,uz,vx,vy,vz; one row per
+    sample and probe), monitors/peaks.npy ([N,3]: |u|, |v|, |a|) and monitors/energy.csv -> the summary's entries."""
+    import os
+
+    import numpy as np
+
+    out = {}
+    if traces:
+        os.makedirs(os.path.join(out_dir, "probes"), exist_ok=True)
+        tr = st.receiver_traces()
+        with open(os.path.join(out_dir, "probes", "traces.csv"), "w") as f:
+            f.write("step,time,node,ux,uy,uz,vx,vy,vz\n")
+            for i in range(tr.steps.size):
+                for r, node in enumerate(probes):
+                    vals = ",".join(repr(float(x)) for x in (*tr.u[i, r], *tr.v[i, r]))
+                    f.write(f"{int(tr.steps[i])},{float(tr.time[i])!r},{int(node)},{vals}\n")
+        out["trace_samples"] = int(tr.steps.size)
+    if peaks or energy:
+        os.makedirs(os.path.join(out_dir, "monitors"), exist_ok=True)
+    if peaks:
+        np.save(os.path.join(out_dir, "monitors", "peaks.npy"), np.stack(st.peaks(), axis=1))
+    if energy:
+        e = st.energy()
+        with open(os.path.join(out_dir, "monitors", "energy.csv"), "w") as f:
+            f.write("step,time,kinetic,potential,work,dissipated,balance\n")
+            for row in zip(e.steps, e.time, e.kinetic, e.potential, e.work, e.dissipated, e.balance()):
+                f.write(f"{int(row[0])}," + ",".join(repr(float(x)) for x in row[1:]) + "\n")
+        out["energy_samples"] = int(e.steps.size)
+    return out
 
 
 def absorbing_setup(cfg, m, P):
@@ -203,15 +261,28 @@ def main(argv=None) -> int:
     ap.add_argument("--time-varying-loads", action="store_true")
     ap.add_argument("--integrator", choices=["newmark", "explicit"], default="newmark")
     ap.add_argument("--safety", type=float, default=0.9, help="explicit: fraction of the critical step")
+    ap.add_argument("--trace-every", type=int, default=0, metavar="K",
+                    help="explicit: receiver traces at output.probes every K steps -> <out>/probes/traces.csv")
+    ap.add_argument("--peaks", action="store_true", help="explicit: peak |u|, |v|, |a| maps -> <out>/monitors/peaks.npy")
+    ap.add_argument("--energy-every", type=int, default=0, metavar="K",
+                    help="explicit: energy ledger every K steps -> <out>/monitors/energy.csv (needs beta_R == 0: "
+                         "--mass-damping-only)")
+    ap.add_argument("--mass-damping-only", action="store_true",
+                    help="explicit: keep the scenario's alpha_R and drop its stiffness-proportional beta_R")
     a = ap.parse_args(argv)
     try:
         if a.integrator == "explicit":
             if a.time_varying_loads or a.paused:
                 raise ScenarioError("--time-varying-loads and --paused belong to the newmark integrator")
             s = run_scenario_explicit(a.scenario, a.steps, a.out,
-                                      _lib.MODE_FAST if a.mode == "fast" else _lib.MODE_PARITY, a.device, a.safety)
+                                      _lib.MODE_FAST if a.mode == "fast" else _lib.MODE_PARITY, a.device, a.safety,
+                                      trace_every=a.trace_every, peaks=a.peaks, energy_every=a.energy_every,
+                                      mass_damping_only=a.mass_damping_only)
             print(json.dumps(dict(summary=s)))
             return 0
+        if a.trace_every or a.peaks or a.energy_every or a.mass_damping_only:
+            raise ScenarioError("--trace-every, --peaks, --energy-every and --mass-damping-only belong to the explicit "
+                                "integrator")
         s = run_scenario(a.scenario, a.steps, a.out, _lib.MODE_FAST if a.mode == "fast" else _lib.MODE_PARITY,
                          a.device, a.paused, a.time_varying_loads)
     except ScenarioError as e:

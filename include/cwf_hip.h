@@ -442,6 +442,39 @@ int cwf_hip_stepper_time(const cwf_hip_stepper *st, double *current_time, double
  * C >= 0, however large; per node the eigenvalues of P are ((1 - h) - b) / ((1 + h) + b) with b >= 0 those of B, inside
  * (-1, 1]. So critical_dt and lambda_max are those of the stepper without dashpots, and dashpots scaled by 1e4 run at
  * the same step (tests/test_gpu_absorbing.py).
+ *
+ * Monitors (cwf_hip_explicit_set_monitors): what a wave run takes home, recorded on the device while advance() queues
+ * its steps. "Step count n" is the number of steps since create; after the update that makes it n the state is u_n and
+ * v_(n-1/2). A stepper without monitors launches exactly the kernels it launches without this section.
+ *   Receivers: after the update that makes the step count n, when n % receiver_every == 0 and a row is free, a gather
+ *     kernel (one thread per receiver) writes u_n and v_(n-1/2) of the receiver nodes to row `held` of two device
+ *     buffers [capacity][count][3], in the caller's receiver order. A full buffer drops the sample and counts it.
+ *   Peak maps: three f32 per node, zero at set and at reset, raised in the update pass from the values it stores (a
+ *     constrained DOF enters with u = bc_value, v = 0), each with max(p, x) = x > p ? x : p (a NaN never raises a peak):
+ *       peak_u: x = f32(sqrt(((double)un_0 un_0 + (double)un_1 un_1) + (double)un_2 un_2))       un = u_(n+1)
+ *       peak_v: the same of vn = v_(n+1/2)
+ *       peak_a: the same of a_k = ((double)vn_k - (double)v_k) / dt, the central acceleration at t_n
+ *   Energy ledger (needs beta_R == 0): per free DOF k of node n in the update of step i (step count i -> i + 1), in
+ *     fp64 without fused multiply-adds, m = (double)mass[n], y = K u_i as the pass holds it (f32):
+ *       vb   = 0.5 * ((double)vn_k + (double)v_k)
+ *       kin  = 0.5 * (m * ((double)vn_k * (double)vn_k))
+ *       pot  = 0.5 * ((double)un_k * (double)y_k)
+ *       work = dt * (vb * (double)f_k)
+ *       diss = dt * (alpha_R * (m * (vb * vb)))
+ *            + (dashpot node) dt * (vb_k * ((C_k0 vb_0 + C_k1 vb_1) + C_k2 vb_2))     C as given to set_dashpots
+ *     A constrained DOF contributes 0 to all four (its vb, from the stored vn = 0, still enters a dashpot row). With
+ *     H_i = sum kin + sum pot = 1/2 v+^T M v+ + 1/2 u_(i+1)^T K u_i the scheme satisfies, in exact arithmetic,
+ *     H_i - H_(i-1) = sum work_i - sum diss_i, dashpots and alpha_R included, so
+ *     kinetic + potential - work_cum + dissipated_cum is constant along a run: the number the ledger exists to show.
+ *     Summation order (a function of N alone): a node adds its components (t_0 + t_1) + t_2; a workgroup of the update
+ *     pass holds nodes 256 b .. 256 b + 255 (internal order; lanes past N carry zeros) and reduces them in a fixed
+ *     tree: within each 64-lane wave x += x[lane + 32], + 16, + 8, + 4, + 2, + 1, then (w_0 + w_1) + (w_2 + w_3) over
+ *     its four waves. Work and dissipation are added every step to the workgroup's own two fp64 accumulators
+ *     (acc = acc + share; no atomics); kinetic and potential are written to its two "current" slots on sampled steps.
+ *     The update that makes the step count n is sampled when n % energy_every == 0 and a row is free; a one-workgroup
+ *     kernel then folds the shares: thread t adds workgroups t, t + 256, ... in that order from 0, the 256 sums fold
+ *     pairwise (s[t] += s[t + stride], stride 128 ... 1) into the row {kinetic, potential, work_cum, dissipated_cum}.
+ *     The cumulative columns include the unsampled steps; a full buffer drops rows, not sums.
  * ------------------------------------------------------------------------------------- */
 typedef struct cwf_explicit_desc
 {
@@ -495,10 +528,54 @@ int cwf_hip_explicit_time(const cwf_hip_explicit *ex, double *current_time, doub
  * count == 0 removes it (the stepper then launches what a stepper that never had dashpots launches). Errors, all
  * CWF_ERR_ARGUMENT and leaving the previous set in force: "dashpot node out of range" {index=<i>, node=<id>},
  * "dashpot node listed twice" {index=<i>, node=<id>}, and a refused matrix (cwf_explicit_dashpot_update's texts)
- * {index=<i>}. A dashpot on a constrained DOF has no effect: the mask wins. */
+ * {index=<i>}. A dashpot on a constrained DOF has no effect: the mask wins. While an energy ledger is set
+ * (cwf_hip_explicit_set_monitors) the matrices as given are uploaded too, 72 bytes per dashpot node indexed by the same
+ * slot and read only by the ledger, and a later set replaces them with the records. */
 int cwf_hip_explicit_set_dashpots(cwf_hip_explicit *ex, uint64_t count, const uint32_t *node_ids, const double *C);
 /* The set in force as it was given; node_ids and C are nullable (count only). */
 int cwf_hip_explicit_get_dashpots(cwf_hip_explicit *ex, uint64_t *count, uint32_t *node_ids, double *C);
+/* Monitors of the scheme above. Replaces the previous set; desc NULL or all zero removes everything and frees the
+ * buffers (the stepper then launches what a stepper that never had monitors launches). u, v, the step count, loads and
+ * dashpots are kept; peaks, cumulative sums and sample counts start at zero. May be called between advance calls. All
+ * buffers are allocated here, in the stepper's arena. Everything refusable is checked before anything changes, and a
+ * refusal leaves the previous set in force: CWF_ERR_ARGUMENT "receiver node out of range" {index=<i>, node=<id>},
+ * "receiver node listed twice" {index=<i>, node=<id>}, "receiver_every must be at least 1", "monitor capacity must not
+ * be zero" (a zero capacity with a non-zero count / every), "null pointer"; CWF_ERR_UNSUPPORTED "the energy ledger
+ * needs rayleigh_beta == 0" {rayleigh_beta=<beta>}; CWF_ERR_ALLOC. */
+typedef struct cwf_explicit_monitor_desc
+{
+    uint64_t receiver_count;
+    const uint32_t *receiver_nodes; /* [receiver_count] distinct nodes, the caller's numbering */
+    uint64_t receiver_every;        /* >= 1 when receiver_count > 0 */
+    uint64_t receiver_capacity;     /* samples (rows) */
+    uint64_t energy_every;          /* 0: no ledger */
+    uint64_t energy_capacity;       /* samples (rows) */
+    uint32_t peaks;                 /* 0 / 1 */
+    uint32_t reserved;
+} cwf_explicit_monitor_desc;
+
+typedef struct cwf_explicit_monitor_info
+{
+    uint64_t receiver_count, receiver_every, receiver_capacity, receiver_samples, receiver_dropped;
+    uint64_t energy_every, energy_capacity, energy_samples, energy_dropped;
+    uint32_t peaks, reserved;
+} cwf_explicit_monitor_info;
+
+int cwf_hip_explicit_set_monitors(cwf_hip_explicit *ex, const cwf_explicit_monitor_desc *desc);
+/* The same set: sample counts rewound, peaks and cumulative sums zeroed. */
+int cwf_hip_explicit_reset_monitors(cwf_hip_explicit *ex);
+/* Samples held and dropped (a full buffer drops further samples and counts them; stepping goes on). */
+int cwf_hip_explicit_monitor_info(cwf_hip_explicit *ex, cwf_explicit_monitor_info *info);
+/* Rows first .. first + count - 1 of the receiver buffers into host memory: steps [count] (the step count of each row;
+ * time = steps x dt), u and v [count][receivers][3], each nullable. CWF_ERR_ARGUMENT "monitor rows out of range"
+ * {first=<first>, count=<count>, held=<rows held>}. */
+int cwf_hip_explicit_read_receivers(cwf_hip_explicit *ex, uint64_t first, uint64_t count, uint64_t *steps, float *u,
+                                    float *v);
+/* The peak maps, [N] each in the caller's node order, each nullable; n = N. CWF_ERR_ARGUMENT "no peak maps are set". */
+int cwf_hip_explicit_read_peaks(cwf_hip_explicit *ex, float *peak_u, float *peak_v, float *peak_a, uint64_t n,
+                                int ptr_kind);
+/* Ledger rows into host memory: steps [count], rows [count][4] = {kinetic, potential, work_cum, dissipated_cum}. */
+int cwf_hip_explicit_read_energy(cwf_hip_explicit *ex, uint64_t first, uint64_t count, uint64_t *steps, double *rows);
 /* Host only, no GPU: P and Q of the scheme above from C (row-major), the node's mass, alpha_R and dt, by the
  * closed-form 3x3 inverse. CWF_ERR_ARGUMENT for a C that is not finite ("dashpot matrix is not finite"), not symmetric
  * (|C_ij - C_ji| > 1e-12 trace: "dashpot matrix is not symmetric") or not positive semidefinite (a principal minor

@@ -3,6 +3,7 @@
 
     python tools/explicit_bench.py [--configs c2 c3 c2:hex8] [--steps 2000] [--newmark-steps 3] [--out FILE]
     python tools/explicit_bench.py --absorbing [--configs c3] [--steps 2000]
+    python tools/explicit_bench.py --monitors [--configs c2 c3] [--steps 2000]
 
 Per config (a FAST handle of the block, created with scalars (1, 0)), in one process and one JSON line each, appended
 to --out (default profiles/explicit_c2.json):
@@ -19,6 +20,11 @@ to --out (default profiles/explicit_c2.json):
 profiles/explicit_absorbing.json: step_us of the stepper without dashpots, with viscous dashpots (cwf.absorbing) on the
 five faces of the block other than z = max, and after clear_dashpots again, in one process on one handle; the share
 of dashpot nodes and the bytes per node the update pass then moves (84 + 144 x share).
+
+--monitors: the cost of the stepper's monitors. Per config one line, appended to profiles/explicit_monitors.json:
+step_us of one stepper on one handle without monitors, with peak maps only, with the ledger only (energy_every 1 and
+100), with 64 receivers (every 1 and 10), with everything together, and after clear_monitors again, next to the
+estimate from bytes (the update pass's 80 B per node plus what the monitor moves, scaled from the plain step).
 """
 import argparse
 import ctypes as C
@@ -143,6 +149,45 @@ def measure_absorbing(key, steps, device):
     return out
 
 
+def measure_monitors(key, steps, device):
+    import numpy as np
+
+    name, _, element = key.partition(":")
+    case = scenarios.config_case(name, element=element or "tet4")
+    P = case.packing
+    N = P.node_count
+    sysm = pcg.MatrixFreeSystem.from_packing(P, case.materials, 1.0, 0.0, mode=_lib.MODE_FAST, device=device)
+    out = dict(config=key, name=case.name, nodes=N, steps=steps,
+               kernel=(_lib.load().cwf_hip_system_keff_kernel(sysm.handle()) or b"").decode())
+    ex = ExplicitStepper(P, case.materials, RayleighCoefficients(0.0, 0.0), system=sysm)
+    out["dt"] = ex.telemetry().dt
+    receivers = np.random.Generator(np.random.PCG64(5)).permutation(N)[:64]
+    total = 200 + steps  # timed_steps warms up with 200 steps
+    sets = [
+        ("plain", None),
+        ("peaks", dict(peaks=True)),
+        ("ledger_every_1", dict(energy_every=1, energy_capacity=total)),
+        ("ledger_every_100", dict(energy_every=100, energy_capacity=total // 100 + 1)),
+        ("receivers64_every_1", dict(receivers=receivers, receiver_every=1, receiver_capacity=total)),
+        ("receivers64_every_10", dict(receivers=receivers, receiver_every=10, receiver_capacity=total // 10 + 1)),
+        ("all", dict(receivers=receivers, receiver_every=1, receiver_capacity=total, peaks=True, energy_every=1,
+                     energy_capacity=total)),
+        ("cleared", None),
+    ]
+    for label, kw in sets:
+        if kw is None:
+            ex.clear_monitors()
+        else:
+            ex.set_monitors(**kw)
+        out["step_us_" + label] = timed_steps(ex, steps)
+    # bytes per node of the update pass: 80 plain; peaks at most +24 (three 4-B loads, up to three 4-B stores);
+    # the ledger +32 B per 256-node workgroup every step (its two accumulators read and written)
+    out["update_bytes_per_node"] = dict(plain=80, peaks=104, ledger=80 + 32 / 256, all=104 + 32 / 256)
+    ex.close()
+    sysm.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", nargs="+", default=["c2", "c3", "c2:hex8"])
@@ -150,13 +195,19 @@ def main():
     ap.add_argument("--newmark-steps", type=int, default=3)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--absorbing", action="store_true", help="the cost of dashpots on five faces (see above)")
+    ap.add_argument("--monitors", action="store_true", help="the cost of the monitors (see above)")
     ap.add_argument("--out", default=None, help="default profiles/explicit_c2.json (--absorbing: "
-                                                 "profiles/explicit_absorbing.json)")
+                                                 "profiles/explicit_absorbing.json, --monitors: "
+                                                 "profiles/explicit_monitors.json)")
     a = ap.parse_args()
-    a.out = a.out or os.path.join(ROOT, "profiles", "explicit_absorbing.json" if a.absorbing else "explicit_c2.json")
+    a.out = a.out or os.path.join(ROOT, "profiles", "explicit_monitors.json" if a.monitors else
+                                  "explicit_absorbing.json" if a.absorbing else "explicit_c2.json")
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    for key in (["c3"] if a.absorbing and a.configs == ap.get_default("configs") else a.configs):
-        line = json.dumps(measure_absorbing(key, a.steps, a.device) if a.absorbing else
+    if a.configs == ap.get_default("configs"):
+        a.configs = ["c2", "c3"] if a.monitors else ["c3"] if a.absorbing else a.configs
+    for key in a.configs:
+        line = json.dumps(measure_monitors(key, a.steps, a.device) if a.monitors else
+                          measure_absorbing(key, a.steps, a.device) if a.absorbing else
                           measure(key, a.steps, a.newmark_steps, a.device))
         print(line, flush=True)
         with open(a.out, "a") as f:
