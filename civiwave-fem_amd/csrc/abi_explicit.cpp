@@ -1,7 +1,7 @@
 // abi_explicit.cpp -- the explicit central-difference stepper of the C-ABI (include/cwf_hip.h "Explicit stepper"):
 // create with the stable-step estimate (power iteration on M^-1 K), advance (per step: the handle's operator at
 // scalars (1, 0) on a copy of its DevSys, then the node pass of explicit.hip), state access, the external force,
-// its load pattern and curve, and the two host-only helpers.
+// its load pattern and curve, the load sources, and the two host-only helpers.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -48,6 +48,26 @@ struct cwf_hip_explicit : TransientState
         }
     } mon;
     double *dC = nullptr;  // the ledger's slot-indexed C array (arena), while a ledger and dashpots are both set
+    // set_sources: the set in force as given (get_sources) and its device arrays (the stepper's arena); dev.loaded == 0:
+    // no set
+    struct Sources
+    {
+        struct Given
+        {
+            std::vector<double> times, values, amplitude, delay;
+            std::vector<uint32_t> ids;
+        };
+        std::vector<Given> given;
+        uint64_t entries = 0, points = 0, bytes = 0;
+        ExplicitSources dev{};
+        void release(DeviceArena &mem)
+        {
+            for (const void *p : {(const void *)dev.node, (const void *)dev.off, (const void *)dev.rec,
+                                  (const void *)dev.cur, (const void *)dev.tab, (const void *)dev.fext})
+                mem.free(const_cast<void *>(p));
+            *this = Sources();
+        }
+    } src;
 };
 
 namespace
@@ -300,6 +320,8 @@ int cwf_hip_explicit_advance(cwf_hip_explicit *t, uint64_t n_steps, cwf_explicit
             fast_keff_partials_ds(s, t->w, true, st);
         else
             parity_keff_ds(s, t->w, t->y, true, nullptr, st);
+        if (t->src.dev.loaded)  // f_n of the loaded nodes into the force buffer the update pass reads
+            explicit_sources(t->src.dev, (double)t->steps * t->dt, t->f, st);
         const bool edue = mon.eevery && (t->steps + 1) % mon.eevery == 0;
         a.esample = edue && mon.esteps.size() < mon.ecap ? 1u : 0u;
         explicit_update(s, a, st);
@@ -368,13 +390,25 @@ int cwf_hip_explicit_set_external_force(cwf_hip_explicit *t, const float *f, uin
 {
     if (!t || !f)
         return set_error(nullptr, CWF_ERR_ARGUMENT, "null pointer");
-    return transient_set(*t, "external force", t->f, f, n, kind);
+    if (int st = transient_set(*t, "external force", t->f, f, n, kind))
+        return st;
+    if (t->src.dev.loaded)  // the loaded nodes' f_ext follows
+    {
+        cwf_hip_system *h = t->sys;
+        explicit_sources_fext(t->src.dev, t->f, true, h->stream);
+        HIPTRY(h, hipGetLastError());
+        HIPTRY(h, hipStreamSynchronize(h->stream));
+    }
+    return 0;
 }
 
 int cwf_hip_explicit_set_load_pattern(cwf_hip_explicit *t, const double *base, const double *pattern, uint64_t n)
 {
     if (!t || !base || !pattern)
         return set_error(nullptr, CWF_ERR_ARGUMENT, "null pointer");
+    if (t->src.dev.loaded)
+        return set_error(t->sys, CWF_ERR_UNSUPPORTED, "load sources and a load pattern exclude each other",
+                         "sources=" + std::to_string(t->src.given.size()));
     return transient_set_load_pattern(*t, base, pattern, n);
 }
 
@@ -488,6 +522,217 @@ int cwf_hip_explicit_get_dashpots(cwf_hip_explicit *t, uint64_t *count, uint32_t
         std::copy(t->dash_ids.begin(), t->dash_ids.end(), node_ids);
     if (C)
         std::copy(t->dash_C.begin(), t->dash_C.end(), C);
+    return 0;
+}
+
+int cwf_hip_explicit_set_sources(cwf_hip_explicit *t, const cwf_explicit_source_desc *sources, uint32_t count)
+{
+    if (!t)
+        return set_error(nullptr, CWF_ERR_ARGUMENT, "null handle");
+    cwf_hip_system *h = t->sys;
+    if (int st = check_ready(h))
+        return st;
+    hipStream_t s = h->stream;
+    cwf_hip_explicit::Sources &cur = t->src;
+    if (count == 0)
+    {
+        if (cur.dev.loaded)
+        {
+            explicit_sources_fext(cur.dev, t->f, false, s);  // f_ext back into the force buffer
+            HIPTRY(h, hipGetLastError());
+            HIPTRY(h, hipStreamSynchronize(s));
+        }
+        cur.release(t->mem);
+        return 0;
+    }
+    // everything that can be refused, on the host, before anything changes
+    if (!sources)
+        return set_error(h, CWF_ERR_ARGUMENT, "null pointer");
+    if (count > CWF_EXPLICIT_MAX_SOURCES)
+        return set_error(h, CWF_ERR_SIZE, "too many load sources",
+                         "count=" + std::to_string(count) + "\nmax=" + std::to_string(CWF_EXPLICIT_MAX_SOURCES));
+    if (t->lbase)
+        return set_error(h, CWF_ERR_UNSUPPORTED, "load sources and a load pattern exclude each other");
+    const uint64_t N = h->ds.N;
+    const uint32_t kNone = 0xFFFFFFFFu;
+    std::vector<uint32_t> slot(std::max<uint64_t>(N, 4), kNone);  // caller's node -> its index among the loaded nodes
+    std::vector<uint32_t> seen(std::max<uint64_t>(N, 4), kNone);  // caller's node -> the last source that listed it
+    uint64_t entries = 0, points = 0, nodes = 0;
+    for (uint32_t q = 0; q < count; ++q)
+    {
+        const cwf_explicit_source_desc &d = sources[q];
+        const std::string sq = "source=" + std::to_string(q);
+        if (d.curve_points < 1 || d.curve_points > CWF_EXPLICIT_MAX_CURVE_POINTS)
+            return set_error(h, CWF_ERR_SIZE, "load source curve must have 1 to 4096 points",
+                             sq + "\ncount=" + std::to_string(d.curve_points));
+        if (!d.entry_count)
+            return set_error(h, CWF_ERR_ARGUMENT, "load source has no entries", sq);
+        if (!d.times || !d.values || !d.node_ids || !d.amplitude || !d.delay)
+            return set_error(h, CWF_ERR_ARGUMENT, "null pointer", sq);
+        for (uint64_t i = 0; i < d.curve_points; ++i)
+        {
+            if (!std::isfinite(d.times[i]) || !std::isfinite(d.values[i]))
+                return set_error(h, CWF_ERR_ARGUMENT, "load source curve is not finite",
+                                 sq + "\nindex=" + std::to_string(i));
+            if (i && !(d.times[i] >= d.times[i - 1]))
+                return set_error(h, CWF_ERR_ARGUMENT, "load source curve times must ascend",
+                                 sq + "\nindex=" + std::to_string(i));
+        }
+        for (uint64_t i = 0; i < d.entry_count; ++i)
+        {
+            const uint32_t node = d.node_ids[i];
+            const std::string at = sq + "\nindex=" + std::to_string(i);
+            if (node >= N)
+                return set_error(h, CWF_ERR_ARGUMENT, "load source node out of range",
+                                 at + "\nnode=" + std::to_string(node));
+            if (seen[node] == q)
+                return set_error(h, CWF_ERR_ARGUMENT, "load source node listed twice",
+                                 at + "\nnode=" + std::to_string(node));
+            seen[node] = q;
+            if (!std::isfinite(d.delay[i]) || !std::isfinite(d.amplitude[3 * i]) ||
+                !std::isfinite(d.amplitude[3 * i + 1]) || !std::isfinite(d.amplitude[3 * i + 2]))
+                return set_error(h, CWF_ERR_ARGUMENT, "load source entry is not finite", at);
+            if (slot[node] == kNone)
+                slot[node] = (uint32_t)nodes++;
+        }
+        entries += d.entry_count;
+        points += d.curve_points;
+    }
+    // the loaded nodes in the internal order: their indices move as a one-word node vector (bit copies), as
+    // set_dashpots moves its slots, and come back as a list
+    DevicePtr<uint32_t> order;
+    if (order.alloc(slot.size()) != hipSuccess)
+        return set_error(h, CWF_ERR_ALLOC, t->alloc_error);
+    std::vector<uint32_t> back(slot.size());
+    if (int st = vec_in(h, reinterpret_cast<const float *>(slot.data()), reinterpret_cast<float *>(order.get()),
+                        CWF_PTR_HOST, 1))
+        return st;
+    HIPTRY(h, hipMemcpyAsync(back.data(), order.get(), N * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIPTRY(h, hipStreamSynchronize(s));
+    std::vector<uint32_t> rank(nodes), node(nodes);  // caller-side index -> l; l -> internal node
+    uint32_t L = 0;
+    for (uint64_t n = 0; n < N; ++n)
+        if (back[n] != kNone)
+        {
+            rank[back[n]] = L;
+            node[L++] = (uint32_t)n;
+        }
+    if (L != nodes)
+        return set_error(h, CWF_ERR_INDEX, "load source nodes were lost in the node order");
+    // the CSR: counts, offsets, then the entries source by source, so that a node's entries ascend in source index
+    std::vector<uint32_t> off(nodes + 1, 0), dir(2 * entries);
+    std::vector<double> rec(4 * entries), tab(2 * points);
+    for (uint32_t q = 0; q < count; ++q)
+        for (uint64_t i = 0; i < sources[q].entry_count; ++i)
+            ++off[rank[slot[sources[q].node_ids[i]]] + 1];
+    for (uint64_t l = 0; l < nodes; ++l)
+        off[l + 1] += off[l];
+    std::vector<uint32_t> fill(off.begin(), off.end() - 1);
+    uint64_t at = 0;
+    for (uint32_t q = 0; q < count; ++q)
+    {
+        const cwf_explicit_source_desc &d = sources[q];
+        std::copy(d.times, d.times + d.curve_points, tab.begin() + at);
+        std::copy(d.values, d.values + d.curve_points, tab.begin() + at + d.curve_points);
+        for (uint64_t i = 0; i < d.entry_count; ++i)
+        {
+            const uint32_t e = fill[rank[slot[d.node_ids[i]]]]++;
+            rec[4ull * e] = d.amplitude[3 * i];
+            rec[4ull * e + 1] = d.amplitude[3 * i + 1];
+            rec[4ull * e + 2] = d.amplitude[3 * i + 2];
+            rec[4ull * e + 3] = d.delay[i];
+            dir[2ull * e] = (uint32_t)at;
+            dir[2ull * e + 1] = (uint32_t)d.curve_points;
+        }
+        at += 2 * d.curve_points;
+    }
+    // the new set's buffers; the stepper's once everything went well
+    cwf_hip_explicit::Sources m;
+    uint32_t *dnode = nullptr, *doff = nullptr, *ddir = nullptr;
+    double *drec = nullptr, *dtab = nullptr;
+    float *dfext = nullptr;
+    int st = t->alloc(&dnode, node.size());
+    st = st ? st : t->alloc(&doff, off.size());
+    st = st ? st : t->alloc(&drec, rec.size());
+    st = st ? st : t->alloc(&ddir, dir.size());
+    st = st ? st : t->alloc(&dtab, tab.size());
+    st = st ? st : t->alloc(&dfext, 3 * (size_t)nodes);
+    m.dev = ExplicitSources{(uint32_t)nodes, dnode, doff, drec, ddir, dtab, dfext};
+    hipError_t e = hipSuccess;
+    const auto up = [&](void *dst, const void *from, size_t bytes) {
+        if (!st && e == hipSuccess)
+            e = hipMemcpyAsync(dst, from, bytes, hipMemcpyHostToDevice, s);
+    };
+    up(dnode, node.data(), node.size() * sizeof(uint32_t));
+    up(doff, off.data(), off.size() * sizeof(uint32_t));
+    up(drec, rec.data(), rec.size() * sizeof(double));
+    up(ddir, dir.data(), dir.size() * sizeof(uint32_t));
+    up(dtab, tab.data(), tab.size() * sizeof(double));
+    if (!st && e == hipSuccess)
+        e = hipStreamSynchronize(s);
+    if (st || e != hipSuccess)
+    {
+        (void)hipStreamSynchronize(s);
+        m.release(t->mem);
+        return st ? st : hip_fail(h, e, "explicit set_sources");
+    }
+    // the force buffer holds f_n at the previous set's nodes: their f_ext goes back before the new set's is taken out
+    if (cur.dev.loaded)
+        explicit_sources_fext(cur.dev, t->f, false, s);
+    explicit_sources_fext(m.dev, t->f, true, s);
+    e = hipGetLastError();
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(s);
+    if (e != hipSuccess)
+    {
+        m.release(t->mem);
+        return hip_fail(h, e, "explicit set_sources");
+    }
+    m.entries = entries;
+    m.points = points;
+    m.bytes = (node.size() + off.size() + dir.size()) * sizeof(uint32_t) + (rec.size() + tab.size()) * sizeof(double) +
+              3 * nodes * sizeof(float);
+    m.given.resize(count);
+    for (uint32_t q = 0; q < count; ++q)
+    {
+        const cwf_explicit_source_desc &d = sources[q];
+        auto &g = m.given[q];
+        g.times.assign(d.times, d.times + d.curve_points);
+        g.values.assign(d.values, d.values + d.curve_points);
+        g.ids.assign(d.node_ids, d.node_ids + d.entry_count);
+        g.amplitude.assign(d.amplitude, d.amplitude + 3 * d.entry_count);
+        g.delay.assign(d.delay, d.delay + d.entry_count);
+    }
+    cur.release(t->mem);
+    cur = std::move(m);
+    return 0;
+}
+
+int cwf_hip_explicit_get_sources(cwf_hip_explicit *t, uint32_t *count, cwf_explicit_source_desc *sources)
+{
+    if (!t || !count)
+        return set_error(nullptr, CWF_ERR_ARGUMENT, "null pointer");
+    *count = (uint32_t)t->src.given.size();
+    for (size_t q = 0; sources && q < t->src.given.size(); ++q)
+    {
+        const auto &g = t->src.given[q];
+        sources[q] = cwf_explicit_source_desc{g.times.size(), g.times.data(), g.values.data(), g.ids.size(),
+                                              g.ids.data(), g.amplitude.data(), g.delay.data()};
+    }
+    return 0;
+}
+
+int cwf_hip_explicit_source_info(cwf_hip_explicit *t, cwf_explicit_source_info *info)
+{
+    if (!t || !info)
+        return set_error(nullptr, CWF_ERR_ARGUMENT, "null pointer");
+    cwf_explicit_source_info I{};
+    I.source_count = (uint32_t)t->src.given.size();
+    I.entry_count = t->src.entries;
+    I.loaded_nodes = t->src.dev.loaded;
+    I.curve_points = t->src.points;
+    I.device_bytes = t->src.bytes;
+    *info = I;
     return 0;
 }
 

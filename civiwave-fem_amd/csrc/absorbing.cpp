@@ -1,10 +1,12 @@
 // absorbing.cpp -- host side of the explicit stepper's absorbing (viscous, Lysmer-Kuhlemeyer) boundaries
 // (include/cwf_hip.h "Absorbing boundaries"): the dashpot matrices of a face list from the owning elements'
-// materials, and the per-node update matrices P, Q of the scheme. No GPU; fp64, compiled with -ffp-contract=off.
+// materials, the per-node update matrices P, Q of the scheme, and the entries of an obliquely incident plane wave.
+// No GPU; fp64, compiled with -ffp-contract=off.
 #include <algorithm>
 #include <array>
 #include <cmath>
 #include <cstdint>
+#include <cstdio>
 #include <map>
 #include <string>
 #include <unordered_map>
@@ -113,17 +115,20 @@ extern "C" int cwf_explicit_dashpot_update(const double C[9], double mass, doubl
     return 0;
 }
 
-extern "C" int cwf_absorbing_dashpots(uint64_t N, const double *coords, uint64_t E, uint32_t nodes_per_element,
-                                      const uint32_t *connectivity, const uint32_t *element_material,
-                                      uint64_t material_count, const double *rho, const double *lame_lambda,
-                                      const double *lame_mu, uint64_t F, uint32_t nodes_per_face,
-                                      const uint32_t *faces, uint64_t *count, uint32_t *node_ids, double *C)
+namespace
+{
+// what both face-list entry points need of a face: area, unit normal (the winding's), the element that owns it
+struct FaceFrames
+{
+    std::vector<double> area, normal;
+    std::vector<uint64_t> element;
+};
+
+// the faces' geometry and owners; 0 or the error (set)
+int face_frames(uint64_t N, const double *coords, uint64_t E, uint32_t nodes_per_element, const uint32_t *connectivity,
+                uint64_t F, uint32_t nodes_per_face, const uint32_t *faces, FaceFrames &out)
 {
     using cwf::set_error;
-    if (!count || (F && (!coords || !connectivity || !element_material || !rho || !lame_lambda || !lame_mu ||
-                         !faces || !node_ids || !C)))
-        return set_error(nullptr, CWF_ERR_ARGUMENT, "null pointer");
-    *count = 0;
     if (nodes_per_element != 4 && nodes_per_element != 8)
         return set_error(nullptr, CWF_ERR_ARGUMENT, "elements must be tet4 or hex8",
                          "nodes_per_element=" + std::to_string(nodes_per_element));
@@ -132,7 +137,9 @@ extern "C" int cwf_absorbing_dashpots(uint64_t N, const double *coords, uint64_t
                          "nodes_per_face=" + std::to_string(nodes_per_face));
     const uint32_t k = nodes_per_face;
     // area and unit normal per face; the faces' keys
-    std::vector<double> area(F), normal(3 * F);
+    std::vector<double> &area = out.area, &normal = out.normal;
+    area.assign(F, 0.0);
+    normal.assign(3 * F, 0.0);
     std::unordered_map<Key, Owner, KeyHash> owners;
     std::vector<uint8_t> on_face(N, 0);
     for (uint64_t f = 0; f < F; ++f)
@@ -191,24 +198,64 @@ extern "C" int cwf_absorbing_dashpots(uint64_t N, const double *coords, uint64_t
             }
         }
     }
+    out.element.assign(F, 0);
+    for (uint64_t f = 0; f < F; ++f)
+    {
+        const Owner &o = owners[key_of(faces + (uint64_t)k * f, k)];
+        if (o.count != 1)
+            return set_error(nullptr, CWF_ERR_ARGUMENT, "absorbing face is not a boundary face of the mesh",
+                             "face=" + std::to_string(f));
+        out.element[f] = o.element;
+    }
+    return 0;
+}
+
+// rho, V_p, V_s of face f's owning element; 0 or the error (set)
+int face_speeds(uint64_t f, uint64_t element, const uint32_t *element_material, uint64_t material_count,
+                const double *rho, const double *lame_lambda, const double *lame_mu, uint32_t *material, double *r,
+                double *vp, double *vs)
+{
+    using cwf::set_error;
+    const uint32_t mi = element_material[element];
+    if (mi >= material_count)
+        return set_error(nullptr, CWF_ERR_MATERIAL_RANGE, "element physical group missing assignment",
+                         "elements [" + std::to_string(element) + "]");
+    *material = mi;
+    *r = rho[mi];
+    *vp = std::sqrt((lame_lambda[mi] + 2.0 * lame_mu[mi]) / *r);
+    *vs = std::sqrt(lame_mu[mi] / *r);
+    if (!(*r > 0.0) || !std::isfinite(*vp) || !std::isfinite(*vs))
+        return set_error(nullptr, CWF_ERR_MATERIALS, "absorbing face's material has no wave speeds",
+                         "face=" + std::to_string(f) + "\nmaterial=" + std::to_string(mi));
+    return 0;
+}
+}  // namespace
+
+extern "C" int cwf_absorbing_dashpots(uint64_t N, const double *coords, uint64_t E, uint32_t nodes_per_element,
+                                      const uint32_t *connectivity, const uint32_t *element_material,
+                                      uint64_t material_count, const double *rho, const double *lame_lambda,
+                                      const double *lame_mu, uint64_t F, uint32_t nodes_per_face,
+                                      const uint32_t *faces, uint64_t *count, uint32_t *node_ids, double *C)
+{
+    using cwf::set_error;
+    if (!count || (F && (!coords || !connectivity || !element_material || !rho || !lame_lambda || !lame_mu ||
+                         !faces || !node_ids || !C)))
+        return set_error(nullptr, CWF_ERR_ARGUMENT, "null pointer");
+    *count = 0;
+    FaceFrames fr;
+    if (int st = face_frames(N, coords, E, nodes_per_element, connectivity, F, nodes_per_face, faces, fr))
+        return st;
+    const uint32_t k = nodes_per_face;
     std::map<uint32_t, std::array<double, 9>> acc;
     for (uint64_t f = 0; f < F; ++f)
     {
         const uint32_t *n = faces + (uint64_t)k * f;
-        const Owner &o = owners[key_of(n, k)];
-        if (o.count != 1)
-            return set_error(nullptr, CWF_ERR_ARGUMENT, "absorbing face is not a boundary face of the mesh",
-                             "face=" + std::to_string(f));
-        const uint32_t mi = element_material[o.element];
-        if (mi >= material_count)
-            return set_error(nullptr, CWF_ERR_MATERIAL_RANGE, "element physical group missing assignment",
-                             "elements [" + std::to_string(o.element) + "]");
-        const double r = rho[mi], vp = std::sqrt((lame_lambda[mi] + 2.0 * lame_mu[mi]) / r),
-                     vs = std::sqrt(lame_mu[mi] / r);
-        if (!(r > 0.0) || !std::isfinite(vp) || !std::isfinite(vs))
-            return set_error(nullptr, CWF_ERR_MATERIALS, "absorbing face's material has no wave speeds",
-                             "face=" + std::to_string(f) + "\nmaterial=" + std::to_string(mi));
-        const double share = area[f] / (double)k, *nu = normal.data() + 3 * f;
+        uint32_t mi;
+        double r, vp, vs;
+        if (int st = face_speeds(f, fr.element[f], element_material, material_count, rho, lame_lambda, lame_mu, &mi,
+                                 &r, &vp, &vs))
+            return st;
+        const double share = fr.area[f] / (double)k, *nu = fr.normal.data() + 3 * f;
         double Cf[9];
         for (int i = 0; i < 3; ++i)
             for (int j = 0; j < 3; ++j)
@@ -231,5 +278,112 @@ extern "C" int cwf_absorbing_dashpots(uint64_t N, const double *coords, uint64_t
         ++c;
     }
     *count = c;
+    return 0;
+}
+
+extern "C" int cwf_absorbing_incident_plane(uint64_t N, const double *coords, uint64_t E, uint32_t nodes_per_element,
+                                            const uint32_t *connectivity, const uint32_t *element_material,
+                                            uint64_t material_count, const double *rho, const double *lame_lambda,
+                                            const double *lame_mu, uint64_t F, uint32_t nodes_per_face,
+                                            const uint32_t *faces, const double polarisation[3],
+                                            const double propagation[3], const double origin[3], uint64_t *count,
+                                            uint32_t *node_ids, double *A, double *tau, double *wave_speed)
+{
+    using cwf::set_error;
+    if (!count || !polarisation || !propagation || !origin ||
+        (F && (!coords || !connectivity || !element_material || !rho || !lame_lambda || !lame_mu || !faces ||
+               !node_ids || !A || !tau)))
+        return set_error(nullptr, CWF_ERR_ARGUMENT, "null pointer");
+    *count = 0;
+    const double klen = norm3(propagation), dlen = norm3(polarisation);
+    if (!std::isfinite(klen) || !(klen > 0.0))
+        return set_error(nullptr, CWF_ERR_ARGUMENT, "propagation must be a non-zero finite vector");
+    if (!std::isfinite(dlen) || !(dlen > 0.0))
+        return set_error(nullptr, CWF_ERR_ARGUMENT, "polarisation must be a non-zero finite vector");
+    if (!std::isfinite(origin[0]) || !std::isfinite(origin[1]) || !std::isfinite(origin[2]))
+        return set_error(nullptr, CWF_ERR_ARGUMENT, "origin must be finite");
+    const double kh[3] = {propagation[0] / klen, propagation[1] / klen, propagation[2] / klen};
+    const double *d = polarisation;
+    const double dk = (d[0] * kh[0] + d[1] * kh[1]) + d[2] * kh[2];
+    const double cosine = std::fabs(dk) / dlen;
+    const bool pwave = cosine >= 1.0 - CWF_PLANE_WAVE_TOLERANCE;
+    if (!pwave && !(cosine <= CWF_PLANE_WAVE_TOLERANCE))
+    {
+        char b[40];
+        std::snprintf(b, sizeof b, "%.17g", cosine);
+        return set_error(nullptr, CWF_ERR_ARGUMENT,
+                         "polarisation is neither parallel nor perpendicular to the propagation",
+                         std::string("cosine=") + b);
+    }
+    FaceFrames fr;
+    if (int st = face_frames(N, coords, E, nodes_per_element, connectivity, F, nodes_per_face, faces, fr))
+        return st;
+    const uint32_t k = nodes_per_face;
+    std::map<uint32_t, std::array<double, 3>> acc;
+    uint32_t first_material = 0;
+    double c = 0.0;
+    for (uint64_t f = 0; f < F; ++f)
+    {
+        const uint32_t *n = faces + (uint64_t)k * f;
+        uint32_t mi;
+        double r, vp, vs;
+        if (int st = face_speeds(f, fr.element[f], element_material, material_count, rho, lame_lambda, lame_mu, &mi,
+                                 &r, &vp, &vs))
+            return st;
+        if (f == 0)
+            first_material = mi;
+        else if (mi != first_material)
+            return set_error(nullptr, CWF_ERR_UNSUPPORTED, "plane wave faces span more than one material",
+                             "face=" + std::to_string(f) + "\nmaterial=" + std::to_string(mi) +
+                                 "\nfirst_material=" + std::to_string(first_material));
+        c = pwave ? vp : vs;
+        if (!(c > 0.0))
+            return set_error(nullptr, CWF_ERR_MATERIALS, "absorbing face's material has no wave speeds",
+                             "face=" + std::to_string(f) + "\nmaterial=" + std::to_string(mi));
+        // the outward normal: away from the owning element's centroid
+        const uint32_t *en = connectivity + (uint64_t)nodes_per_element * fr.element[f];
+        double away[3];
+        for (int q = 0; q < 3; ++q)
+        {
+            double fc = 0.0, ec = 0.0;
+            for (uint32_t a = 0; a < k; ++a)
+                fc += coords[3ull * n[a] + q];
+            for (uint32_t a = 0; a < nodes_per_element; ++a)
+                ec += coords[3ull * en[a] + q];
+            away[q] = fc / (double)k - ec / (double)nodes_per_element;
+        }
+        const double *nw = fr.normal.data() + 3 * f;
+        const double sign = ((away[0] * nw[0] + away[1] * nw[1]) + away[2] * nw[2]) < 0.0 ? -1.0 : 1.0;
+        const double nu[3] = {sign * nw[0], sign * nw[1], sign * nw[2]};
+        const double lam = lame_lambda[mi], mu = lame_mu[mi];
+        const double dn = (d[0] * nu[0] + d[1] * nu[1]) + d[2] * nu[2];
+        const double kn = (kh[0] * nu[0] + kh[1] * nu[1]) + kh[2] * nu[2];
+        const double share = fr.area[f] / (double)k;
+        double Af[3];
+        for (int q = 0; q < 3; ++q)
+        {
+            const double dash = r * (vp * (dn * nu[q]) + vs * (d[q] - dn * nu[q]));
+            const double trac = -((lam * dk) * nu[q] + mu * (d[q] * kn + kh[q] * dn)) / c;
+            Af[q] = share * (dash + trac);
+        }
+        for (uint32_t a = 0; a < k; ++a)
+        {
+            auto &dst = acc.try_emplace(n[a], std::array<double, 3>{}).first->second;
+            for (int q = 0; q < 3; ++q)
+                dst[q] += Af[q];
+        }
+    }
+    uint64_t cnt = 0;
+    for (const auto &kv : acc)
+    {
+        const double *x = coords + 3ull * kv.first;
+        node_ids[cnt] = kv.first;
+        std::copy(kv.second.begin(), kv.second.end(), A + 3 * cnt);
+        tau[cnt] = ((kh[0] * (x[0] - origin[0]) + kh[1] * (x[1] - origin[1])) + kh[2] * (x[2] - origin[2])) / c;
+        ++cnt;
+    }
+    *count = cnt;
+    if (wave_speed)
+        *wave_speed = c;
     return 0;
 }

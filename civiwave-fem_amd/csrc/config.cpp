@@ -463,7 +463,30 @@ std::string parse_config(const yl::Node &root)
                 throw CfgError{"absorbing incident wave references unknown curve",
                                {"absorbing", idx(i), "incident", "velocity_curve"}};
             j << "{\"direction\": [" << jnum(d.v[0]) << ", " << jnum(d.v[1]) << ", " << jnum(d.v[2])
-              << "], \"velocity_curve\": " << jstr(curve) << "}}";
+              << "], \"velocity_curve\": " << jstr(curve);
+            // an oblique plane wave (optional; each key is emitted only when the document has it)
+            const yl::Node &pn = inc["propagation"];
+            if (pn.defined())
+            {
+                if (!pn.is_seq() || pn.size() != 3)
+                    throw CfgError{"absorbing.incident.propagation must be a non-zero sequence[3]",
+                                   {"absorbing", idx(i), "incident", "propagation"}};
+                const Vec3 k = vec3(pn, {"absorbing", idx(i), "incident", "propagation"});
+                if (k.v[0] == 0.0 && k.v[1] == 0.0 && k.v[2] == 0.0)
+                    throw CfgError{"absorbing.incident.propagation must be a non-zero sequence[3]",
+                                   {"absorbing", idx(i), "incident", "propagation"}};
+                j << ", \"propagation\": [" << jnum(k.v[0]) << ", " << jnum(k.v[1]) << ", " << jnum(k.v[2]) << "]";
+            }
+            const yl::Node &on = inc["origin"];
+            if (on.defined())
+            {
+                if (!on.is_seq() || on.size() != 3)
+                    throw CfgError{"absorbing.incident.origin must be a sequence[3]",
+                                   {"absorbing", idx(i), "incident", "origin"}};
+                const Vec3 o = vec3(on, {"absorbing", idx(i), "incident", "origin"});
+                j << ", \"origin\": [" << jnum(o.v[0]) << ", " << jnum(o.v[1]) << ", " << jnum(o.v[2]) << "]";
+            }
+            j << "}}";
         }
         j << "]";
     }

@@ -781,6 +781,22 @@ void explicit_energy_fold(uint32_t blocks, const double *ecum, const double *ecu
 void explicit_record(uint32_t count, const uint32_t *node, const float *u, const float *v, float *row_u, float *row_v,
                      hipStream_t st);
 void explicit_operator_input(uint32_t N, const float *u, const float *v, double beta, float *w, hipStream_t st);
+// load sources (cwf_hip_explicit_set_sources): a CSR over the loaded nodes in the internal node order, each node's
+// entries in ascending source order; all arrays in the stepper's arena
+struct ExplicitSources
+{
+    uint32_t loaded;       // loaded nodes L (0: no set)
+    const uint32_t *node;  // [L] the internal node, ascending
+    const uint32_t *off;   // [L + 1] the node's entries
+    const double *rec;     // [entries] 32-B records: A_0 A_1 A_2 tau
+    const uint32_t *cur;   // [entries] 8 B: where the entry's curve starts in tab, and its points
+    const double *tab;     // per source its times, then its values
+    float *fext;           // [3 L] f_ext of the loaded nodes
+};
+// f_n of the loaded nodes at t_n = tnow into the force buffer f (one thread per loaded node)
+void explicit_sources(const ExplicitSources &a, double tnow, float *f, hipStream_t st);
+// gather: fext <- f at the loaded nodes; else f <- fext
+void explicit_sources_fext(const ExplicitSources &a, float *f, bool gather, hipStream_t st);
 // power iteration (cwf_hip_lambda_max): the start vector; z = M^-1 y over the free DOFs; x = z / (num / den),
 // the quotient stored in lam[0]
 void explicit_power_start(uint32_t N, const uint32_t *mask, float *x, hipStream_t st);

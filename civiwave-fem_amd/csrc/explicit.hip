@@ -296,6 +296,87 @@ __global__ __launch_bounds__(kBlock) void k_explicit_record(uint32_t count, cons
     store3(row_v, r, load3(v, n));
 }
 
+// Load sources (include/cwf_hip.h "Load sources"): std::lerp as libstdc++ has it, abi_explicit.cpp's lerp_ref
+__device__ __forceinline__ double lerp_dev(double a, double b, double t)
+{
+    if ((a <= 0 && b >= 0) || (a >= 0 && b <= 0))
+        return t * b + (1 - t) * a;
+    if (t == 1)
+        return b;
+    const double x = a + t * (b - a);
+    return ((t > 1) == (b > a)) ? (b < x ? x : b) : (b > x ? x : b);
+}
+
+// cwf_explicit_curve_value on n >= 1 points: the first knot i >= 1 with t <= times[i] by bisection (times ascend, so
+// the test is monotone and the i is the linear scan's, duplicate knots included), then the same operations
+__device__ __forceinline__ double curve_dev(const double *__restrict__ times, const double *__restrict__ values,
+                                            uint32_t n, double t)
+{
+    if (t <= times[0])
+        return values[0];
+    uint32_t lo = 1, hi = n;
+    while (lo < hi)
+    {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (t <= times[mid])
+            hi = mid;
+        else
+            lo = mid + 1;
+    }
+    if (lo >= n)
+        return values[n - 1];
+    const double t0 = times[lo - 1], span = times[lo] - t0;
+    const double w = span > 0.0 ? (t - t0) / span : 0.0;
+    return lerp_dev(values[lo - 1], values[lo], w);
+}
+
+// f_n of the loaded nodes, one thread per loaded node: f_ext from the compact side array, then the node's entries in
+// ascending source order, acc = acc + A c in fp64 without FMA, safe_cast, one 12-B store into the force buffer the
+// update pass reads. Per entry a 32-B record (two 16-B loads), 8 B of curve directory and the bisection's knots
+// (log2(points) + 3 f64 loads out of a table every thread shares: L2 hits); per node 4 + 8 B of CSR and 12 B of f_ext.
+// The tables stay in global memory: a 4096-point curve is 64 KiB, all of a workgroup's LDS, of which a thread reads
+// 15 values; staging it would cost each workgroup the whole table every step.
+__global__ __launch_bounds__(kBlock) void k_explicit_sources(ExplicitSources a, double tnow, float *__restrict__ f)
+{
+    const uint32_t l = blockIdx.x * kBlock + threadIdx.x;
+    if (l >= a.loaded)
+        return;
+    const F3 fe = load3(a.fext, l);
+    double acc0 = (double)fe.c[0], acc1 = (double)fe.c[1], acc2 = (double)fe.c[2];
+    const uint32_t end = a.off[l + 1];
+    for (uint32_t e = a.off[l]; e < end; ++e)
+    {
+        const double2 *rec = reinterpret_cast<const double2 *>(a.rec + 4ull * e);  // 32-B records, hipMalloc'd
+        const double2 r0 = rec[0], r1 = rec[1];
+        const uint2 cu = reinterpret_cast<const uint2 *>(a.cur)[e];
+        const double *times = a.tab + cu.x;
+        const double c = curve_dev(times, times + cu.y, cu.y, tnow - r1.y);
+        acc0 = acc0 + r0.x * c;
+        acc1 = acc1 + r0.y * c;
+        acc2 = acc2 + r1.x * c;
+    }
+    F3 o;
+    o.c[0] = safe_cast(acc0);
+    o.c[1] = safe_cast(acc1);
+    o.c[2] = safe_cast(acc2);
+    store3(f, a.node[l], o);
+}
+
+// the loaded nodes' f_ext: out of the force buffer into the side array (set_sources, set_external_force), and back
+// (a set replaced or removed)
+template <bool GATHER>
+__global__ __launch_bounds__(kBlock) void k_explicit_sources_fext(uint32_t loaded, const uint32_t *__restrict__ node,
+                                                                  float *f, float *fext)
+{
+    const uint32_t l = blockIdx.x * kBlock + threadIdx.x;
+    if (l >= loaded)
+        return;
+    if (GATHER)
+        store3(fext, l, load3(f, node[l]));
+    else
+        store3(f, node[l], load3(fext, l));
+}
+
 // w = f32(u + beta_R v): the operator's input of the first step after create or set_state (later steps' passes
 // store it themselves)
 __global__ __launch_bounds__(kBlock) void k_explicit_input(uint32_t N, const float *__restrict__ u,
@@ -427,6 +508,22 @@ void explicit_record(uint32_t count, const uint32_t *node, const float *u, const
 {
     if (count)
         k_explicit_record<<<grid_for(count, kBlock), kBlock, 0, st>>>(count, node, u, v, row_u, row_v);
+}
+
+void explicit_sources(const ExplicitSources &a, double tnow, float *f, hipStream_t st)
+{
+    if (a.loaded)
+        k_explicit_sources<<<grid_for(a.loaded, kBlock), kBlock, 0, st>>>(a, tnow, f);
+}
+
+void explicit_sources_fext(const ExplicitSources &a, float *f, bool gather, hipStream_t st)
+{
+    if (!a.loaded)
+        return;
+    if (gather)
+        k_explicit_sources_fext<true><<<grid_for(a.loaded, kBlock), kBlock, 0, st>>>(a.loaded, a.node, f, a.fext);
+    else
+        k_explicit_sources_fext<false><<<grid_for(a.loaded, kBlock), kBlock, 0, st>>>(a.loaded, a.node, f, a.fext);
 }
 
 void explicit_operator_input(uint32_t N, const float *u, const float *v, double beta, float *w, hipStream_t st)

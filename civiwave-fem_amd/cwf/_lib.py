@@ -119,6 +119,17 @@ class ExplicitMonitorInfoC(C.Structure):
                 ("peaks", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class ExplicitSourceDescC(C.Structure):
+    _fields_ = [("curve_points", C.c_uint64), ("times", C.c_void_p), ("values", C.c_void_p),
+                ("entry_count", C.c_uint64), ("node_ids", C.c_void_p), ("amplitude", C.c_void_p),
+                ("delay", C.c_void_p)]
+
+
+class ExplicitSourceInfoC(C.Structure):
+    _fields_ = [("source_count", C.c_uint32), ("reserved", C.c_uint32), ("entry_count", C.c_uint64),
+                ("loaded_nodes", C.c_uint64), ("curve_points", C.c_uint64), ("device_bytes", C.c_uint64)]
+
+
 class ShardInfoC(C.Structure):
     _fields_ = [
         ("owned_nodes", C.c_uint64), ("local_nodes", C.c_uint64), ("local_elements", C.c_uint64),
@@ -230,8 +241,13 @@ def load() -> C.CDLL:
         "cwf_hip_explicit_read_receivers": ([P, u64, u64, P, P, P], i32),
         "cwf_hip_explicit_read_peaks": ([P, P, P, P, u64, i32], i32),
         "cwf_hip_explicit_read_energy": ([P, u64, u64, P, P], i32),
+        "cwf_hip_explicit_set_sources": ([P, P, C.c_uint32], i32),
+        "cwf_hip_explicit_get_sources": ([P, P, P], i32),
+        "cwf_hip_explicit_source_info": ([P, P], i32),
         "cwf_explicit_dashpot_update": ([P, f64, f64, f64, P, P], i32),
         "cwf_absorbing_dashpots": ([u64, P, u64, C.c_uint32, P, P, u64, P, P, P, u64, C.c_uint32, P, P, P, P], i32),
+        "cwf_absorbing_incident_plane": ([u64, P, u64, C.c_uint32, P, P, u64, P, P, P, u64, C.c_uint32, P, P, P, P, P, P,
+                                          P, P, P], i32),
         "cwf_hip_lambda_max": ([P, C.c_uint32, P, P], i32),
         "cwf_explicit_critical_dt": ([f64, f64], f64),
         "cwf_explicit_curve_value": ([P, P, u64, f64], f64),

@@ -49,9 +49,9 @@ def element_materials(mesh, cfg) -> np.ndarray:
     return mat
 
 
-def dashpots(mesh, cfg, faces):
-    """-> (node_ids u32 [n] ascending, C f64 [n,3,3]): the viscous-boundary matrices of `faces`, each face with the
-    material of the element that owns it."""
+def _face_call_args(mesh, cfg, faces):
+    """The mesh, material and face arguments cwf_absorbing_dashpots and cwf_absorbing_incident_plane share, and the
+    arrays that keep them alive."""
     faces = np.ascontiguousarray(faces, np.uint32)
     if faces.ndim != 2 or faces.shape[1] not in (3, 4):
         raise ValueError("faces must be u32 [F,3] or [F,4]")
@@ -62,19 +62,50 @@ def dashpots(mesh, cfg, faces):
     rho = np.ascontiguousarray([m.density for m in cfg.materials], np.float64)
     lam = np.ascontiguousarray([l.lambda_ for l in lame], np.float64)
     mu = np.ascontiguousarray([l.mu for l in lame], np.float64)
-    room = max(1, min(mesh.node_count, faces.size))
+    p = _lib.ptr
+    args = (mesh.node_count, p(coords), conn.shape[0], conn.shape[1], p(conn), p(mat), len(cfg.materials), p(rho),
+            p(lam), p(mu), faces.shape[0], faces.shape[1], p(faces))
+    return args, max(1, min(mesh.node_count, faces.size)), (faces, coords, conn, mat, rho, lam, mu)
+
+
+def dashpots(mesh, cfg, faces):
+    """-> (node_ids u32 [n] ascending, C f64 [n,3,3]): the viscous-boundary matrices of `faces`, each face with the
+    material of the element that owns it."""
+    args, room, _keep = _face_call_args(mesh, cfg, faces)
     ids = np.zeros(room, np.uint32)
     Cn = np.zeros(9 * room, np.float64)
     count = C.c_uint64()
     p = _lib.ptr
-    rc = _lib.load().cwf_absorbing_dashpots(mesh.node_count, p(coords), conn.shape[0], conn.shape[1], p(conn), p(mat),
-                                            len(cfg.materials), p(rho), p(lam), p(mu), faces.shape[0],
-                                            faces.shape[1], p(faces), C.byref(count), p(ids), p(Cn))
+    rc = _lib.load().cwf_absorbing_dashpots(*args, C.byref(count), p(ids), p(Cn))
     if rc:
         msg, ctx = _lib.last_error(None)
         raise RuntimeError(f"{msg} {ctx}")
     n = count.value
     return ids[:n].copy(), Cn[:9 * n].reshape(n, 3, 3).copy()
+
+
+def incident_plane_wave(mesh, cfg, faces, polarisation, propagation, origin=(0.0, 0.0, 0.0)):
+    """-> (node_ids u32 [n] ascending, A f64 [n,3], tau f64 [n], wave speed): the entries of the load source that
+    feeds the plane wave of particle velocity d g(t - tau), tau = khat . (x - origin) / c, in through the dashpots of
+    `faces` (cwf_absorbing_incident_plane): the dashpot's share C_n d plus the free-field traction. d = polarisation as
+    given; khat = propagation normalised; c = V_p for d parallel to khat, V_s for d perpendicular, anything else is
+    refused, and so are faces over more than one material."""
+    args, room, _keep = _face_call_args(mesh, cfg, faces)
+    d = np.ascontiguousarray(polarisation, np.float64).reshape(3)
+    k = np.ascontiguousarray(propagation, np.float64).reshape(3)
+    x0 = np.ascontiguousarray(origin, np.float64).reshape(3)
+    ids = np.zeros(room, np.uint32)
+    A = np.zeros(3 * room, np.float64)
+    tau = np.zeros(room, np.float64)
+    count, speed = C.c_uint64(), C.c_double()
+    p = _lib.ptr
+    rc = _lib.load().cwf_absorbing_incident_plane(*args, p(d), p(k), p(x0), C.byref(count), p(ids), p(A), p(tau),
+                                                  C.byref(speed))
+    if rc:
+        msg, ctx = _lib.last_error(None)
+        raise RuntimeError(f"{msg} {ctx}")
+    n = count.value
+    return ids[:n].copy(), A[:3 * n].reshape(n, 3).copy(), tau[:n].copy(), speed.value
 
 
 def merge(parts):

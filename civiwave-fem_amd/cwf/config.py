@@ -49,7 +49,9 @@ def _from_json(d: dict) -> Config:
                                 tuple(None if v is None else f(v) for v in x["value"])) for x in d["dirichlet"]],
         output=OutputSettings(d["output"]["vtu_stride"], list(d["output"]["probes"])),
         absorbing=[AbsorbingBoundary(a["group"], None if a["incident"] is None else
-                                     IncidentWave(_f3(a["incident"]["direction"]), a["incident"]["velocity_curve"]))
+                                     IncidentWave(_f3(a["incident"]["direction"]), a["incident"]["velocity_curve"],
+                                                  *(_f3(a["incident"][k]) if k in a["incident"] else None
+                                                    for k in ("propagation", "origin"))))
                    for a in d.get("absorbing", [])],
     )
 

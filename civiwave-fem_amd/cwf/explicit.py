@@ -87,6 +87,31 @@ class EnergyLedger:
         return self.total() - self.work + self.dissipated
 
 
+MAX_SOURCES = 8  # CWF_EXPLICIT_MAX_SOURCES
+
+
+@dataclass
+class LoadSource:
+    """One load source (include/cwf_hip.h "Load sources"): the force A_e c(t - tau_e) on node_ids[e], c the
+    piecewise-linear curve; node ids distinct, the caller's numbering."""
+    curve: object          # a Curve or a sequence of (time, value)
+    node_ids: np.ndarray   # u32 [n]
+    amplitude: np.ndarray  # f64 [n,3]
+    delay: np.ndarray      # f64 [n], seconds
+
+    def points(self):
+        return list(self.curve.points) if isinstance(self.curve, Curve) else [tuple(p) for p in self.curve]
+
+
+@dataclass
+class SourceInfo:
+    source_count: int
+    entry_count: int
+    loaded_nodes: int
+    curve_points: int
+    device_bytes: int
+
+
 def lambda_max(system: MatrixFreeSystem, iterations: int = 60):
     """-> (estimate of the largest eigenvalue of M^-1 K over the free DOFs, the last iteration's relative change)."""
     lam, change = C.c_double(), C.c_double()
@@ -188,6 +213,56 @@ class ExplicitStepper(TransientState):
 
     def clear_dashpots(self):
         self._check(_lib.load().cwf_hip_explicit_set_dashpots(self._ex, 0, None, None))
+
+    # ---- load sources (include/cwf_hip.h "Load sources") ----
+    def set_sources(self, sources):
+        """sources: LoadSource objects or (curve, node_ids, amplitude [n,3], delay [n]) tuples, at most MAX_SOURCES;
+        an empty list removes the set. Replaces the previous set, which stays in force if this one is refused
+        (RuntimeError). Sources and a load pattern exclude each other."""
+        srcs = [s if isinstance(s, LoadSource) else LoadSource(*s) for s in (sources or [])]
+        descs = (_lib.ExplicitSourceDescC * max(len(srcs), 1))()
+        keep = []
+        for d, s in zip(descs, srcs):
+            pts = s.points()
+            times = np.ascontiguousarray([p[0] for p in pts], np.float64)
+            values = np.ascontiguousarray([p[1] for p in pts], np.float64)
+            ids = np.ascontiguousarray(s.node_ids, np.uint32).reshape(-1)
+            amp = np.ascontiguousarray(s.amplitude, np.float64).reshape(-1)
+            tau = np.ascontiguousarray(s.delay, np.float64).reshape(-1)
+            if amp.size != 3 * ids.size or tau.size != ids.size:
+                raise ValueError("a source needs 3 amplitudes and 1 delay per node")
+            keep.append((times, values, ids, amp, tau))
+            d.curve_points, d.times, d.values = len(pts), times.ctypes.data, values.ctypes.data
+            d.entry_count, d.node_ids, d.amplitude, d.delay = ids.size, ids.ctypes.data, amp.ctypes.data, tau.ctypes.data
+        self._check(_lib.load().cwf_hip_explicit_set_sources(self._ex, descs if srcs else None, len(srcs)))
+
+    def clear_sources(self):
+        self._check(_lib.load().cwf_hip_explicit_set_sources(self._ex, None, 0))
+
+    def get_sources(self):
+        """-> [LoadSource] as they were set (curve: a list of (time, value))."""
+        n = C.c_uint32()
+        descs = (_lib.ExplicitSourceDescC * MAX_SOURCES)()
+        self._check(_lib.load().cwf_hip_explicit_get_sources(self._ex, C.byref(n), descs))
+
+        def arr(p, ctype, count, dtype):
+            return np.ctypeslib.as_array(C.cast(p, C.POINTER(ctype)), shape=(count,)).astype(dtype) if count else \
+                np.zeros(0, dtype)
+
+        out = []
+        for d in descs[:n.value]:
+            m, k = int(d.entry_count), int(d.curve_points)
+            t, v = arr(d.times, C.c_double, k, np.float64), arr(d.values, C.c_double, k, np.float64)
+            out.append(LoadSource([(float(a), float(b)) for a, b in zip(t, v)], arr(d.node_ids, C.c_uint32, m, np.uint32),
+                                  arr(d.amplitude, C.c_double, 3 * m, np.float64).reshape(m, 3),
+                                  arr(d.delay, C.c_double, m, np.float64)))
+        return out
+
+    def source_info(self) -> SourceInfo:
+        i = _lib.ExplicitSourceInfoC()
+        self._check(_lib.load().cwf_hip_explicit_source_info(self._ex, C.byref(i)))
+        return SourceInfo(int(i.source_count), int(i.entry_count), int(i.loaded_nodes), int(i.curve_points),
+                          int(i.device_bytes))
 
     # ---- monitors (include/cwf_hip.h "Monitors") ----
     def set_monitors(self, receivers=None, receiver_every: int = 1, receiver_capacity: int = 0, peaks: bool = False,

@@ -96,6 +96,8 @@ class OutputSettings:
 class IncidentWave:
     direction: tuple  # the incident particle velocity is direction * curve(t), in m/s
     velocity_curve: str
+    propagation: Optional[tuple] = None  # an oblique plane wave travels along it (None: normal to the boundary)
+    origin: Optional[tuple] = None       # where the curve's t = 0 front passes (None with propagation: the zero vector)
 
 
 @dataclass

@@ -17,7 +17,9 @@ every step's start time instead (the viewer's custom-load path, viewer.cpp:262-2
 step instead: ``--steps`` still counts output frames, one every ceil(dt_scenario / dt_explicit) explicit steps (the
 scenario's ``time.dt`` is the output interval), through the same VTU and probe writers; loads are those of t = 0.
 A scenario's ``absorbing:`` entries (explicit only) put viscous dashpots on their groups' faces; an entry's
-``incident: {direction, velocity_curve}`` feeds that curve in through the dashpots as an incident wave.
+``incident: {direction, velocity_curve}`` feeds that curve in through the dashpots as an incident wave. With
+``propagation: [x, y, z]`` (and ``origin``) the wave is a plane wave travelling obliquely along it, each boundary node
+with its own arrival delay; such entries, and entries naming different curves, run as the stepper's load sources.
 ``--trace-every K``, ``--peaks`` and ``--energy-every K`` (explicit only) turn on the stepper's monitors: receiver
 traces at ``output.probes`` every K explicit steps (``probes/traces.csv``), the peak |u|, |v|, |a| maps
 (``monitors/peaks.npy``, [N,3]) and the energy ledger (``monitors/energy.csv``), written after the last frame. The
@@ -133,6 +135,8 @@ def run_scenario_explicit(cfg_path: str, steps: int, out_dir: str | None, mode: 
     wall0, last = time.perf_counter(), None
     try:
         absorbing_nodes = set_absorbing(st, cfg, m, P)
+        info = st.source_info()
+        sources = dict(sources=info.source_count, source_nodes=info.loaded_nodes) if info.source_count else {}
         tel = st.telemetry()
         per_frame = max(1, math.ceil(cfg.time.initial_dt / tel.dt))
         monitored = trace_every > 0 or peaks or energy_every > 0
@@ -165,7 +169,7 @@ def run_scenario_explicit(cfg_path: str, steps: int, out_dir: str | None, mode: 
                     integrator="explicit", explicit_steps=tel.steps, steps_per_frame=per_frame, dt=tel.dt,
                     critical_dt=tel.critical_dt, lambda_max=tel.lambda_max, wall_s=wall, final_time=tel.time,
                     last=last, mode="fast" if mode == _lib.MODE_FAST else "parity", absorbing_nodes=absorbing_nodes,
-                    **written)
+                    **sources, **written)
     finally:
         if om is not None:
             om.close()
@@ -205,46 +209,73 @@ def write_monitors(st, out_dir, probes, traces: bool, peaks: bool, energy: bool)
     return out
 
 
+class AbsorbingSetup(tuple):
+    """(node_ids, C summed per node, load base, load pattern, curve), as absorbing_setup always returned it; ``sources``
+    holds the load sources of a scenario that needs them (then base, pattern and curve are None)."""
+    sources = ()
+
+
 def absorbing_setup(cfg, m, P):
-    """The scenario's ``absorbing:`` entries -> (node_ids, C summed per node, load base, load pattern, curve); the last
-    three are None without an incident wave. base is the static load vector, pattern the entries' incident patterns
-    summed, curve the one curve they name."""
+    """The scenario's ``absorbing:`` entries -> AbsorbingSetup (node_ids, C summed per node, load base, load pattern,
+    curve); the last three are None without an incident wave. Entries of the plain form (no ``propagation``) that
+    name one curve between them: base is the static load vector, pattern the entries' incident patterns summed, curve
+    the one they name. An entry with ``propagation``, or more than one curve: every incident entry becomes a load
+    source instead (.sources; a plain entry's is 2 C_n d with zero delays)."""
     import numpy as np
 
     from . import absorbing
+    from .explicit import MAX_SOURCES, LoadSource
 
-    parts, pattern, names = [], np.zeros(P.dof_count, np.float64), []
+    parts, pattern, names, sources = [], np.zeros(P.dof_count, np.float64), [], []
     for i, entry in enumerate(cfg.absorbing):
         try:
-            ids, Cn = absorbing.dashpots(m, cfg, absorbing.faces_of_group(m, entry.group))
+            faces = absorbing.faces_of_group(m, entry.group)
+            ids, Cn = absorbing.dashpots(m, cfg, faces)
+            if not ids.size:
+                raise ScenarioError(f"absorbing [{i}]: group '{entry.group}' has no boundary faces")
+            inc = entry.incident
+            if inc is not None and inc.propagation is not None:
+                sid, A, tau, _ = absorbing.incident_plane_wave(m, cfg, faces, inc.direction, inc.propagation,
+                                                               inc.origin or (0.0, 0.0, 0.0))
+                sources.append(LoadSource(cfg.curves[inc.velocity_curve], sid, A, tau))
+            elif inc is not None:
+                sources.append(LoadSource(cfg.curves[inc.velocity_curve], ids,
+                                          2.0 * (Cn @ np.asarray(inc.direction, np.float64)), np.zeros(ids.size)))
         except (KeyError, ValueError, RuntimeError) as e:
+            if isinstance(e, ScenarioError):
+                raise
             raise ScenarioError(f"absorbing [{i}]: {e.args[0] if e.args else e}") from None
-        if not ids.size:
-            raise ScenarioError(f"absorbing [{i}]: group '{entry.group}' has no boundary faces")
         parts.append((ids, Cn))
         if entry.incident is not None:
             pattern += absorbing.incident_pattern(ids, Cn, entry.incident.direction, P.node_count)
             if entry.incident.velocity_curve not in names:
                 names.append(entry.incident.velocity_curve)
-    if len(names) > 1:
-        raise ScenarioError("explicit stepper takes one load curve")
     ids, Cn = absorbing.merge(parts)
     if not names:
-        return ids, Cn, None, None, None
+        return AbsorbingSetup((ids, Cn, None, None, None))
+    if len(names) > 1 or any(e.incident is not None and e.incident.propagation is not None for e in cfg.absorbing):
+        if len(sources) > MAX_SOURCES:
+            raise ScenarioError(f"explicit stepper takes at most {MAX_SOURCES} load sources")
+        out = AbsorbingSetup((ids, Cn, None, None, None))
+        out.sources = sources
+        return out
     base = pack.assemble_load_vector(m, cfg, P.lumped_mass64)
-    return ids, Cn, base, pattern, cfg.curves[names[0]]
+    return AbsorbingSetup((ids, Cn, base, pattern, cfg.curves[names[0]]))
 
 
 def set_absorbing(st, cfg, m, P) -> int:
-    """Put the scenario's absorbing boundaries and incident wave on an ExplicitStepper -> dashpot nodes."""
+    """Put the scenario's absorbing boundaries and incident waves on an ExplicitStepper -> dashpot nodes."""
     if not cfg.absorbing:
         return 0
-    ids, Cn, base, pattern, curve = absorbing_setup(cfg, m, P)
+    setup = absorbing_setup(cfg, m, P)
+    ids, Cn, base, pattern, curve = setup
     if curve is not None:
         st.set_load_pattern(base, pattern)
         st.set_load_curve(curve)
     try:
         st.set_dashpots(ids, Cn)
+        if setup.sources:
+            st.set_sources(setup.sources)
     except RuntimeError as e:
         raise ScenarioError(str(e)) from None
     return int(ids.size)

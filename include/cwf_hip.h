@@ -475,6 +475,26 @@ int cwf_hip_stepper_time(const cwf_hip_stepper *st, double *current_time, double
  *     kernel then folds the shares: thread t adds workgroups t, t + 256, ... in that order from 0, the 256 sums fold
  *     pairwise (s[t] += s[t + stride], stride 128 ... 1) into the row {kinetic, potential, work_cum, dissipated_cum}.
  *     The cumulative columns include the unsampled steps; a full buffer drops rows, not sums.
+ *
+ * Load sources (cwf_hip_explicit_set_sources): loads whose time function differs from node to node -- an obliquely
+ * incident plane wave, a three-component ground motion, a travelling front. A source is a piecewise-linear curve and a
+ * list of entries (node, amplitude A[3], delay tau in seconds, any sign); a set holds up to CWF_EXPLICIT_MAX_SOURCES
+ * sources. At step n a node with entries (a loaded node) gets, per component k, in fp64 without fused multiply-adds,
+ *     acc   = (double)f_ext_k                                f_ext: the external force as last set (create /
+ *                                                            set_external_force)
+ *     for each of the node's entries e, ascending source index s:
+ *         c   = cwf_explicit_curve_value(curve_s, (double)n dt - tau_e)
+ *         acc = acc + A_ek c
+ *     f_n,k = safe_cast(acc)                                 cwf_hip_stepper_set_load_scale's rounding
+ * and a node without entries reads f_ext as before. A kernel with one thread per loaded node runs before the update
+ * pass of every step and stores these f_n into the stepper's force buffer, which the update pass reads as it reads the
+ * external force: constrained DOFs are masked as always, and dashpots, peak maps and the ledger's work term see f_n.
+ * n dt is formed on the host and passed to the launch; the kernel finds the curve's segment by bisection, the same
+ * knot the linear scan of cwf_explicit_curve_value stops at (duplicate knots included), and evaluates it in the same
+ * operations. cwf_hip_explicit_get_state(4) returns f_n of the last step; the loaded nodes' f_ext is kept in a side
+ * array of 12 bytes per loaded node, which set_external_force refreshes and a removed set writes back. Sources and a
+ * load pattern exclude each other. A stepper without sources launches exactly the kernels it launches without this
+ * section and allocates nothing for it.
  * ------------------------------------------------------------------------------------- */
 typedef struct cwf_explicit_desc
 {
@@ -576,6 +596,46 @@ int cwf_hip_explicit_read_peaks(cwf_hip_explicit *ex, float *peak_u, float *peak
                                 int ptr_kind);
 /* Ledger rows into host memory: steps [count], rows [count][4] = {kinetic, potential, work_cum, dissipated_cum}. */
 int cwf_hip_explicit_read_energy(cwf_hip_explicit *ex, uint64_t first, uint64_t count, uint64_t *steps, double *rows);
+/* Load sources of the scheme above. */
+#define CWF_EXPLICIT_MAX_SOURCES 8
+typedef struct cwf_explicit_source_desc
+{
+    uint64_t curve_points;   /* 1 .. CWF_EXPLICIT_MAX_CURVE_POINTS */
+    const double *times;     /* [curve_points] ascending (equal neighbours: a step) */
+    const double *values;    /* [curve_points] */
+    uint64_t entry_count;    /* >= 1 */
+    const uint32_t *node_ids; /* [entry_count] distinct within the source, the caller's numbering */
+    const double *amplitude; /* [3 entry_count] A, in N per unit of the curve */
+    const double *delay;     /* [entry_count] tau in seconds */
+} cwf_explicit_source_desc;
+
+typedef struct cwf_explicit_source_info
+{
+    uint32_t source_count, reserved;
+    uint64_t entry_count;   /* over all sources */
+    uint64_t loaded_nodes;  /* distinct nodes with an entry */
+    uint64_t curve_points;  /* over all sources */
+    uint64_t device_bytes;  /* what the set holds in the stepper's arena */
+} cwf_explicit_source_info;
+
+/* Replaces the set in force by `count` sources (1 .. CWF_EXPLICIT_MAX_SOURCES); count == 0 removes it, writes f_ext
+ * back and frees its buffers (the stepper then launches what a stepper that never had sources launches). u, v, the step
+ * count, f_ext, dashpots and monitors are kept. On the device: a CSR over the loaded nodes in the handle's node order
+ * (the ids move through the permutation as set_dashpots' slots do), per entry a 32-byte record A | tau and 8 bytes of
+ * curve directory, the curves' tables, and 12 bytes of f_ext per loaded node; all in the stepper's arena. Everything
+ * refusable is checked on the host before anything changes, and a refusal leaves the previous set in force:
+ * CWF_ERR_SIZE "too many load sources" {count=<n>, max=8} and "load source curve must have 1 to 4096 points"
+ * {source=<s>, count=<n>}; CWF_ERR_ARGUMENT "null pointer" {source=<s>}, "load source has no entries" {source=<s>},
+ * "load source curve is not finite" / "load source curve times must ascend" {source=<s>, index=<i>}, "load source node
+ * out of range" / "load source node listed twice" {source=<s>, index=<i>, node=<id>}, "load source entry is not
+ * finite" {source=<s>, index=<i>}; CWF_ERR_UNSUPPORTED "load sources and a load pattern exclude each other" when a load
+ * pattern is set (cwf_hip_explicit_set_load_pattern answers the same while sources are in force); CWF_ERR_ALLOC. */
+int cwf_hip_explicit_set_sources(cwf_hip_explicit *ex, const cwf_explicit_source_desc *sources, uint32_t count);
+/* The set in force as it was given: *count sources; `sources` (nullable: count only; else room for
+ * CWF_EXPLICIT_MAX_SOURCES) is filled with pointers into the stepper's own copies, valid until the next set_sources
+ * or destroy. */
+int cwf_hip_explicit_get_sources(cwf_hip_explicit *ex, uint32_t *count, cwf_explicit_source_desc *sources);
+int cwf_hip_explicit_source_info(cwf_hip_explicit *ex, cwf_explicit_source_info *info);
 /* Host only, no GPU: P and Q of the scheme above from C (row-major), the node's mass, alpha_R and dt, by the
  * closed-form 3x3 inverse. CWF_ERR_ARGUMENT for a C that is not finite ("dashpot matrix is not finite"), not symmetric
  * (|C_ij - C_ji| > 1e-12 trace: "dashpot matrix is not symmetric") or not positive semidefinite (a principal minor
@@ -599,6 +659,29 @@ int cwf_absorbing_dashpots(uint64_t node_count, const double *coords, uint64_t e
                            const double *lame_lambda, const double *lame_mu, uint64_t face_count,
                            uint32_t nodes_per_face, const uint32_t *faces, uint64_t *count, uint32_t *node_ids,
                            double *C);
+/* Host only, no GPU: an obliquely incident plane wave through the viscous boundary of a face list, as entries of a load
+ * source. The wave has particle velocity d g(t - tau), tau = khat . (x - x0) / c, khat = propagation / |propagation|,
+ * d = polarisation as given (not normalised), c = V_p when d is parallel to khat and V_s when it is perpendicular:
+ * with q = |d . khat| / (|d| |khat|), q >= 1 - CWF_PLANE_WAVE_TOLERANCE is a P wave, q <= CWF_PLANE_WAVE_TOLERANCE an
+ * S wave, anything between is refused. Its stress is sigma = -(g / c) [lambda (d . khat) I + mu (d khat^T + khat
+ * d^T)]. A boundary node gets the dashpot's share plus the free-field traction,
+ *     A_n = sum over its faces (a_f / k_f) [rho (V_p nu nu^T + V_s (I - nu nu^T)) d + S nu],   S = sigma / g,
+ * nu the face's outward unit normal (away from the owning element's centroid, whatever the face's winding), a_f and
+ * k_f as in cwf_absorbing_dashpots; the first term sums to C_n d. tau_n = khat . (x_n - x0) / c. For khat = -nu on a
+ * flat face this is 2 C_n d with equal delays, cwf.absorbing.incident_pattern. Mesh, materials and faces as in
+ * cwf_absorbing_dashpots, and its errors; all owning elements must share one material: CWF_ERR_UNSUPPORTED "plane wave
+ * faces span more than one material" {face=<i>, material=<m>, first_material=<m0>}. CWF_ERR_ARGUMENT "propagation
+ * must be a non-zero finite vector", "polarisation must be a non-zero finite vector", "polarisation is neither
+ * parallel nor perpendicular to the propagation" {cosine=<q>}. Out: *count nodes ascending in node_ids, A (3 per
+ * node), tau (1 per node), room as in cwf_absorbing_dashpots; *wave_speed (nullable) = c. */
+#define CWF_PLANE_WAVE_TOLERANCE 1e-9
+int cwf_absorbing_incident_plane(uint64_t node_count, const double *coords, uint64_t element_count,
+                                 uint32_t nodes_per_element, const uint32_t *connectivity,
+                                 const uint32_t *element_material, uint64_t material_count, const double *rho,
+                                 const double *lame_lambda, const double *lame_mu, uint64_t face_count,
+                                 uint32_t nodes_per_face, const uint32_t *faces, const double polarisation[3],
+                                 const double propagation[3], const double origin[3], uint64_t *count,
+                                 uint32_t *node_ids, double *A, double *tau, double *wave_speed);
 /* lambda_max of M^-1 K over the free DOFs by `iterations` (0 -> 60) power iterations from a fixed start vector (a hash
  * of the node index), the handle's operator at scalars (1, 0) and fp64 dots in a fixed order: the same handle gives
  * the same bits on every call. The estimate is the quotient (K x . M^-1 K x) / (x . K x), which approaches lambda_max

@@ -4,6 +4,7 @@
     python tools/explicit_bench.py [--configs c2 c3 c2:hex8] [--steps 2000] [--newmark-steps 3] [--out FILE]
     python tools/explicit_bench.py --absorbing [--configs c3] [--steps 2000]
     python tools/explicit_bench.py --monitors [--configs c2 c3] [--steps 2000]
+    python tools/explicit_bench.py --sources [--configs c2 c3] [--steps 2000]
 
 Per config (a FAST handle of the block, created with scalars (1, 0)), in one process and one JSON line each, appended
 to --out (default profiles/explicit_c2.json):
@@ -25,6 +26,14 @@ of dashpot nodes and the bytes per node the update pass then moves (84 + 144 x s
 step_us of one stepper on one handle without monitors, with peak maps only, with the ledger only (energy_every 1 and
 100), with 64 receivers (every 1 and 10), with everything together, and after clear_monitors again, next to the
 estimate from bytes (the update pass's 80 B per node plus what the monitor moves, scaled from the plain step).
+
+--sources: the cost of load sources (include/cwf_hip.h "Load sources"). Per config one line, appended to
+profiles/explicit_sources.json, FAST handle, dashpots on the five faces other than z = max throughout: step_us with no
+time-varying load, with the vertical incident pattern and curve (the update pass's PATTERN instantiation), with the same
+wave as a source on the base, with an oblique plane-wave source on the five faces, with three sources on every node at
+zero delay (a three-component record), and after the set is removed; next to the loaded nodes, the entries and the bytes
+the source kernel moves by its layout (per loaded node 4 B node + 8 B offsets + 12 B f_ext + 12 B stored, per entry a
+32-B record + 8 B curve directory; the curve's knots are shared and stay in L2).
 """
 import argparse
 import ctypes as C
@@ -188,6 +197,81 @@ def measure_monitors(key, steps, device):
     return out
 
 
+def five_faces(case):
+    """The boundary faces of the block other than z = max, and those of z = min alone."""
+    import numpy as np
+
+    from cwf import meshgen
+
+    P, m = case.packing, case.mesh
+    X = m.coords
+    lo, hi = X.min(0), X.max(0)
+    k = m.tets.shape[1]
+    faces = []
+    for axis, value in ((2, lo[2]), (0, lo[0]), (0, hi[0]), (1, lo[1]), (1, hi[1])):
+        on = np.nonzero(X[:, axis] == value)[0]
+        sel = np.zeros(P.node_count, bool)
+        sel[on] = True
+        t = m.tets[sel[m.tets].sum(1) >= (4 if k == 8 else 3)]  # only elements with a face on that plane
+        faces.append(meshgen.boundary_faces(t, on))
+    return np.concatenate(faces), faces[0]
+
+
+def measure_sources(key, steps, device):
+    import math
+
+    import numpy as np
+
+    from cwf import absorbing
+    from cwf.explicit import LoadSource
+
+    name, _, element = key.partition(":")
+    case = scenarios.config_case(name, element=element or "tet4")
+    P, m = case.packing, case.mesh
+    N = P.node_count
+    faces, base = five_faces(case)
+    ids, Cn = absorbing.dashpots(m, case.cfg, faces)
+    bid, bC = absorbing.dashpots(m, case.cfg, base)
+    sysm = pcg.MatrixFreeSystem.from_packing(P, case.materials, 1.0, 0.0, mode=_lib.MODE_FAST, device=device)
+    out = dict(config=key, name=case.name, nodes=N, steps=steps, dashpot_nodes=int(ids.size),
+               kernel=(_lib.load().cwf_hip_system_keff_kernel(sysm.handle()) or b"").decode())
+    ex = ExplicitStepper(P, case.materials, RayleighCoefficients(0.0, 0.0), system=sysm)
+    dt = ex.telemetry().dt
+    out["dt"] = dt
+    ex.set_dashpots(ids, Cn)
+    # a Gaussian velocity pulse over the whole run, 1024 points
+    total = 2 * (200 + steps) * dt
+    t = np.linspace(0.0, 6.0 * total, 1024)
+    curve = list(zip(t, 1e-3 * np.exp(-0.5 * ((t - 0.5 * total) / (0.1 * total)) ** 2)))
+    d = np.array([0.0, 0.0, 1.0])
+    out["step_us_plain"] = timed_steps(ex, steps)
+    pat = ExplicitStepper(P, case.materials, RayleighCoefficients(0.0, 0.0), system=sysm, dt=dt)
+    pat.set_dashpots(ids, Cn)
+    pat.set_load_pattern(np.zeros(P.dof_count), absorbing.incident_pattern(bid, bC, d, N))
+    pat.set_load_curve(curve)
+    out["step_us_pattern"] = timed_steps(pat, steps)
+    pat.close()
+    a = math.radians(30.0)
+    khat = np.array([math.sin(a), 0.0, math.cos(a)])
+    oid, oA, otau, _ = absorbing.incident_plane_wave(m, case.cfg, faces, khat, khat, m.coords.min(0))
+    rec = [LoadSource(curve, np.arange(N, dtype=np.uint32), np.eye(3)[k][None, :] * np.ones((N, 1)), np.zeros(N))
+           for k in range(3)]
+    sets = [("source_vertical", [LoadSource(curve, bid, 2.0 * (bC @ d), np.zeros(bid.size))]),
+            ("source_oblique", [LoadSource(curve, oid, oA, otau)]),
+            ("dense_three", rec),
+            ("removed", [])]
+    for label, srcs in sets:
+        ex.set_sources(srcs)
+        i = ex.source_info()
+        out["step_us_" + label] = timed_steps(ex, steps)
+        if srcs:
+            out[label] = dict(loaded_nodes=i.loaded_nodes, entries=i.entry_count, device_bytes=i.device_bytes,
+                              kernel_bytes_per_step=36 * i.loaded_nodes + 40 * i.entry_count)
+    ex.close()
+    sysm.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", nargs="+", default=["c2", "c3", "c2:hex8"])
@@ -196,17 +280,21 @@ def main():
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--absorbing", action="store_true", help="the cost of dashpots on five faces (see above)")
     ap.add_argument("--monitors", action="store_true", help="the cost of the monitors (see above)")
+    ap.add_argument("--sources", action="store_true", help="the cost of load sources (see above)")
     ap.add_argument("--out", default=None, help="default profiles/explicit_c2.json (--absorbing: "
                                                  "profiles/explicit_absorbing.json, --monitors: "
-                                                 "profiles/explicit_monitors.json)")
+                                                 "profiles/explicit_monitors.json, --sources: "
+                                                 "profiles/explicit_sources.json)")
     a = ap.parse_args()
-    a.out = a.out or os.path.join(ROOT, "profiles", "explicit_monitors.json" if a.monitors else
+    a.out = a.out or os.path.join(ROOT, "profiles", "explicit_sources.json" if a.sources else
+                                  "explicit_monitors.json" if a.monitors else
                                   "explicit_absorbing.json" if a.absorbing else "explicit_c2.json")
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     if a.configs == ap.get_default("configs"):
-        a.configs = ["c2", "c3"] if a.monitors else ["c3"] if a.absorbing else a.configs
+        a.configs = ["c2", "c3"] if a.monitors or a.sources else ["c3"] if a.absorbing else a.configs
     for key in a.configs:
-        line = json.dumps(measure_monitors(key, a.steps, a.device) if a.monitors else
+        line = json.dumps(measure_sources(key, a.steps, a.device) if a.sources else
+                          measure_monitors(key, a.steps, a.device) if a.monitors else
                           measure_absorbing(key, a.steps, a.device) if a.absorbing else
                           measure(key, a.steps, a.newmark_steps, a.device))
         print(line, flush=True)
