@@ -68,6 +68,24 @@ struct cwf_hip_explicit : TransientState
             *this = Sources();
         }
     } src;
+    // set_element_monitors: the set in force, its device buffers (the stepper's arena) and the host's sample bookkeeping
+    struct ElementMonitors
+    {
+        uint64_t gcount = 0, gevery = 0, gcap = 0, gdropped = 0;
+        uint32_t *gelem = nullptr;     // [gcount] the gauge elements (elements keep the caller's numbering)
+        float *grows = nullptr;        // [gcap][gcount][13]
+        std::vector<uint64_t> gsteps;  // the step count of each row held
+        uint64_t eevery = 0, esamples = 0, stride = 0;
+        uint32_t maps = 0;
+        float *vm = nullptr, *shear = nullptr;  // [stride]
+        float *range = nullptr;                 // [12][stride]: min of component c at plane c, max at 6 + c
+        void release(DeviceArena &mem)
+        {
+            for (void *p : {(void *)gelem, (void *)grows, (void *)vm, (void *)shear, (void *)range})
+                mem.free(p);
+            *this = ElementMonitors();
+        }
+    } emon;
 };
 
 namespace
@@ -312,6 +330,14 @@ int cwf_hip_explicit_advance(cwf_hip_explicit *t, uint64_t n_steps, cwf_explicit
     a.dC = dash ? t->dC : nullptr;
     a.alpha = t->alpha;
     const uint32_t blocks = explicit_update_blocks(s.N);
+    cwf_hip_explicit::ElementMonitors &em = t->emon;
+    ExplicitElementPass ep{};
+    ep.von_mises = em.vm;
+    ep.shear_strain = em.shear;
+    ep.stress_range = em.range;
+    ep.stride = em.stride;
+    ep.gauge_count = (uint32_t)em.gcount;
+    ep.gauge_elements = em.gelem;
     for (uint64_t i = 0; i < n_steps; ++i)
     {
         if (pattern)
@@ -343,6 +369,24 @@ int cwf_hip_explicit_advance(cwf_hip_explicit *t, uint64_t n_steps, cwf_explicit
             }
             else
                 ++mon.rdropped;
+        }
+        // element monitors: u_steps through the post stack's element pass, envelopes over all elements, gauges per gauge
+        if (em.eevery || em.gcount)
+        {
+            ep.envelope = em.eevery && t->steps % em.eevery == 0;
+            ep.gauge_row = nullptr;
+            if (em.gcount && t->steps % em.gevery == 0)
+            {
+                if (em.gsteps.size() < em.gcap)
+                    ep.gauge_row = em.grows + 13 * em.gcount * em.gsteps.size();
+                else
+                    ++em.gdropped;
+            }
+            explicit_element_monitors(s, t->u, ep, st);
+            if (ep.envelope)
+                ++em.esamples;
+            if (ep.gauge_row)
+                em.gsteps.push_back(t->steps);
         }
     }
     if (n_steps)
@@ -978,6 +1022,228 @@ int cwf_hip_explicit_read_energy(cwf_hip_explicit *t, uint64_t first, uint64_t c
         HIPTRY(h, hipMemcpyAsync(rows, m.erows + 4 * first, 4 * count * sizeof(double), hipMemcpyDeviceToHost,
                                  h->stream));
     HIPTRY(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+namespace
+{
+const uint32_t kBitsPlusInf = 0x7F800000u, kBitsMinusInf = 0xFF800000u;
+
+// the maps at their start values: von Mises and shear strain +0.0, the stress minima +inf, the maxima -inf
+hipError_t start_envelopes(const cwf_hip_explicit::ElementMonitors &m, hipStream_t s)
+{
+    hipError_t e = hipSuccess;
+    if (m.vm)
+        e = hipMemsetAsync(m.vm, 0, m.stride * sizeof(float), s);
+    if (e == hipSuccess && m.shear)
+        e = hipMemsetAsync(m.shear, 0, m.stride * sizeof(float), s);
+    if (e == hipSuccess && m.range)
+        e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(m.range), (int)kBitsPlusInf, 6 * m.stride, s);
+    if (e == hipSuccess && m.range)
+        e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(m.range + 6 * m.stride), (int)kBitsMinusInf,
+                              6 * m.stride, s);
+    return e;
+}
+}  // namespace
+
+}  // extern "C"
+
+// what cwf_hip_explicit_set_element_monitors refuses of a desc, on the host alone: 0, or the code with *msg and *ctx
+int cwf::element_monitor_refusal(const cwf_explicit_element_monitor_desc &d, uint64_t E, std::string *msg,
+                                 std::string *ctx)
+{
+    const auto no = [&](const char *m, std::string c = std::string()) {
+        *msg = m;
+        *ctx = std::move(c);
+        return (int)CWF_ERR_ARGUMENT;
+    };
+    if (d.gauge_count && !d.gauge_elements)
+        return no("null pointer");
+    if (d.gauge_count && d.gauge_every < 1)
+        return no("gauge_every must be at least 1");
+    if (d.gauge_count && !d.gauge_capacity)
+        return no("monitor capacity must not be zero", "gauge_capacity=" + std::to_string(d.gauge_capacity));
+    const uint32_t known = CWF_ENVELOPE_VON_MISES | CWF_ENVELOPE_SHEAR_STRAIN | CWF_ENVELOPE_STRESS_RANGE;
+    if (d.envelope_maps & ~known)
+        return no("unknown envelope map", "maps=" + std::to_string(d.envelope_maps));
+    if (d.envelope_maps && !d.envelope_every)
+        return no("envelope_maps without envelope_every", "maps=" + std::to_string(d.envelope_maps));
+    if (d.envelope_every && !d.envelope_maps)
+        return no("envelope_every without envelope_maps", "envelope_every=" + std::to_string(d.envelope_every));
+    std::vector<bool> seen(d.gauge_count ? E : 0, false);
+    for (uint64_t i = 0; i < d.gauge_count; ++i)
+    {
+        const uint32_t e = d.gauge_elements[i];
+        if (e >= E)
+            return no("gauge element out of range", "index=" + std::to_string(i) + "\nelement=" + std::to_string(e));
+        if (seen[e])
+            return no("gauge element listed twice", "index=" + std::to_string(i) + "\nelement=" + std::to_string(e));
+        seen[e] = true;
+    }
+    return 0;
+}
+
+extern "C" {
+
+int cwf_hip_explicit_set_element_monitors(cwf_hip_explicit *t, const cwf_explicit_element_monitor_desc *desc)
+{
+    if (!t)
+        return set_error(nullptr, CWF_ERR_ARGUMENT, "null handle");
+    cwf_hip_system *h = t->sys;
+    if (int st = check_ready(h))
+        return st;
+    hipStream_t s = h->stream;
+    const cwf_explicit_element_monitor_desc none{};
+    const cwf_explicit_element_monitor_desc &d = desc ? *desc : none;
+    const uint64_t E = h->ds.E;
+    // everything that can be refused, on the host, before anything changes
+    std::string msg, ctx;
+    if (int code = element_monitor_refusal(d, E, &msg, &ctx))
+        return set_error(h, code, msg, ctx);
+    const uint64_t kMaxBytes = 1ull << 44;  // no device holds more: a product past it is an allocation failure
+    if (d.gauge_count && d.gauge_capacity > kMaxBytes / (52 * d.gauge_count))
+        return set_error(h, CWF_ERR_ALLOC, t->alloc_error);
+    HIPTRY(h, hipStreamSynchronize(s));
+    // the new set's buffers; the stepper's once everything went well
+    cwf_hip_explicit::ElementMonitors m;
+    int st = 0;
+    if (d.gauge_count)
+    {
+        m.gcount = d.gauge_count;
+        m.gevery = d.gauge_every;
+        m.gcap = d.gauge_capacity;
+        st = st ? st : t->alloc(&m.gelem, m.gcount);
+        st = st ? st : t->alloc(&m.grows, (size_t)(13 * m.gcount * m.gcap));
+    }
+    if (d.envelope_every)
+    {
+        m.eevery = d.envelope_every;
+        m.maps = d.envelope_maps;
+        m.stride = std::max<uint64_t>(E, 4);
+        if (m.maps & CWF_ENVELOPE_VON_MISES)
+            st = st ? st : t->alloc(&m.vm, m.stride);
+        if (m.maps & CWF_ENVELOPE_SHEAR_STRAIN)
+            st = st ? st : t->alloc(&m.shear, m.stride);
+        if (m.maps & CWF_ENVELOPE_STRESS_RANGE)
+            st = st ? st : t->alloc(&m.range, 12 * m.stride);
+    }
+    hipError_t e = hipSuccess;
+    if (!st && m.gcount)  // elements keep the caller's numbering on the device: the ids go up as given
+        e = hipMemcpyAsync(m.gelem, d.gauge_elements, m.gcount * sizeof(uint32_t), hipMemcpyHostToDevice, s);
+    if (!st && e == hipSuccess)
+        e = start_envelopes(m, s);
+    if (!st && e == hipSuccess)
+        e = hipStreamSynchronize(s);
+    if (st || e != hipSuccess)
+    {
+        (void)hipStreamSynchronize(s);
+        m.release(t->mem);
+        return st ? st : hip_fail(h, e, "explicit set_element_monitors");
+    }
+    m.gsteps.reserve((size_t)std::min<uint64_t>(m.gcap, 1u << 20));
+    t->emon.release(t->mem);
+    t->emon = std::move(m);
+    return 0;
+}
+
+int cwf_hip_explicit_reset_element_monitors(cwf_hip_explicit *t)
+{
+    if (!t)
+        return set_error(nullptr, CWF_ERR_ARGUMENT, "null handle");
+    cwf_hip_system *h = t->sys;
+    if (int st = check_ready(h))
+        return st;
+    cwf_hip_explicit::ElementMonitors &m = t->emon;
+    HIPTRY(h, start_envelopes(m, h->stream));
+    HIPTRY(h, hipStreamSynchronize(h->stream));
+    m.gsteps.clear();
+    m.gdropped = m.esamples = 0;
+    return 0;
+}
+
+int cwf_hip_explicit_element_monitor_info(cwf_hip_explicit *t, cwf_explicit_element_monitor_info *info)
+{
+    if (!t || !info)
+        return set_error(nullptr, CWF_ERR_ARGUMENT, "null pointer");
+    const cwf_hip_explicit::ElementMonitors &m = t->emon;
+    cwf_explicit_element_monitor_info I{};
+    I.gauge_count = m.gcount;
+    I.gauge_every = m.gevery;
+    I.gauge_capacity = m.gcap;
+    I.gauge_samples = m.gsteps.size();
+    I.gauge_dropped = m.gdropped;
+    I.envelope_every = m.eevery;
+    I.envelope_samples = m.esamples;
+    I.envelope_maps = m.maps;
+    *info = I;
+    return 0;
+}
+
+int cwf_hip_explicit_read_gauges(cwf_hip_explicit *t, uint64_t first, uint64_t count, uint64_t *steps, float *rows)
+{
+    if (!t)
+        return set_error(nullptr, CWF_ERR_ARGUMENT, "null handle");
+    cwf_hip_system *h = t->sys;
+    if (int st = check_ready(h))
+        return st;
+    const cwf_hip_explicit::ElementMonitors &m = t->emon;
+    if (int st = rows_in_range(h, first, count, m.gsteps.size()))
+        return st;
+    if (!count)
+        return 0;
+    if (steps)
+        std::copy(m.gsteps.begin() + first, m.gsteps.begin() + first + count, steps);
+    if (rows)
+        HIPTRY(h, hipMemcpyAsync(rows, m.grows + 13 * m.gcount * first, (size_t)(13 * m.gcount * count) * sizeof(float),
+                                 hipMemcpyDeviceToHost, h->stream));
+    HIPTRY(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+int cwf_hip_explicit_read_envelopes(cwf_hip_explicit *t, float *von_mises, float *shear_strain, float *stress_min,
+                                    float *stress_max, uint64_t n, int kind)
+{
+    if (!t)
+        return set_error(nullptr, CWF_ERR_ARGUMENT, "null handle");
+    cwf_hip_system *h = t->sys;
+    if (int st = check_ready(h))
+        return st;
+    const cwf_hip_explicit::ElementMonitors &m = t->emon;
+    if ((von_mises && !m.vm) || (shear_strain && !m.shear) || ((stress_min || stress_max) && !m.range))
+        return set_error(h, CWF_ERR_ARGUMENT, "envelope map is not set", "maps=" + std::to_string(m.maps));
+    const uint64_t E = h->ds.E;
+    if (n != E)
+        return set_error(h, CWF_ERR_SIZE, "envelope map span size mismatch",
+                         "span=" + std::to_string(n) + "\nelements=" + std::to_string(E));
+    hipStream_t s = h->stream;
+    const hipMemcpyKind back = kind == CWF_PTR_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (von_mises)
+        HIPTRY(h, hipMemcpyAsync(von_mises, m.vm, E * sizeof(float), back, s));
+    if (shear_strain)
+        HIPTRY(h, hipMemcpyAsync(shear_strain, m.shear, E * sizeof(float), back, s));
+    // the stress range: plane c of the device layout is column c of the caller's [E][6]
+    float *const out[2] = {stress_min, stress_max};
+    std::vector<float> plane;
+    for (int q = 0; q < 2; ++q)
+    {
+        if (!out[q])
+            continue;
+        const float *src = m.range + 6 * q * m.stride;
+        if (kind == CWF_PTR_DEVICE)
+        {
+            for (int c = 0; c < 6; ++c)
+                HIPTRY(h, hipMemcpy2DAsync(out[q] + c, 6 * sizeof(float), src + c * m.stride, sizeof(float),
+                                           sizeof(float), E, hipMemcpyDeviceToDevice, s));
+            continue;
+        }
+        plane.resize(6 * m.stride);
+        HIPTRY(h, hipMemcpyAsync(plane.data(), src, plane.size() * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIPTRY(h, hipStreamSynchronize(s));
+        for (uint64_t e = 0; e < E; ++e)
+            for (int c = 0; c < 6; ++c)
+                out[q][6 * e + c] = plane[c * m.stride + e];
+    }
+    HIPTRY(h, hipStreamSynchronize(s));
     return 0;
 }
 

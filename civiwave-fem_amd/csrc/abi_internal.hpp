@@ -274,4 +274,9 @@ int transient_set(TransientState &c, const char *what, float *dst, const float *
 int transient_set_load_pattern(TransientState &c, const double *base, const double *pattern, uint64_t n);
 int transient_time(double now, double dt, double *current_time, double *time_step);
 
+// abi_explicit.cpp: what cwf_hip_explicit_set_element_monitors refuses of a desc for a handle of E elements, on the
+// host alone (no device, no handle): 0, or the error code with the message in *msg and its context lines in *ctx
+int element_monitor_refusal(const cwf_explicit_element_monitor_desc &d, uint64_t E, std::string *msg,
+                            std::string *ctx);
+
 }  // namespace cwf

@@ -654,6 +654,20 @@ bool x_flush_iter(unsigned j);  // iteration j's update applies the lazy x terms
 // sharded FAST PCG (comm.cpp orchestrates; fast_dispatch.hip, pcg_update.hip and kernels_fast.hip launch)
 // post.hip: derived fields (derived_fields.cpp:139-211) -> f32 [13 E] / [13 N] (either may be NULL)
 void derived_fields(cwf_hip_system *h, const float *u, float *elem_out, float *node_out, hipStream_t st);
+// post.hip: the explicit stepper's element monitors of one sampled step (cwf_hip_explicit_set_element_monitors); u in
+// the handle's node order. envelope: this step is due, the maps that are set (NULL: not) are raised; gauge_row (NULL:
+// no gauge sample at this step): the sample's row [gauge_count][13]
+struct ExplicitElementPass
+{
+    bool envelope;
+    float *von_mises, *shear_strain;  // [E] each
+    float *stress_range;              // 12 planes `stride` floats apart: min of component c at c, max at 6 + c
+    uint64_t stride;
+    uint32_t gauge_count;
+    const uint32_t *gauge_elements;   // [gauge_count]
+    float *gauge_row;
+};
+void explicit_element_monitors(const DevSys &s, const float *u, const ExplicitElementPass &a, hipStream_t st);
 bool fast_direct_fold(const cwf_hip_system *h);  // unsharded: consumers fold per-workgroup shares
 void fast_fold_pap(cwf_hip_system *h, hipStream_t st);  // local p.Ap shares -> g_pap[rank]
 void fast_fold_rrz(cwf_hip_system *h, unsigned it, hipStream_t st);  // local r.r / r.z shares -> g_rrz[2 rank]

@@ -108,6 +108,18 @@ __device__ __forceinline__ double von_mises(const double s[6])
     return sqrt(energy < 0.0 ? 0.0 : energy);  // std::max(energy, 0.0), NaN passes through
 }
 
+// the 52-B element record {strain[6], stress[6], vm} of one element's tensors
+__device__ __forceinline__ void store_element_record(float *__restrict__ o, const ElemTensors &t)
+{
+#pragma unroll
+    for (int c = 0; c < 6; ++c)
+    {
+        o[c] = (float)t.strain[c];
+        o[6 + c] = (float)t.stress[c];
+    }
+    o[12] = (float)von_mises(t.stress);
+}
+
 template <bool ISO, bool HEX>
 __global__ __launch_bounds__(kBlock) void k_derived_elements(DevSys s, const float *__restrict__ u,
                                                              float *__restrict__ out)
@@ -117,14 +129,86 @@ __global__ __launch_bounds__(kBlock) void k_derived_elements(DevSys s, const flo
         return;
     ElemTensors t;
     element_tensors<ISO, HEX>(s, u, e, t);
-    float *o = out + 13ull * e;
-#pragma unroll
-    for (int c = 0; c < 6; ++c)
+    store_element_record(out + 13ull * e, t);
+}
+
+// Element monitors of the explicit stepper (include/cwf_hip.h "Element monitors"). They live here so that strain,
+// stress and von Mises are the code above, under this file's flags.
+//
+// Gauges: one thread per gauge element, its derived-fields record into the sample's row [count][13].
+template <bool ISO, bool HEX>
+__global__ __launch_bounds__(kBlock) void k_explicit_gauges(DevSys s, const float *__restrict__ u, uint32_t count,
+                                                            const uint32_t *__restrict__ elem, float *__restrict__ row)
+{
+    const uint32_t r = blockIdx.x * kBlock + threadIdx.x;
+    if (r >= count)
+        return;
+    ElemTensors t;
+    element_tensors<ISO, HEX>(s, u, elem[r], t);
+    store_element_record(row + 13ull * r, t);
+}
+
+// the effective shear strain 2 sqrt(J2) of the strain deviator (engineering shears), in the header's statement order
+__device__ __forceinline__ double effective_shear_strain(const double e[6])
+{
+    const double d0 = e[0] - e[1], d1 = e[1] - e[2], d2 = e[2] - e[0];
+    const double sd = d0 * d0 + d1 * d1 + d2 * d2;
+    const double sg = e[3] * e[3] + e[4] * e[4] + e[5] * e[5];
+    return sqrt(sd * (2.0 / 3.0) + sg);
+}
+
+// Envelopes: one thread per element. Every map is a plane of one f32 per element (the stress range: planes c and
+// 6 + c hold min and max of component c, `stride` floats apart), so a wavefront reads and writes consecutive words.
+// The maps' old values are loaded first, next to the element's records and its u gathers; a value is stored only
+// where it replaces the old one. Which maps are active is uniform over the launch (NULL: not set).
+template <bool ISO, bool HEX>
+__global__ __launch_bounds__(kBlock) void k_explicit_envelope(DevSys s, const float *__restrict__ u,
+                                                              float *__restrict__ vm, float *__restrict__ shear,
+                                                              float *__restrict__ range, uint64_t stride)
+{
+    const uint32_t e = blockIdx.x * kBlock + threadIdx.x;
+    if (e >= s.E)
+        return;
+    float old_vm = 0.f, old_shear = 0.f, lo[6], hi[6];
+    if (vm)
+        old_vm = vm[e];
+    if (shear)
+        old_shear = shear[e];
+    if (range)
     {
-        o[c] = (float)t.strain[c];
-        o[6 + c] = (float)t.stress[c];
+#pragma unroll
+        for (int c = 0; c < 6; ++c)
+        {
+            lo[c] = range[c * stride + e];
+            hi[c] = range[(6 + c) * stride + e];
+        }
     }
-    o[12] = (float)von_mises(t.stress);
+    ElemTensors t;
+    element_tensors<ISO, HEX>(s, u, e, t);
+    if (vm)
+    {
+        const float x = (float)von_mises(t.stress);
+        if (x > old_vm)
+            vm[e] = x;
+    }
+    if (shear)
+    {
+        const float x = (float)effective_shear_strain(t.strain);
+        if (x > old_shear)
+            shear[e] = x;
+    }
+    if (range)
+    {
+#pragma unroll
+        for (int c = 0; c < 6; ++c)
+        {
+            const float x = (float)t.stress[c];
+            if (x < lo[c])
+                range[c * stride + e] = x;
+            if (x > hi[c])
+                range[(6 + c) * stride + e] = x;
+        }
+    }
 }
 
 template <bool ISO, bool HEX>
@@ -188,7 +272,28 @@ void derived_fields_k(const DevSys &s, const float *u, float *elem_out, float *n
             k_derived_nodes<false, HEX><<<grid_for(s.N), kBlock, 0, st>>>(s, u, node_out);
     }
 }
+
+template <bool ISO, bool HEX>
+void element_monitors_k(const DevSys &s, const float *u, const ExplicitElementPass &a, hipStream_t st)
+{
+    if (a.envelope)
+        k_explicit_envelope<ISO, HEX><<<grid_for(s.E), kBlock, 0, st>>>(s, u, a.von_mises, a.shear_strain,
+                                                                        a.stress_range, a.stride);
+    if (a.gauge_row)
+        k_explicit_gauges<ISO, HEX><<<grid_for(a.gauge_count), kBlock, 0, st>>>(s, u, a.gauge_count, a.gauge_elements,
+                                                                                a.gauge_row);
+}
 }  // namespace
+
+void explicit_element_monitors(const DevSys &s, const float *u, const ExplicitElementPass &a, hipStream_t st)
+{
+    if (!s.E || (!a.envelope && !a.gauge_row))
+        return;
+    if (s.hex)
+        s.iso ? element_monitors_k<true, true>(s, u, a, st) : element_monitors_k<false, true>(s, u, a, st);
+    else
+        s.iso ? element_monitors_k<true, false>(s, u, a, st) : element_monitors_k<false, false>(s, u, a, st);
+}
 
 void derived_fields(cwf_hip_system *h, const float *u, float *elem_out, float *node_out, hipStream_t st)
 {

@@ -119,6 +119,21 @@ class ExplicitMonitorInfoC(C.Structure):
                 ("peaks", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+ENVELOPE_VON_MISES, ENVELOPE_SHEAR_STRAIN, ENVELOPE_STRESS_RANGE = 1, 2, 4
+
+
+class ExplicitElementMonitorDescC(C.Structure):
+    _fields_ = [("gauge_count", C.c_uint64), ("gauge_elements", C.c_void_p), ("gauge_every", C.c_uint64),
+                ("gauge_capacity", C.c_uint64), ("envelope_every", C.c_uint64), ("envelope_maps", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class ExplicitElementMonitorInfoC(C.Structure):
+    _fields_ = [("gauge_count", C.c_uint64), ("gauge_every", C.c_uint64), ("gauge_capacity", C.c_uint64),
+                ("gauge_samples", C.c_uint64), ("gauge_dropped", C.c_uint64), ("envelope_every", C.c_uint64),
+                ("envelope_samples", C.c_uint64), ("envelope_maps", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class ExplicitSourceDescC(C.Structure):
     _fields_ = [("curve_points", C.c_uint64), ("times", C.c_void_p), ("values", C.c_void_p),
                 ("entry_count", C.c_uint64), ("node_ids", C.c_void_p), ("amplitude", C.c_void_p),
@@ -241,6 +256,11 @@ def load() -> C.CDLL:
         "cwf_hip_explicit_read_receivers": ([P, u64, u64, P, P, P], i32),
         "cwf_hip_explicit_read_peaks": ([P, P, P, P, u64, i32], i32),
         "cwf_hip_explicit_read_energy": ([P, u64, u64, P, P], i32),
+        "cwf_hip_explicit_set_element_monitors": ([P, P], i32),
+        "cwf_hip_explicit_reset_element_monitors": ([P], i32),
+        "cwf_hip_explicit_element_monitor_info": ([P, P], i32),
+        "cwf_hip_explicit_read_gauges": ([P, u64, u64, P, P], i32),
+        "cwf_hip_explicit_read_envelopes": ([P, P, P, P, P, u64, i32], i32),
         "cwf_hip_explicit_set_sources": ([P, P, C.c_uint32], i32),
         "cwf_hip_explicit_get_sources": ([P, P, P], i32),
         "cwf_hip_explicit_source_info": ([P, P], i32),

@@ -87,6 +87,62 @@ class EnergyLedger:
         return self.total() - self.work + self.dissipated
 
 
+@dataclass
+class ElementMonitorInfo:
+    gauge_count: int
+    gauge_every: int
+    gauge_capacity: int
+    gauge_samples: int
+    gauge_dropped: int
+    envelope_every: int
+    envelope_samples: int
+    von_mises: bool
+    shear_strain: bool
+    stress_range: bool
+
+
+@dataclass
+class GaugeTraces:
+    """Rows of the gauge buffer: {strain[6], stress[6], von_mises} of the gauge elements for u at the step counts
+    ``steps`` (time = steps x dt), the rows cwf.post derives from the same u."""
+    steps: np.ndarray   # u64 [samples]
+    time: np.ndarray    # f64 [samples]
+    rows: np.ndarray    # f32 [samples, gauges, 13]
+
+    @property
+    def strain(self) -> np.ndarray:
+        return self.rows[:, :, 0:6]
+
+    @property
+    def stress(self) -> np.ndarray:
+        return self.rows[:, :, 6:12]
+
+    @property
+    def von_mises(self) -> np.ndarray:
+        return self.rows[:, :, 12]
+
+
+@dataclass
+class Envelopes:
+    """The envelope maps that are set (the others None), the caller's element order (include/cwf_hip.h "Element
+    monitors"): peak von Mises stress and peak effective shear strain f32 [E], the six stresses' minima and maxima
+    f32 [E,6]."""
+    von_mises: np.ndarray | None = None
+    shear_strain: np.ndarray | None = None
+    stress_min: np.ndarray | None = None
+    stress_max: np.ndarray | None = None
+
+
+def effective_shear_strain(strain) -> np.ndarray:
+    """The envelope's effective shear strain of Voigt strains [..., 6] (engineering shears), float64, in the header's
+    statement order: 2 sqrt(J2) of the strain deviator, |gamma| in pure shear (host only)."""
+    e = np.asarray(strain, np.float64)
+    d0, d1, d2 = e[..., 0] - e[..., 1], e[..., 1] - e[..., 2], e[..., 2] - e[..., 0]
+    sd = d0 * d0 + d1 * d1 + d2 * d2
+    sg = e[..., 3] * e[..., 3] + e[..., 4] * e[..., 4] + e[..., 5] * e[..., 5]
+    return np.sqrt(sd * (2.0 / 3.0) + sg)
+
+
 MAX_SOURCES = 8  # CWF_EXPLICIT_MAX_SOURCES
 
 
@@ -164,6 +220,7 @@ class ExplicitStepper(TransientState):
         self._ex = ex
         self.dof_count = packing.dof_count
         self.node_count = packing.node_count
+        self.element_count = packing.element_count
 
     def advance(self, n_steps: int) -> Expected:
         t = _lib.ExplicitTelemetryC()
@@ -313,3 +370,58 @@ class ExplicitStepper(TransientState):
         self._check(_lib.load().cwf_hip_explicit_read_energy(self._ex, 0, n, _lib.ptr(steps), _lib.ptr(rows)))
         return EnergyLedger(steps, steps.astype(np.float64) * self.time_step(), rows[:, 0].copy(), rows[:, 1].copy(),
                             rows[:, 2].copy(), rows[:, 3].copy())
+
+    # ---- element monitors (include/cwf_hip.h "Element monitors") ----
+    def set_element_monitors(self, gauges=None, gauge_every: int = 1, gauge_capacity: int = 0,
+                             envelope_every: int = 0, von_mises: bool = False, shear_strain: bool = False,
+                             stress_range: bool = False):
+        """Gauge rows {strain, stress, von Mises} at the elements ``gauges`` (distinct ids) every ``gauge_every``
+        steps, and every ``envelope_every`` steps (0: none) the envelope maps asked for: peak von Mises stress, peak
+        effective shear strain, min / max of the six stresses. A set of its own next to set_monitors'. Replaces the
+        previous set, which stays in force if this one is refused (RuntimeError)."""
+        elems = np.zeros(0, np.uint32) if gauges is None else np.ascontiguousarray(gauges, np.uint32).reshape(-1)
+        maps = (_lib.ENVELOPE_VON_MISES if von_mises else 0) | (_lib.ENVELOPE_SHEAR_STRAIN if shear_strain else 0) | \
+            (_lib.ENVELOPE_STRESS_RANGE if stress_range else 0)
+        d = _lib.ExplicitElementMonitorDescC(elems.size, _lib.ptr(elems) if elems.size else None,
+                                             int(gauge_every) if elems.size else 0,
+                                             int(gauge_capacity) if elems.size else 0, int(envelope_every), maps, 0)
+        self._check(_lib.load().cwf_hip_explicit_set_element_monitors(self._ex, C.byref(d)))
+
+    def clear_element_monitors(self):
+        self._check(_lib.load().cwf_hip_explicit_set_element_monitors(self._ex, None))
+
+    def reset_element_monitors(self):
+        """The same set: sample counts rewound, the maps back at their start values."""
+        self._check(_lib.load().cwf_hip_explicit_reset_element_monitors(self._ex))
+
+    def element_monitor_info(self) -> ElementMonitorInfo:
+        i = _lib.ExplicitElementMonitorInfoC()
+        self._check(_lib.load().cwf_hip_explicit_element_monitor_info(self._ex, C.byref(i)))
+        m = int(i.envelope_maps)
+        return ElementMonitorInfo(*(int(getattr(i, n)) for n, _ in _lib.ExplicitElementMonitorInfoC._fields_[:7]),
+                                  bool(m & _lib.ENVELOPE_VON_MISES), bool(m & _lib.ENVELOPE_SHEAR_STRAIN),
+                                  bool(m & _lib.ENVELOPE_STRESS_RANGE))
+
+    def gauge_traces(self) -> GaugeTraces:
+        i = self.element_monitor_info()
+        n, g = i.gauge_samples, i.gauge_count
+        steps = np.zeros(n, np.uint64)
+        rows = np.zeros((n, g, 13), np.float32)
+        self._check(_lib.load().cwf_hip_explicit_read_gauges(self._ex, 0, n, _lib.ptr(steps), _lib.ptr(rows)))
+        return GaugeTraces(steps, steps.astype(np.float64) * self.time_step(), rows)
+
+    def envelopes(self) -> Envelopes:
+        """The maps that are set; RuntimeError "envelope map is not set" when there is none."""
+        i = self.element_monitor_info()
+        E = self.element_count
+        if not (i.von_mises or i.shear_strain or i.stress_range):
+            self._check(_lib.load().cwf_hip_explicit_read_envelopes(self._ex, _lib.ptr(np.zeros(max(E, 1), np.float32)),
+                                                                    None, None, None, E, _lib.PTR_HOST))
+        out = Envelopes(np.zeros(E, np.float32) if i.von_mises else None,
+                        np.zeros(E, np.float32) if i.shear_strain else None,
+                        np.zeros((E, 6), np.float32) if i.stress_range else None,
+                        np.zeros((E, 6), np.float32) if i.stress_range else None)
+        self._check(_lib.load().cwf_hip_explicit_read_envelopes(
+            self._ex, _lib.ptr(out.von_mises), _lib.ptr(out.shear_strain), _lib.ptr(out.stress_min),
+            _lib.ptr(out.stress_max), E, _lib.PTR_HOST))
+        return out

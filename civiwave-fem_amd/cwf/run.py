@@ -4,6 +4,7 @@
                                     [--time-varying-loads] [--device K]
                                     [--integrator newmark|explicit] [--safety 0.9]
                                     [--trace-every K] [--peaks] [--energy-every K] [--mass-damping-only]
+                                    [--envelope-every K] [--gauges e0,e1,... [--gauge-every K]]
 
 The reference has no such executable (SURVEY.md section 0.4: its only binary is the viewer demo);
 this wires its pieces in the order the viewer backend does (src/ui/viewer.cpp:200-277):
@@ -24,6 +25,11 @@ with its own arrival delay; such entries, and entries naming different curves, r
 traces at ``output.probes`` every K explicit steps (``probes/traces.csv``), the peak |u|, |v|, |a| maps
 (``monitors/peaks.npy``, [N,3]) and the energy ledger (``monitors/energy.csv``), written after the last frame. The
 ledger needs beta_R == 0, which no scenario's ``damping:`` gives: ``--mass-damping-only`` keeps alpha_R and drops beta_R.
+``--envelope-every K`` and ``--gauges e0,e1,... [--gauge-every K]`` (explicit only) turn on its element monitors: every
+K explicit steps the peak von Mises stress, the peak effective shear strain and the min / max of the six stresses per
+element (``monitors/envelope_von_mises.npy``, ``envelope_shear_strain.npy`` [E]; ``envelope_stress_min.npy``,
+``envelope_stress_max.npy`` [E,6]), and the strain / stress / von Mises rows of the gauge elements
+(``monitors/gauges.csv``, one line per sample and gauge).
 
 Mesh paths are resolved like the reference (relative to the working directory) and, failing that,
 relative to the YAML file's directory. One JSON line per step is printed; the last line is a summary.
@@ -114,11 +120,14 @@ def run_scenario(cfg_path: str, steps: int, out_dir: str | None, mode: int = _li
 
 def run_scenario_explicit(cfg_path: str, steps: int, out_dir: str | None, mode: int = _lib.MODE_PARITY,
                           device: int = 0, safety: float = 0.9, log=print, trace_every: int = 0, peaks: bool = False,
-                          energy_every: int = 0, mass_damping_only: bool = False) -> dict:
+                          energy_every: int = 0, mass_damping_only: bool = False, envelope_every: int = 0,
+                          gauges=(), gauge_every: int = 1) -> dict:
     """`steps` output frames of the explicit stepper, ceil(cfg.time.initial_dt / dt) explicit steps each.
     trace_every / peaks / energy_every: the stepper's monitors (receivers at cfg.output.probes), written under
     out_dir after the last frame; their capacities follow from `steps`. mass_damping_only: the stepper gets the
-    scenario's alpha_R and beta_R = 0 (a scenario's damping always has beta_R > 0, which the energy ledger refuses)."""
+    scenario's alpha_R and beta_R = 0 (a scenario's damping always has beta_R > 0, which the energy ledger refuses).
+    envelope_every / gauges, gauge_every: the stepper's element monitors (all three envelope maps; gauge elements in
+    the mesh's numbering), written under out_dir after the last frame."""
     import math
 
     from .explicit import ExplicitStepper
@@ -151,6 +160,16 @@ def run_scenario_explicit(cfg_path: str, steps: int, out_dir: str | None, mode: 
                                 energy_capacity=max(total // max(energy_every, 1), 1))
             except RuntimeError as e:
                 raise ScenarioError(str(e)) from None
+        element_monitored = envelope_every > 0 or len(gauges) > 0
+        if element_monitored:
+            every = max(gauge_every, 1)
+            try:
+                st.set_element_monitors(gauges=list(gauges) or None, gauge_every=every,
+                                        gauge_capacity=max(steps * per_frame // every, 1),
+                                        envelope_every=max(envelope_every, 0), von_mises=envelope_every > 0,
+                                        shear_strain=envelope_every > 0, stress_range=envelope_every > 0)
+            except RuntimeError as e:
+                raise ScenarioError(str(e)) from None
         for frame in range(steps):
             r = st.advance(per_frame)
             if not r.has_value():
@@ -164,6 +183,8 @@ def run_scenario_explicit(cfg_path: str, steps: int, out_dir: str | None, mode: 
             log(json.dumps(last))
         written = write_monitors(st, out_dir, cfg.output.probes, trace_every > 0, peaks, energy_every > 0) \
             if monitored and out_dir else {}
+        if element_monitored:
+            written.update(write_element_monitors(st, out_dir, gauges, envelope_every > 0))
         wall = time.perf_counter() - wall0
         return dict(scenario=cfg_path, nodes=P.node_count, tets=P.element_count, dofs=P.dof_count, steps=steps,
                     integrator="explicit", explicit_steps=tel.steps, steps_per_frame=per_frame, dt=tel.dt,
@@ -206,6 +227,38 @@ def write_monitors(st, out_dir, probes, traces: bool, peaks: bool, energy: bool)
             for row in zip(e.steps, e.time, e.kinetic, e.potential, e.work, e.dissipated, e.balance()):
                 f.write(f"{int(row[0])}," + ",".join(repr(float(x)) for x in row[1:]) + "\n")
         out["energy_samples"] = int(e.steps.size)
+    return out
+
+
+def write_element_monitors(st, out_dir, gauges, envelopes: bool) -> dict:
+    """The stepper's element monitors as files under out_dir/monitors (out_dir None: no files): the four envelope_*.npy
+    maps and gauges.csv (one row per sample and gauge) -> the summary's entries."""
+    import os
+
+    import numpy as np
+
+    info = st.element_monitor_info()
+    out = {}
+    if out_dir:
+        os.makedirs(os.path.join(out_dir, "monitors"), exist_ok=True)
+    if envelopes:
+        out["envelope_samples"] = info.envelope_samples
+        if out_dir:
+            env = st.envelopes()
+            for name in ("von_mises", "shear_strain", "stress_min", "stress_max"):
+                np.save(os.path.join(out_dir, "monitors", f"envelope_{name}.npy"), getattr(env, name))
+    if len(gauges):
+        out["gauge_samples"] = info.gauge_samples
+        if out_dir:
+            tr = st.gauge_traces()
+            comps = ("xx", "yy", "zz", "xy", "yz", "xz")
+            with open(os.path.join(out_dir, "monitors", "gauges.csv"), "w") as f:
+                f.write("step,time,element," + ",".join(f"strain_{c}" for c in comps) + "," +
+                        ",".join(f"stress_{c}" for c in comps) + ",von_mises\n")
+                for i in range(tr.steps.size):
+                    for g, elem in enumerate(gauges):
+                        vals = ",".join(repr(float(x)) for x in tr.rows[i, g])
+                        f.write(f"{int(tr.steps[i])},{float(tr.time[i])!r},{int(elem)},{vals}\n")
     return out
 
 
@@ -300,7 +353,18 @@ def main(argv=None) -> int:
                          "--mass-damping-only)")
     ap.add_argument("--mass-damping-only", action="store_true",
                     help="explicit: keep the scenario's alpha_R and drop its stiffness-proportional beta_R")
+    ap.add_argument("--envelope-every", type=int, default=0, metavar="K",
+                    help="explicit: peak von Mises, peak effective shear strain and stress min / max per element, "
+                         "raised every K steps -> <out>/monitors/envelope_*.npy")
+    ap.add_argument("--gauges", default="", metavar="E0,E1,...",
+                    help="explicit: strain / stress / von Mises rows of these elements -> <out>/monitors/gauges.csv")
+    ap.add_argument("--gauge-every", type=int, default=1, metavar="K", help="explicit: a gauge row every K steps")
     a = ap.parse_args(argv)
+    try:
+        gauges = [int(x) for x in a.gauges.split(",") if x.strip()]
+    except ValueError:
+        print("error: --gauges takes element numbers separated by commas", file=sys.stderr)
+        return 1
     try:
         if a.integrator == "explicit":
             if a.time_varying_loads or a.paused:
@@ -308,12 +372,15 @@ def main(argv=None) -> int:
             s = run_scenario_explicit(a.scenario, a.steps, a.out,
                                       _lib.MODE_FAST if a.mode == "fast" else _lib.MODE_PARITY, a.device, a.safety,
                                       trace_every=a.trace_every, peaks=a.peaks, energy_every=a.energy_every,
-                                      mass_damping_only=a.mass_damping_only)
+                                      mass_damping_only=a.mass_damping_only, envelope_every=a.envelope_every,
+                                      gauges=gauges, gauge_every=a.gauge_every)
             print(json.dumps(dict(summary=s)))
             return 0
         if a.trace_every or a.peaks or a.energy_every or a.mass_damping_only:
             raise ScenarioError("--trace-every, --peaks, --energy-every and --mass-damping-only belong to the explicit "
                                 "integrator")
+        if a.envelope_every or gauges or a.gauge_every != 1:
+            raise ScenarioError("--envelope-every, --gauges and --gauge-every belong to the explicit integrator")
         s = run_scenario(a.scenario, a.steps, a.out, _lib.MODE_FAST if a.mode == "fast" else _lib.MODE_PARITY,
                          a.device, a.paused, a.time_varying_loads)
     except ScenarioError as e:

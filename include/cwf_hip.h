@@ -596,6 +596,66 @@ int cwf_hip_explicit_read_peaks(cwf_hip_explicit *ex, float *peak_u, float *peak
                                 int ptr_kind);
 /* Ledger rows into host memory: steps [count], rows [count][4] = {kinetic, potential, work_cum, dissipated_cum}. */
 int cwf_hip_explicit_read_energy(cwf_hip_explicit *ex, uint64_t first, uint64_t count, uint64_t *steps, double *rows);
+/* Element monitors: stresses and strains recorded on the device while advance() queues its steps, a set of its own next
+ * to the node monitors above (neither touches the other). Both parts sample by the receivers' rule: after the update
+ * that makes the step count n, when n % every == 0, u_n is sampled; the row and "this step is due" are launch
+ * arguments, there are no device counters. A stepper without element monitors launches exactly the kernels it launches
+ * without this section and allocates nothing for it.
+ *   Gauges: one thread per gauge element writes the 13 floats {strain[6], stress[6], von_mises} of the element, bit for
+ *     bit the row cwf_hip_derived_fields returns for the same u, to row `held` of a buffer [capacity][gauges][13] in the
+ *     caller's gauge order. A full buffer drops the sample and counts it.
+ *   Envelopes: one pass over all E elements per due step. With x the value the derived-fields element pass would store
+ *     (f32) a stored value is replaced only where x > peak (maxima) or x < low (minima), so a NaN never enters:
+ *       CWF_ENVELOPE_VON_MISES     peak von Mises stress, from +0.0
+ *       CWF_ENVELOPE_SHEAR_STRAIN  peak effective shear strain, from +0.0: with the element's fp64 strain e[0..5], in
+ *                                  fp64 without fused multiply-adds and with the IEEE square root,
+ *                                    d0 = e0 - e1; d1 = e1 - e2; d2 = e2 - e0;
+ *                                    sd = d0 d0 + d1 d1 + d2 d2; sg = e3 e3 + e4 e4 + e5 e5;
+ *                                    g = sqrt(sd (2.0 / 3.0) + sg), stored as f32
+ *                                  (2 sqrt(J2) of the strain deviator with engineering shears: |gamma| in pure shear)
+ *       CWF_ENVELOPE_STRESS_RANGE  min (from +inf) and max (from -inf) of each of the six stresses
+ *     On the device every map is a plane of one f32 per element, the stress range twelve of them (component-major), so
+ *     that a wavefront's loads and stores are consecutive words; the caller sees [E] and [E][6]. */
+#define CWF_ENVELOPE_VON_MISES 1u
+#define CWF_ENVELOPE_SHEAR_STRAIN 2u
+#define CWF_ENVELOPE_STRESS_RANGE 4u
+typedef struct cwf_explicit_element_monitor_desc
+{
+    uint64_t gauge_count;
+    const uint32_t *gauge_elements; /* [gauge_count] distinct elements, the caller's numbering */
+    uint64_t gauge_every;           /* >= 1 when gauge_count > 0 */
+    uint64_t gauge_capacity;        /* samples (rows) */
+    uint64_t envelope_every;        /* 0: no envelopes */
+    uint32_t envelope_maps;         /* CWF_ENVELOPE_* bits; non-zero exactly when envelope_every is */
+    uint32_t reserved;
+} cwf_explicit_element_monitor_desc;
+
+typedef struct cwf_explicit_element_monitor_info
+{
+    uint64_t gauge_count, gauge_every, gauge_capacity, gauge_samples, gauge_dropped;
+    uint64_t envelope_every, envelope_samples; /* envelope_samples: element passes since set or reset */
+    uint32_t envelope_maps, reserved;
+} cwf_explicit_element_monitor_info;
+
+/* Replaces the previous set; desc NULL or all zero removes it and frees its buffers. u, v, the step count, loads,
+ * dashpots, sources and the node monitors are kept; the maps start at their start values and the sample counts at
+ * zero. All buffers are allocated here, in the stepper's arena. Everything refusable is checked before anything
+ * changes, and a refusal leaves the previous set in force: CWF_ERR_ARGUMENT "gauge element out of range" {index=<i>,
+ * element=<id>}, "gauge element listed twice" {index=<i>, element=<id>}, "gauge_every must be at least 1", "monitor
+ * capacity must not be zero", "unknown envelope map" {maps=<bits>}, "envelope_maps without envelope_every",
+ * "envelope_every without envelope_maps", "null pointer"; CWF_ERR_ALLOC. */
+int cwf_hip_explicit_set_element_monitors(cwf_hip_explicit *ex, const cwf_explicit_element_monitor_desc *desc);
+/* The same set: sample counts rewound, the maps back at their start values. */
+int cwf_hip_explicit_reset_element_monitors(cwf_hip_explicit *ex);
+int cwf_hip_explicit_element_monitor_info(cwf_hip_explicit *ex, cwf_explicit_element_monitor_info *info);
+/* Rows first .. first + count - 1 of the gauge buffer into host memory: steps [count], rows [count][gauges][13], each
+ * nullable. CWF_ERR_ARGUMENT "monitor rows out of range" {first=<first>, count=<count>, held=<rows held>}. */
+int cwf_hip_explicit_read_gauges(cwf_hip_explicit *ex, uint64_t first, uint64_t count, uint64_t *steps, float *rows);
+/* The envelope maps in the caller's element order: von_mises and shear_strain [E], stress_min and stress_max [E][6],
+ * each nullable; n = E. CWF_ERR_ARGUMENT "envelope map is not set" for a map asked for that the set does not hold;
+ * CWF_ERR_SIZE "envelope map span size mismatch" {span=<n>, elements=<E>}. */
+int cwf_hip_explicit_read_envelopes(cwf_hip_explicit *ex, float *von_mises, float *shear_strain, float *stress_min,
+                                    float *stress_max, uint64_t n, int ptr_kind);
 /* Load sources of the scheme above. */
 #define CWF_EXPLICIT_MAX_SOURCES 8
 typedef struct cwf_explicit_source_desc

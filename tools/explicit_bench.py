@@ -5,6 +5,7 @@
     python tools/explicit_bench.py --absorbing [--configs c3] [--steps 2000]
     python tools/explicit_bench.py --monitors [--configs c2 c3] [--steps 2000]
     python tools/explicit_bench.py --sources [--configs c2 c3] [--steps 2000]
+    python tools/explicit_bench.py --envelopes [--configs c2 c3 c2:hex8] [--steps 2000]
 
 Per config (a FAST handle of the block, created with scalars (1, 0)), in one process and one JSON line each, appended
 to --out (default profiles/explicit_c2.json):
@@ -34,6 +35,14 @@ wave as a source on the base, with an oblique plane-wave source on the five face
 zero delay (a three-component record), and after the set is removed; next to the loaded nodes, the entries and the bytes
 the source kernel moves by its layout (per loaded node 4 B node + 8 B offsets + 12 B f_ext + 12 B stored, per entry a
 32-B record + 8 B curve directory; the curve's knots are shared and stay in L2).
+
+--envelopes: the cost of the element monitors (include/cwf_hip.h "Element monitors"). Per config one line, appended to
+profiles/explicit_envelopes.json, one stepper on one FAST handle: step_us without element monitors, with each envelope
+map alone and with all three at envelope_every 1, 10 and 100, with 64 gauges at every 1 and 10, and after
+clear_element_monitors again; next to them the time of one element pass (the every-1 step minus the plain step) and
+the estimate from bytes at the 6.25 TB/s copy ceiling: per element its record (tet4: 64 B + 4 B material; hex8: 32 B
+of corner ids + 96 B of gradients + 4 B), the u gathers counted once per node (12 B x nodes / elements: the rest are
+cache hits), and the maps read once and written at most once (4 to 56 B each way).
 """
 import argparse
 import ctypes as C
@@ -272,6 +281,47 @@ def measure_sources(key, steps, device):
     return out
 
 
+def measure_envelopes(key, steps, device):
+    import numpy as np
+
+    name, _, element = key.partition(":")
+    case = scenarios.config_case(name, element=element or "tet4")
+    P = case.packing
+    N, E = P.node_count, P.element_count
+    hex8 = (element or "tet4") == "hex8"
+    sysm = pcg.MatrixFreeSystem.from_packing(P, case.materials, 1.0, 0.0, mode=_lib.MODE_FAST, device=device)
+    out = dict(config=key, name=case.name, nodes=N, elements=E, steps=steps,
+               kernel=(_lib.load().cwf_hip_system_keff_kernel(sysm.handle()) or b"").decode())
+    ex = ExplicitStepper(P, case.materials, RayleighCoefficients(0.0, 0.0), system=sysm)
+    out["dt"] = ex.telemetry().dt
+    gauges = np.random.Generator(np.random.PCG64(5)).permutation(E)[:64]
+    total = 200 + steps  # timed_steps warms up with 200 steps
+    maps = dict(von_mises=dict(von_mises=True), shear_strain=dict(shear_strain=True),
+                stress_range=dict(stress_range=True),
+                all=dict(von_mises=True, shear_strain=True, stress_range=True))
+    out["step_us_plain"] = timed_steps(ex, steps)
+    for label, kw in maps.items():
+        for every in (1, 10, 100):
+            ex.set_element_monitors(envelope_every=every, **kw)
+            out[f"step_us_{label}_every_{every}"] = timed_steps(ex, steps)
+    for every in (1, 10):
+        ex.set_element_monitors(gauges=gauges, gauge_every=every, gauge_capacity=total // every + 1)
+        out[f"step_us_gauges64_every_{every}"] = timed_steps(ex, steps)
+    ex.clear_element_monitors()
+    out["step_us_cleared"] = timed_steps(ex, steps)
+    record = (32 + 96 + 4) if hex8 else (64 + 4)
+    map_bytes = dict(von_mises=4, shear_strain=4, stress_range=48, all=56)
+    ceiling = 6.25e12
+    for label, b in map_bytes.items():
+        lo, hi = E * (record + b) + 12 * N, E * (record + 2 * b) + 12 * N  # nothing stored .. every value stored
+        out[f"pass_{label}"] = dict(measured_us=out[f"step_us_{label}_every_1"] - out["step_us_plain"],
+                                    bytes_low=lo, bytes_high=hi, estimate_us_low=1e6 * lo / ceiling,
+                                    estimate_us_high=1e6 * hi / ceiling)
+    ex.close()
+    sysm.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", nargs="+", default=["c2", "c3", "c2:hex8"])
@@ -281,19 +331,23 @@ def main():
     ap.add_argument("--absorbing", action="store_true", help="the cost of dashpots on five faces (see above)")
     ap.add_argument("--monitors", action="store_true", help="the cost of the monitors (see above)")
     ap.add_argument("--sources", action="store_true", help="the cost of load sources (see above)")
-    ap.add_argument("--out", default=None, help="default profiles/explicit_c2.json (--absorbing: "
+    ap.add_argument("--envelopes", action="store_true", help="the cost of the element monitors (see above)")
+    ap.add_argument("--out", default=None, help="default profiles/explicit_c2.json (--envelopes: "
+                                                 "profiles/explicit_envelopes.json, --absorbing: "
                                                  "profiles/explicit_absorbing.json, --monitors: "
                                                  "profiles/explicit_monitors.json, --sources: "
                                                  "profiles/explicit_sources.json)")
     a = ap.parse_args()
-    a.out = a.out or os.path.join(ROOT, "profiles", "explicit_sources.json" if a.sources else
+    a.out = a.out or os.path.join(ROOT, "profiles", "explicit_envelopes.json" if a.envelopes else
+                                  "explicit_sources.json" if a.sources else
                                   "explicit_monitors.json" if a.monitors else
                                   "explicit_absorbing.json" if a.absorbing else "explicit_c2.json")
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    if a.configs == ap.get_default("configs"):
+    if a.configs == ap.get_default("configs") and not a.envelopes:
         a.configs = ["c2", "c3"] if a.monitors or a.sources else ["c3"] if a.absorbing else a.configs
     for key in a.configs:
-        line = json.dumps(measure_sources(key, a.steps, a.device) if a.sources else
+        line = json.dumps(measure_envelopes(key, a.steps, a.device) if a.envelopes else
+                          measure_sources(key, a.steps, a.device) if a.sources else
                           measure_monitors(key, a.steps, a.device) if a.monitors else
                           measure_absorbing(key, a.steps, a.device) if a.absorbing else
                           measure(key, a.steps, a.newmark_steps, a.device))
