@@ -8,6 +8,7 @@
 #include <cstring>
 
 #include "abi_internal.hpp"
+#include "plasticity.hpp"
 
 using namespace cwf;
 
@@ -86,6 +87,22 @@ struct cwf_hip_explicit : TransientState
             *this = ElementMonitors();
         }
     } emon;
+    // set_plasticity: the set in force (dev.slots == 0: none), its device arrays (the stepper's arena), the slots'
+    // elements on the host (read_plasticity scatters through them) and the values as given
+    struct Plasticity
+    {
+        ExplicitPlasticity dev{};
+        std::vector<uint32_t> elem;
+        uint64_t bytes = 0;
+        void release(DeviceArena &mem)
+        {
+            for (const void *p : {(const void *)dev.elem, (const void *)dev.yield_hard, (const void *)dev.state,
+                                  (const void *)dev.corner, (const void *)dev.anode, (const void *)dev.aoff,
+                                  (const void *)dev.cpos, (const void *)dev.p})
+                mem.free(const_cast<void *>(p));
+            *this = Plasticity();
+        }
+    } pl;
 };
 
 namespace
@@ -329,6 +346,8 @@ int cwf_hip_explicit_advance(cwf_hip_explicit *t, uint64_t n_steps, cwf_explicit
     a.ecur = mon.ecur;
     a.dC = dash ? t->dC : nullptr;
     a.alpha = t->alpha;
+    const ExplicitPlasticity &pl = t->pl.dev;
+    a.p = pl.slots ? pl.p : nullptr;
     const uint32_t blocks = explicit_update_blocks(s.N);
     cwf_hip_explicit::ElementMonitors &em = t->emon;
     ExplicitElementPass ep{};
@@ -342,6 +361,8 @@ int cwf_hip_explicit_advance(cwf_hip_explicit *t, uint64_t n_steps, cwf_explicit
     {
         if (pattern)
             a.scale = t->last_scale = curve_at(t, (double)t->steps * t->dt);
+        if (pl.slots)  // the return map at u_n and the affected nodes' correction force, before the operator launch
+            explicit_plasticity(s, t->u, pl, st);
         if (fast)
             fast_keff_partials_ds(s, t->w, true, st);
         else
@@ -410,7 +431,11 @@ int cwf_hip_explicit_get_state(cwf_hip_explicit *t, int which, float *out, uint6
 {
     if (!t || !out)
         return set_error(nullptr, CWF_ERR_ARGUMENT, "null pointer");
-    const float *src = which == 0 ? t->u : which == 1 ? t->v : which == 4 ? t->f : nullptr;
+    const float *src = which == 0   ? t->u
+                       : which == 1 ? t->v
+                       : which == 4 ? t->f
+                       : which == 5 ? (t->pl.dev.slots ? t->pl.dev.p : nullptr)
+                                    : nullptr;
     // the update pass formed f_n in registers: the same rounding, on request
     const bool reform = which == 4 && t->lbase && !t->ctimes.empty() && t->steps;
     return transient_get(*t, src, out, n, kind, reform ? &t->last_scale : nullptr);
@@ -803,6 +828,9 @@ int cwf_hip_explicit_set_monitors(cwf_hip_explicit *t, const cwf_explicit_monito
     if (d.energy_every && t->beta != 0.0)
         return set_error(h, CWF_ERR_UNSUPPORTED, "the energy ledger needs rayleigh_beta == 0",
                          "rayleigh_beta=" + num(t->beta));
+    if (d.energy_every && t->pl.dev.slots)
+        return set_error(h, CWF_ERR_UNSUPPORTED, "the energy ledger and plasticity exclude each other",
+                         "plastic_elements=" + std::to_string(t->pl.dev.slots));
     const uint32_t kNone = 0xFFFFFFFFu;
     std::vector<uint32_t> slot(d.receiver_count ? std::max<uint64_t>(N, 4) : 0, kNone);
     for (uint64_t i = 0; i < d.receiver_count; ++i)
@@ -1244,6 +1272,244 @@ int cwf_hip_explicit_read_envelopes(cwf_hip_explicit *t, float *von_mises, float
                 out[q][6 * e + c] = plane[c * m.stride + e];
     }
     HIPTRY(h, hipStreamSynchronize(s));
+    return 0;
+}
+
+int cwf_explicit_j2_update(const double D[36], double yield, double hardening, double volume, const double strain[6],
+                           double state[8], double sigma_p[6])
+{
+    if (!D || !strain || !state || !sigma_p)
+        return 0;
+    return j2_update(D, yield, hardening, volume, strain, state, state[6], state[7], sigma_p) ? 1 : 0;
+}
+
+int cwf_hip_explicit_set_plasticity(cwf_hip_explicit *t, const cwf_explicit_plasticity_desc *desc)
+{
+    if (!t)
+        return set_error(nullptr, CWF_ERR_ARGUMENT, "null handle");
+    cwf_hip_system *h = t->sys;
+    if (int st = check_ready(h))
+        return st;
+    hipStream_t s = h->stream;
+    if (!desc)
+    {
+        HIPTRY(h, hipStreamSynchronize(s));
+        t->pl.release(t->mem);
+        return 0;
+    }
+    // everything that can be refused, on the host, before anything changes
+    const DevSys &ds = h->ds;
+    const uint64_t N = ds.N, E = ds.E, M = ds.M;
+    if (ds.hex)
+        return set_error(h, CWF_ERR_UNSUPPORTED, "plasticity needs tet4 elements", "element=hex8");
+    if (desc->material_count != M)
+        return set_error(h, CWF_ERR_ARGUMENT, "plasticity material count mismatch",
+                         "material_count=" + std::to_string(desc->material_count) +
+                             "\nmaterials=" + std::to_string(M));
+    if (!desc->yield_stress || !desc->hardening)
+        return set_error(h, CWF_ERR_ARGUMENT, "null pointer");
+    std::vector<uint8_t> plastic(M, 0);
+    std::vector<double> yh(2 * M);
+    bool any = false;
+    for (uint64_t m = 0; m < M; ++m)
+    {
+        const double sy = desc->yield_stress[m], H = desc->hardening[m];
+        if (!(sy >= 0.0) || !(H >= 0.0))
+            return set_error(h, CWF_ERR_ARGUMENT, "yield stress and hardening must be non-negative",
+                             "material=" + std::to_string(m) + "\nyield_stress=" + num(sy) + "\nhardening=" + num(H));
+        plastic[m] = sy > 0.0 && std::isfinite(sy);
+        any = any || plastic[m];
+        yh[2 * m] = sy;
+        yh[2 * m + 1] = H;
+    }
+    if (t->mon.ecum)
+        return set_error(h, CWF_ERR_UNSUPPORTED, "the energy ledger and plasticity exclude each other",
+                         "energy_every=" + std::to_string(t->mon.eevery));
+    HIPTRY(h, hipStreamSynchronize(s));
+    std::vector<double> D(36 * M);
+    HIPTRY(h, hipMemcpy(D.data(), ds.dmat, D.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (uint64_t m = 0; m < M; ++m)
+        if (plastic[m] && !iso_pattern(D.data() + 36 * m))
+            return set_error(h, CWF_ERR_UNSUPPORTED, "a plastic material needs an isotropic stiffness",
+                             "material=" + std::to_string(m));
+    if (!any)  // every material elastic: nothing to run
+    {
+        t->pl.release(t->mem);
+        return 0;
+    }
+    // the slots (plastic elements, ascending) and the affected nodes' compact CSR, from the handle's own arrays: the
+    // node -> incidence CSR is in the handle's node order and ascends in element per node
+    std::vector<uint32_t> mat(E), off(N + 1), inc(4 * E);
+    HIPTRY(h, hipMemcpy(mat.data(), ds.mat, E * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIPTRY(h, hipMemcpy(off.data(), ds.off, (N + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIPTRY(h, hipMemcpy(inc.data(), ds.inc, 4 * E * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    const uint32_t kNone = 0xFFFFFFFFu;
+    std::vector<uint32_t> slot_of(E, kNone), elem;
+    for (uint64_t e = 0; e < E; ++e)
+        if (mat[e] < M && plastic[mat[e]])
+        {
+            slot_of[e] = (uint32_t)elem.size();
+            elem.push_back((uint32_t)e);
+        }
+    if (elem.empty())
+    {
+        t->pl.release(t->mem);
+        return 0;
+    }
+    // node-major corner forces: position q of the array is the q-th plastic incidence in node order, so a node's run
+    // ascends in element; cpos tells each slot where its four corners go
+    std::vector<uint32_t> anode, aoff(1, 0), cpos(4 * elem.size(), 0);
+    uint32_t run = 0;
+    for (uint64_t n = 0; n < N; ++n)
+    {
+        for (uint32_t j = off[n]; j < off[n + 1]; ++j)
+        {
+            const uint32_t e = inc[j] >> 2;
+            if (e < E && slot_of[e] != kNone)
+                cpos[4ull * slot_of[e] + (inc[j] & 3u)] = run++;
+        }
+        if (run != aoff.back())
+        {
+            anode.push_back((uint32_t)n);
+            aoff.push_back(run);
+        }
+    }
+    if (run != cpos.size())  // every corner of every plastic element is some node's incidence, once
+        return set_error(h, CWF_ERR_INDEX, "plastic incidences do not cover the elements' corners",
+                         "incidences=" + std::to_string(run) + "\ncorners=" + std::to_string(cpos.size()));
+    // the new set's buffers; the stepper's once everything went well
+    const size_t slots = elem.size(), plen = std::max<size_t>(3 * N, 4);
+    cwf_hip_explicit::Plasticity m;
+    uint32_t *delem = nullptr, *danode = nullptr, *daoff = nullptr, *dcpos = nullptr;
+    double *dyh = nullptr, *dstate = nullptr;
+    float *dcorner = nullptr, *dp = nullptr;
+    int st = t->alloc(&delem, slots);
+    st = st ? st : t->alloc(&dyh, yh.size());
+    st = st ? st : t->alloc(&dstate, 8 * slots);
+    st = st ? st : t->alloc(&dcorner, 12 * slots);
+    st = st ? st : t->alloc(&danode, anode.size());
+    st = st ? st : t->alloc(&daoff, aoff.size());
+    st = st ? st : t->alloc(&dcpos, cpos.size());
+    st = st ? st : t->alloc(&dp, plen);
+    m.dev = ExplicitPlasticity{(uint32_t)slots, (uint32_t)anode.size(), delem, dyh, dstate, dcorner, danode, daoff,
+                               dcpos, dp};
+    hipError_t e = hipSuccess;
+    const auto up = [&](void *dst, const void *from, size_t bytes) {
+        if (!st && e == hipSuccess)
+            e = hipMemcpyAsync(dst, from, bytes, hipMemcpyHostToDevice, s);
+    };
+    const auto zero = [&](void *dst, size_t bytes) {
+        if (!st && e == hipSuccess)
+            e = hipMemsetAsync(dst, 0, bytes, s);
+    };
+    up(delem, elem.data(), slots * sizeof(uint32_t));
+    up(dyh, yh.data(), yh.size() * sizeof(double));
+    up(danode, anode.data(), anode.size() * sizeof(uint32_t));
+    up(daoff, aoff.data(), aoff.size() * sizeof(uint32_t));
+    up(dcpos, cpos.data(), cpos.size() * sizeof(uint32_t));
+    zero(dstate, 8 * slots * sizeof(double));
+    zero(dcorner, 12 * slots * sizeof(float));
+    zero(dp, plen * sizeof(float));
+    if (!st && e == hipSuccess)
+        e = hipStreamSynchronize(s);
+    if (st || e != hipSuccess)
+    {
+        (void)hipStreamSynchronize(s);
+        m.release(t->mem);
+        return st ? st : hip_fail(h, e, "explicit set_plasticity");
+    }
+    m.bytes = (slots + anode.size() + aoff.size() + cpos.size()) * sizeof(uint32_t) +
+              (yh.size() + 8 * slots) * sizeof(double) + (12 * slots + plen) * sizeof(float);
+    m.elem = std::move(elem);
+    t->pl.release(t->mem);
+    t->pl = std::move(m);
+    return 0;
+}
+
+int cwf_hip_explicit_reset_plasticity(cwf_hip_explicit *t)
+{
+    if (!t)
+        return set_error(nullptr, CWF_ERR_ARGUMENT, "null handle");
+    cwf_hip_system *h = t->sys;
+    if (int st = check_ready(h))
+        return st;
+    const ExplicitPlasticity &p = t->pl.dev;
+    if (!p.slots)
+        return 0;
+    HIPTRY(h, hipMemsetAsync(p.state, 0, 8ull * p.slots * sizeof(double), h->stream));
+    HIPTRY(h, hipMemsetAsync(p.corner, 0, 12ull * p.slots * sizeof(float), h->stream));
+    HIPTRY(h, hipMemsetAsync(p.p, 0, std::max<size_t>(3ull * h->ds.N, 4) * sizeof(float), h->stream));
+    HIPTRY(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+namespace
+{
+// the slots' 64-B records on the host
+int plastic_state(cwf_hip_explicit *t, std::vector<double> &state)
+{
+    cwf_hip_system *h = t->sys;
+    state.resize(8ull * t->pl.dev.slots);
+    if (state.empty())
+        return 0;
+    HIPTRY(h, hipMemcpyAsync(state.data(), t->pl.dev.state, state.size() * sizeof(double), hipMemcpyDeviceToHost,
+                             h->stream));
+    HIPTRY(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+}  // namespace
+
+int cwf_hip_explicit_plasticity_info(cwf_hip_explicit *t, cwf_explicit_plasticity_info *info)
+{
+    if (!t || !info)
+        return set_error(nullptr, CWF_ERR_ARGUMENT, "null pointer");
+    if (int st = check_ready(t->sys))
+        return st;
+    std::vector<double> state;
+    if (int st = plastic_state(t, state))
+        return st;
+    cwf_explicit_plasticity_info I{};
+    I.plastic_elements = t->pl.dev.slots;
+    I.affected_nodes = t->pl.dev.affected;
+    for (size_t q = 0; q < t->pl.dev.slots; ++q)
+        I.yielded_elements += state[8 * q + 6] > 0.0 ? 1 : 0;
+    I.bytes = t->pl.bytes;
+    *info = I;
+    return 0;
+}
+
+int cwf_hip_explicit_read_plasticity(cwf_hip_explicit *t, double *ep, double *abar, double *wp, uint64_t n)
+{
+    if (!t)
+        return set_error(nullptr, CWF_ERR_ARGUMENT, "null handle");
+    cwf_hip_system *h = t->sys;
+    if (int st = check_ready(h))
+        return st;
+    if (!t->pl.dev.slots)
+        return set_error(h, CWF_ERR_ARGUMENT, "no plasticity is set");
+    const uint64_t E = h->ds.E;
+    if (n != E)
+        return set_error(h, CWF_ERR_SIZE, "plasticity span size mismatch",
+                         "span=" + std::to_string(n) + "\nelements=" + std::to_string(E));
+    std::vector<double> state;
+    if (int st = plastic_state(t, state))
+        return st;
+    if (ep)
+        std::fill(ep, ep + 6 * E, 0.0);
+    if (abar)
+        std::fill(abar, abar + E, 0.0);
+    if (wp)
+        std::fill(wp, wp + E, 0.0);
+    for (size_t q = 0; q < t->pl.elem.size(); ++q)
+    {
+        const uint32_t e = t->pl.elem[q];
+        if (ep)
+            std::copy(&state[8 * q], &state[8 * q] + 6, ep + 6ull * e);
+        if (abar)
+            abar[e] = state[8 * q + 6];
+        if (wp)
+            wp[e] = state[8 * q + 7];
+    }
     return 0;
 }
 

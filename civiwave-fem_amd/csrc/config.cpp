@@ -199,7 +199,21 @@ std::string parse_config(const yl::Node &root)
             throw CfgError{"material names must be unique", {"materials", idx(i), "name"}};
         names.insert(name);
         j << (i ? ", " : "") << "{\"name\": " << jstr(name) << ", \"E\": " << jnum(E) << ", \"nu\": " << jnum(nu)
-          << ", \"rho\": " << jnum(rho) << "}";
+          << ", \"rho\": " << jnum(rho);
+        // J2 plasticity of the explicit integrator (optional; the keys are emitted only when the entry has them)
+        for (const char *key : {"yield_stress", "hardening_modulus"})
+        {
+            if (!m[key].defined())
+                continue;
+            const double v = guard({"materials", idx(i), key}, [&] { return m[key].as_double(); });
+            if (!(v >= 0.0))
+                throw CfgError{std::string("material.") + key + " must be >= 0", {"materials", idx(i), key}};
+            j << ", \"" << key << "\": " << jnum(v);
+        }
+        if (m["hardening_modulus"].defined() && !m["yield_stress"].defined())
+            throw CfgError{"material.hardening_modulus needs material.yield_stress",
+                           {"materials", idx(i), "hardening_modulus"}};
+        j << "}";
     }
     j << "]";
     // assignments

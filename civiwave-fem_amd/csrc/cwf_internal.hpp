@@ -668,6 +668,23 @@ struct ExplicitElementPass
     float *gauge_row;
 };
 void explicit_element_monitors(const DevSys &s, const float *u, const ExplicitElementPass &a, hipStream_t st);
+// post.hip: the explicit stepper's plasticity (cwf_hip_explicit_set_plasticity), all arrays in the stepper's arena. A
+// slot is a plastic element (ascending element index); an affected node has at least one plastic incident element.
+struct ExplicitPlasticity
+{
+    uint32_t slots, affected;   // 0 slots: no plasticity
+    const uint32_t *elem;       // [slots] the slot's element
+    const double *yield_hard;   // [M] 16-B records {sy, H} by material
+    double *state;              // [slots] 64-B records ep[6] abar wp
+    float *corner;              // [4 slots][3] the corner forces, node-major: affected node i's plastic incidences are
+                                // the run [aoff[i], aoff[i + 1]), ascending element; +0.0 until the element yields
+    const uint32_t *anode;      // [affected] the internal node, ascending
+    const uint32_t *aoff;       // [affected + 1] the node's run in corner
+    const uint32_t *cpos;       // [slots] 16-B records: the position in corner of each of the slot's four corners
+    float *p;                   // [3N] the correction force (zero at the other nodes)
+};
+// one step's element pass and node pass on u = u_n (the handle's node order): p of the affected nodes is rewritten
+void explicit_plasticity(const DevSys &s, const float *u, const ExplicitPlasticity &a, hipStream_t st);
 bool fast_direct_fold(const cwf_hip_system *h);  // unsharded: consumers fold per-workgroup shares
 void fast_fold_pap(cwf_hip_system *h, hipStream_t st);  // local p.Ap shares -> g_pap[rank]
 void fast_fold_rrz(cwf_hip_system *h, unsigned it, hipStream_t st);  // local r.r / r.z shares -> g_rrz[2 rank]
@@ -785,6 +802,8 @@ struct ExplicitPass
     const double *dC;          // the ledger's dashpot matrices as given, 9 f64 per slot (NULL: no dashpots)
     double alpha;              // alpha_R, read by the ledger only
     uint32_t esample;          // this step is sampled: ecur is written
+    const float *p;            // plasticity's correction force (NULL: none, the instantiations without it run): the
+                               // pass takes g = ((f - y) + p) / m in both forms
 };
 constexpr uint32_t kNoDashpot = 0xFFFFFFFFu;
 void explicit_update(const DevSys &s, const ExplicitPass &a, hipStream_t st);

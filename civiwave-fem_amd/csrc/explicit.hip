@@ -45,7 +45,9 @@ __device__ __forceinline__ float safe_cast(double v)
 // carried through on node N - 1's loads, stores nothing and shares zeros. Peaks: three 4-B loads and up to three 4-B
 // stores per node (+24 B worst case; a peak that did not rise is not stored). Ledger: a dashpot node loads its C
 // (72 B); per workgroup 16 B read and written every step, 16 B more written on a sampled step.
-template <bool FOLD, bool PATTERN, bool DAMP, bool DASH, bool MON>
+// PLAS: plasticity (include/cwf_hip.h "Plasticity"): the node's correction force p (+12 B) enters g = ((f - y) + p) / m
+// in both forms; a stepper without plasticity launches the instantiations without it, whose code is what it was.
+template <bool FOLD, bool PATTERN, bool DAMP, bool DASH, bool MON, bool PLAS>
 __global__ __launch_bounds__(kBlock) void k_explicit_update(DevSys s, ExplicitPass a)
 {
     const uint32_t gid = blockIdx.x * kBlock + threadIdx.x;
@@ -92,6 +94,9 @@ __global__ __launch_bounds__(kBlock) void k_explicit_update(DevSys s, ExplicitPa
     }
     else
         f = load3(a.f, n);
+    F3 pl;
+    if constexpr (PLAS)
+        pl = load3(a.p, n);
     F3 un, vn, wn;
     const double m = (double)mass;
     bool bad = false;
@@ -112,7 +117,12 @@ __global__ __launch_bounds__(kBlock) void k_explicit_update(DevSys s, ExplicitPa
         double g[3];
 #pragma unroll
         for (int k = 0; k < 3; ++k)
-            g[k] = ((double)f.c[k] - (double)y.c[k]) / m;
+        {
+            if constexpr (PLAS)
+                g[k] = (((double)f.c[k] - (double)y.c[k]) + (double)pl.c[k]) / m;
+            else
+                g[k] = ((double)f.c[k] - (double)y.c[k]) / m;
+        }
 #pragma unroll
         for (int k = 0; k < 3; ++k)
         {
@@ -126,7 +136,11 @@ __global__ __launch_bounds__(kBlock) void k_explicit_update(DevSys s, ExplicitPa
 #pragma unroll
         for (int k = 0; k < 3; ++k)
         {
-            vn.c[k] = (float)(a.c1 * (double)v.c[k] + a.c2 * (((double)f.c[k] - (double)y.c[k]) / m));
+            if constexpr (PLAS)
+                vn.c[k] = (float)(a.c1 * (double)v.c[k] +
+                                  a.c2 * ((((double)f.c[k] - (double)y.c[k]) + (double)pl.c[k]) / m));
+            else
+                vn.c[k] = (float)(a.c1 * (double)v.c[k] + a.c2 * (((double)f.c[k] - (double)y.c[k]) / m));
             un.c[k] = (float)((double)u.c[k] + a.dt * (double)vn.c[k]);
         }
     }
@@ -454,7 +468,7 @@ __global__ __launch_bounds__(kBlock) void k_power_scale(uint32_t D, const float 
     x[i] = l > 0.0 ? (float)((double)z[i] / l) : 0.f;
 }
 
-template <bool FOLD, bool PATTERN>
+template <bool FOLD, bool PATTERN, bool PLAS>
 void launch_update(const DevSys &s, const ExplicitPass &a, hipStream_t st)
 {
     // a stepper without dashpots, and one without peak maps and ledger, launches the instantiations it always did
@@ -464,26 +478,26 @@ void launch_update(const DevSys &s, const ExplicitPass &a, hipStream_t st)
         if (a.dslot)
         {
             if (a.w != a.u)
-                k_explicit_update<FOLD, PATTERN, true, true, true><<<grid, kBlock, 0, st>>>(s, a);
+                k_explicit_update<FOLD, PATTERN, true, true, true, PLAS><<<grid, kBlock, 0, st>>>(s, a);
             else
-                k_explicit_update<FOLD, PATTERN, false, true, true><<<grid, kBlock, 0, st>>>(s, a);
+                k_explicit_update<FOLD, PATTERN, false, true, true, PLAS><<<grid, kBlock, 0, st>>>(s, a);
         }
         else if (a.w != a.u)
-            k_explicit_update<FOLD, PATTERN, true, false, true><<<grid, kBlock, 0, st>>>(s, a);
+            k_explicit_update<FOLD, PATTERN, true, false, true, PLAS><<<grid, kBlock, 0, st>>>(s, a);
         else
-            k_explicit_update<FOLD, PATTERN, false, false, true><<<grid, kBlock, 0, st>>>(s, a);
+            k_explicit_update<FOLD, PATTERN, false, false, true, PLAS><<<grid, kBlock, 0, st>>>(s, a);
     }
     else if (a.dslot)
     {
         if (a.w != a.u)
-            k_explicit_update<FOLD, PATTERN, true, true, false><<<grid, kBlock, 0, st>>>(s, a);
+            k_explicit_update<FOLD, PATTERN, true, true, false, PLAS><<<grid, kBlock, 0, st>>>(s, a);
         else
-            k_explicit_update<FOLD, PATTERN, false, true, false><<<grid, kBlock, 0, st>>>(s, a);
+            k_explicit_update<FOLD, PATTERN, false, true, false, PLAS><<<grid, kBlock, 0, st>>>(s, a);
     }
     else if (a.w != a.u)
-        k_explicit_update<FOLD, PATTERN, true, false, false><<<grid, kBlock, 0, st>>>(s, a);
+        k_explicit_update<FOLD, PATTERN, true, false, false, PLAS><<<grid, kBlock, 0, st>>>(s, a);
     else
-        k_explicit_update<FOLD, PATTERN, false, false, false><<<grid, kBlock, 0, st>>>(s, a);
+        k_explicit_update<FOLD, PATTERN, false, false, false, PLAS><<<grid, kBlock, 0, st>>>(s, a);
 }
 }  // namespace
 
@@ -492,10 +506,17 @@ void explicit_update(const DevSys &s, const ExplicitPass &a, hipStream_t st)
     if (!s.N)
         return;
     const bool pattern = a.lbase != nullptr;
-    if (!a.y)
-        pattern ? launch_update<true, true>(s, a, st) : launch_update<true, false>(s, a, st);
+    if (a.p)
+    {
+        if (!a.y)
+            pattern ? launch_update<true, true, true>(s, a, st) : launch_update<true, false, true>(s, a, st);
+        else
+            pattern ? launch_update<false, true, true>(s, a, st) : launch_update<false, false, true>(s, a, st);
+    }
+    else if (!a.y)
+        pattern ? launch_update<true, true, false>(s, a, st) : launch_update<true, false, false>(s, a, st);
     else
-        pattern ? launch_update<false, true>(s, a, st) : launch_update<false, false>(s, a, st);
+        pattern ? launch_update<false, true, false>(s, a, st) : launch_update<false, false, false>(s, a, st);
 }
 
 void explicit_energy_fold(uint32_t blocks, const double *ecum, const double *ecur, double *row, hipStream_t st)

@@ -115,7 +115,8 @@ int cwf_write_vtu(const char *path, const cwf_frame_view *f, double simulation_t
         }
         Blob blob;
         blob.bytes.reserve(4 * (6 * N) + 64);
-        uint64_t po[6], co[3];
+        uint64_t po[6], co[5];
+        const bool plastic = f->plastic_strain && f->equivalent_plastic_strain;
         po[0] = blob.append(f->displacement, 12 * N);
         po[1] = blob.append(f->velocity, 12 * N);
         po[2] = blob.append(f->acceleration, 12 * N);
@@ -134,6 +135,11 @@ int cwf_write_vtu(const char *path, const cwf_frame_view *f, double simulation_t
             co[1] = blob.append(t.data(), 4 * t.size());
             const auto v = gather_fields(f->element_fields, E, 12, 1);
             co[2] = blob.append(v.data(), 4 * v.size());
+        }
+        if (plastic)
+        {
+            co[3] = blob.append(f->plastic_strain, 24 * E);
+            co[4] = blob.append(f->equivalent_plastic_strain, 4 * E);
         }
         const uint64_t pts_off = blob.append(points.data(), 4 * points.size());
         const uint64_t conn_off = blob.append(conn.data(), 4 * conn.size());
@@ -163,10 +169,11 @@ int cwf_write_vtu(const char *path, const cwf_frame_view *f, double simulation_t
                     "offset=\"%" PRIu64 "\"/>\n",
                     pn[i], pc[i], po[i]);
         fprintf(o, "      </PointData>\n");
-        static const char *cn[3] = {"strain_elem", "stress_elem", "von_mises_elem"};
-        static const int cc[3] = {6, 6, 1};
+        static const char *cn[5] = {"strain_elem", "stress_elem", "von_mises_elem", "plastic_strain",
+                                    "equivalent_plastic_strain"};
+        static const int cc[5] = {6, 6, 1, 6, 1};
         fprintf(o, "      <CellData Scalars=\"von_mises_elem\">\n");
-        for (int i = 0; i < 3; ++i)
+        for (int i = 0; i < (plastic ? 5 : 3); ++i)
             fprintf(o,
                     "        <DataArray type=\"Float32\" Name=\"%s\" NumberOfComponents=\"%d\" format=\"appended\" "
                     "offset=\"%" PRIu64 "\"/>\n",

@@ -11,6 +11,7 @@
 // the element pass produced), then divides by the volume weight and re-evaluates von Mises from the
 // averaged stress. This TU inherits -ffp-contract=off and IEEE fp64 div/sqrt from the Makefile.
 #include "cwf_internal.hpp"
+#include "plasticity.hpp"
 
 namespace cwf
 {
@@ -100,13 +101,7 @@ __device__ __forceinline__ void element_tensors(const DevSys &s, const float *__
     }
 }
 
-// derived_fields.cpp:47-63
-__device__ __forceinline__ double von_mises(const double s[6])
-{
-    const double dxy = s[0] - s[1], dyz = s[1] - s[2], dzx = s[2] - s[0];
-    const double energy = 0.5 * (dxy * dxy + dyz * dyz + dzx * dzx) + 3.0 * (s[3] * s[3] + s[4] * s[4] + s[5] * s[5]);
-    return sqrt(energy < 0.0 ? 0.0 : energy);  // std::max(energy, 0.0), NaN passes through
-}
+// von_mises (derived_fields.cpp:47-63): plasticity.hpp, shared with the host-side return map
 
 // the 52-B element record {strain[6], stress[6], vm} of one element's tensors
 __device__ __forceinline__ void store_element_record(float *__restrict__ o, const ElemTensors &t)
@@ -252,6 +247,133 @@ __global__ __launch_bounds__(kBlock) void k_derived_nodes(DevSys s, const float 
     o[12] = (float)von_mises(avg);
 }
 
+// Plasticity of the explicit stepper (include/cwf_hip.h "Plasticity"). The element pass lives here so that the strain is
+// element_tensors' statement order under this file's flags; the return map is plasticity.hpp's, the host's too.
+//
+struct alignas(4) P3  // a node's or a corner's three f32: one 12-B access
+{
+    float c[3];
+};
+// pack.cpp:41-57 safe_cast_double_to_float, as explicit.hip's
+__device__ __forceinline__ float safe_cast(double v)
+{
+    const double fmax = 3.4028234663852886e38;  // FLT_MAX
+    if (!isfinite(v))
+        return v > 0.0 ? __int_as_float(0x7f800000) : v < 0.0 ? __int_as_float((int)0xff800000u) : __int_as_float(0x7fc00000);
+    if (v > fmax)
+        return 3.4028234663852886e38f;
+    if (v < -fmax)
+        return -3.4028234663852886e38f;
+    return (float)v;
+}
+
+// One thread per slot (plastic element, ascending element index). Every load is issued before the first fp64
+// operation: the slot's element, its 64-B record, material and volume, the 64-B state, then what depends on those (the
+// four u gathers, the material's 12 D entries and its {sy, H}). The state is stored only where the element yielded.
+// The corner forces are pushed: corner a's three floats go to position cpos[slot][a] of the node-major array, so the
+// node pass reads each node's incidences as one contiguous run (four scattered 12-B stores here, which no lane waits
+// for, instead of four scattered 12-B loads per slot there, which measured 9x their bytes in fetches). An element
+// whose abar is still 0 stores nothing: its entries hold the +0.0 they were set to, and +0.0 is what its magnitude-0
+// forces add to a sum that starts at +0.0.
+__global__ __launch_bounds__(kBlock) void k_explicit_plastic_elements(DevSys s, const float *__restrict__ u,
+                                                                      ExplicitPlasticity a)
+{
+    const uint32_t slot = blockIdx.x * kBlock + threadIdx.x;
+    if (slot >= a.slots)
+        return;
+    const uint32_t e = a.elem[slot];
+    const uint4 q0 = s.erec[4u * e + 0u];
+    const uint4 g0 = s.erec[4u * e + 1u], g1 = s.erec[4u * e + 2u], g2 = s.erec[4u * e + 3u];
+    const uint32_t m = s.mat[e];
+    const float volf = s.vol[e];
+    double2 *sp2 = reinterpret_cast<double2 *>(a.state + 8ull * slot);  // 64-B records in a hipMalloc'd array
+    const double2 s0 = sp2[0], s1 = sp2[1], s2 = sp2[2], s3 = sp2[3];
+    const uint4 cp = reinterpret_cast<const uint4 *>(a.cpos)[slot];
+    const uint32_t c[4] = {q0.x, q0.y, q0.z, q0.w};
+    float uf[12];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+    {
+        uf[3 * k] = u[3ull * c[k] + 0];
+        uf[3 * k + 1] = u[3ull * c[k] + 1];
+        uf[3 * k + 2] = u[3ull * c[k] + 2];
+    }
+    const double *Dm = s.dmat + 36ull * m;
+    double D[36];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+    {
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            D[6 * r + k] = Dm[6 * r + k];
+        D[7 * (r + 3)] = Dm[7 * (r + 3)];
+    }
+    const double2 yh = reinterpret_cast<const double2 *>(a.yield_hard)[m];
+    const float g[12] = {__uint_as_float(g0.x), __uint_as_float(g0.y), __uint_as_float(g0.z), __uint_as_float(g0.w),
+                         __uint_as_float(g1.x), __uint_as_float(g1.y), __uint_as_float(g1.z), __uint_as_float(g1.w),
+                         __uint_as_float(g2.x), __uint_as_float(g2.y), __uint_as_float(g2.z), __uint_as_float(g2.w)};
+    // element_tensors' strain
+    double e6[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+    {
+        const double ux = (double)uf[3 * k], uy = (double)uf[3 * k + 1], uz = (double)uf[3 * k + 2];
+        const double gx = (double)g[3 * k], gy = (double)g[3 * k + 1], gz = (double)g[3 * k + 2];
+        e6[0] += gx * ux;
+        e6[1] += gy * uy;
+        e6[2] += gz * uz;
+        e6[3] += gy * ux + gx * uy;
+        e6[4] += gz * uy + gy * uz;
+        e6[5] += gz * ux + gx * uz;
+    }
+    double ep[6] = {s0.x, s0.y, s1.x, s1.y, s2.x, s2.y}, abar = s3.x, wp = s3.y, sp[6];
+    const double V = (double)volf;
+    if (j2_update(D, yh.x, yh.y, V, e6, ep, abar, wp, sp))
+    {
+        sp2[0] = make_double2(ep[0], ep[1]);
+        sp2[1] = make_double2(ep[2], ep[3]);
+        sp2[2] = make_double2(ep[4], ep[5]);
+        sp2[3] = make_double2(abar, wp);
+    }
+    if (!(abar > 0.0))
+        return;
+    const uint32_t pos[4] = {cp.x, cp.y, cp.z, cp.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+    {
+        const double gx = (double)g[3 * k], gy = (double)g[3 * k + 1], gz = (double)g[3 * k + 2];
+        P3 o;
+        o.c[0] = safe_cast(V * ((gx * sp[0] + gy * sp[3]) + gz * sp[5]));
+        o.c[1] = safe_cast(V * ((gy * sp[1] + gx * sp[3]) + gz * sp[4]));
+        o.c[2] = safe_cast(V * ((gz * sp[2] + gy * sp[4]) + gx * sp[5]));
+        *reinterpret_cast<P3 *>(a.corner + 3ull * pos[k]) = o;
+    }
+}
+
+// One thread per affected node: its run of the node-major corner forces (ascending element, built at set time), each
+// widened to double and added from +0.0 in that order, safe_cast, one 12-B store into the correction vector p the
+// update pass reads. Consecutive nodes read consecutive runs. Rows of other nodes stay at the zero they were set to.
+__global__ __launch_bounds__(kBlock) void k_explicit_plastic_nodes(ExplicitPlasticity a)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= a.affected)
+        return;
+    const uint32_t end = a.aoff[i + 1];
+    double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0;
+    for (uint32_t j = a.aoff[i]; j < end; ++j)
+    {
+        const P3 c = *reinterpret_cast<const P3 *>(a.corner + 3ull * j);
+        acc0 = acc0 + (double)c.c[0];
+        acc1 = acc1 + (double)c.c[1];
+        acc2 = acc2 + (double)c.c[2];
+    }
+    P3 o;
+    o.c[0] = safe_cast(acc0);
+    o.c[1] = safe_cast(acc1);
+    o.c[2] = safe_cast(acc2);
+    *reinterpret_cast<P3 *>(a.p + 3ull * a.anode[i]) = o;
+}
+
 inline unsigned grid_for(uint64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
 template <bool HEX>
@@ -293,6 +415,14 @@ void explicit_element_monitors(const DevSys &s, const float *u, const ExplicitEl
         s.iso ? element_monitors_k<true, true>(s, u, a, st) : element_monitors_k<false, true>(s, u, a, st);
     else
         s.iso ? element_monitors_k<true, false>(s, u, a, st) : element_monitors_k<false, false>(s, u, a, st);
+}
+
+void explicit_plasticity(const DevSys &s, const float *u, const ExplicitPlasticity &a, hipStream_t st)
+{
+    if (!a.slots)
+        return;
+    k_explicit_plastic_elements<<<grid_for(a.slots), kBlock, 0, st>>>(s, u, a);
+    k_explicit_plastic_nodes<<<grid_for(a.affected), kBlock, 0, st>>>(a);
 }
 
 void derived_fields(cwf_hip_system *h, const float *u, float *elem_out, float *node_out, hipStream_t st)

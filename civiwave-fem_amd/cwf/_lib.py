@@ -145,6 +145,15 @@ class ExplicitSourceInfoC(C.Structure):
                 ("loaded_nodes", C.c_uint64), ("curve_points", C.c_uint64), ("device_bytes", C.c_uint64)]
 
 
+class ExplicitPlasticityDescC(C.Structure):
+    _fields_ = [("yield_stress", C.c_void_p), ("hardening", C.c_void_p), ("material_count", C.c_uint64)]
+
+
+class ExplicitPlasticityInfoC(C.Structure):
+    _fields_ = [("plastic_elements", C.c_uint64), ("affected_nodes", C.c_uint64), ("yielded_elements", C.c_uint64),
+                ("bytes", C.c_uint64)]
+
+
 class ShardInfoC(C.Structure):
     _fields_ = [
         ("owned_nodes", C.c_uint64), ("local_nodes", C.c_uint64), ("local_elements", C.c_uint64),
@@ -164,6 +173,7 @@ class FrameViewC(C.Structure):
         ("node_count", C.c_uint64), ("element_count", C.c_uint64), ("position0", C.c_void_p),
         ("displacement", C.c_void_p), ("velocity", C.c_void_p), ("acceleration", C.c_void_p),
         ("element_fields", C.c_void_p), ("node_fields", C.c_void_p), ("connectivity", C.c_void_p),
+        ("plastic_strain", C.c_void_p), ("equivalent_plastic_strain", C.c_void_p),
     ]
 
 
@@ -264,6 +274,11 @@ def load() -> C.CDLL:
         "cwf_hip_explicit_set_sources": ([P, P, C.c_uint32], i32),
         "cwf_hip_explicit_get_sources": ([P, P, P], i32),
         "cwf_hip_explicit_source_info": ([P, P], i32),
+        "cwf_hip_explicit_set_plasticity": ([P, P], i32),
+        "cwf_hip_explicit_reset_plasticity": ([P], i32),
+        "cwf_hip_explicit_plasticity_info": ([P, P], i32),
+        "cwf_hip_explicit_read_plasticity": ([P, P, P, P, u64], i32),
+        "cwf_explicit_j2_update": ([P, f64, f64, f64, P, P, P], i32),
         "cwf_explicit_dashpot_update": ([P, f64, f64, f64, P, P], i32),
         "cwf_absorbing_dashpots": ([u64, P, u64, C.c_uint32, P, P, u64, P, P, P, u64, C.c_uint32, P, P, P, P], i32),
         "cwf_absorbing_incident_plane": ([u64, P, u64, C.c_uint32, P, P, u64, P, P, P, u64, C.c_uint32, P, P, P, P, P, P,

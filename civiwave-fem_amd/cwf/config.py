@@ -33,7 +33,8 @@ def _from_json(d: dict) -> Config:
     f = float
     return Config(
         mesh_path=d["mesh_path"],
-        materials=[Material(m["name"], f(m["E"]), f(m["nu"]), f(m["rho"])) for m in d["materials"]],
+        materials=[Material(m["name"], f(m["E"]), f(m["nu"]), f(m["rho"]), f(m.get("yield_stress", 0.0)),
+                            f(m.get("hardening_modulus", 0.0))) for m in d["materials"]],
         assignments=[Assignment(a["group"], a["material"]) for a in d["assignments"]],
         damping=Damping(f(d["damping"]["xi"]), f(d["damping"]["w1"]), f(d["damping"]["w2"])),
         time=TimeSettings(f(d["time"]["initial_dt"]), bool(d["time"]["adaptive"]), f(d["time"]["min_dt"]),

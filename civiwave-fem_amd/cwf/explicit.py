@@ -168,6 +168,40 @@ class SourceInfo:
     device_bytes: int
 
 
+@dataclass
+class PlasticityInfo:
+    plastic_elements: int
+    affected_nodes: int
+    yielded_elements: int
+    bytes: int
+
+
+@dataclass
+class PlasticState:
+    """The plastic state in the caller's element order (include/cwf_hip.h "Plasticity"); elastic elements hold zeros."""
+    plastic_strain: np.ndarray             # f64 [E,6], Voigt, engineering shears
+    equivalent_plastic_strain: np.ndarray  # f64 [E]
+    plastic_work: np.ndarray               # f64 [E], J
+    stiffness: np.ndarray                  # f64 [E,6,6] each element's D
+
+    def stress(self, strain) -> np.ndarray:
+        """D (e - ep) of total strains [E,6] (float64, host): the stress the material carries."""
+        ee = np.asarray(strain, np.float64) - self.plastic_strain
+        return np.einsum("eij,ej->ei", self.stiffness, ee)
+
+
+def j2_update(D, yield_stress: float, hardening: float, volume: float, strain, state):
+    """The element update of the plasticity scheme by the library (host only). D [6,6] isotropic, strain [6], state
+    [8] = ep[6], abar, wp -> (yielded, the new state [8], sigma_p = D ep [6])."""
+    Dm = np.ascontiguousarray(D, np.float64).reshape(36)
+    e = np.ascontiguousarray(strain, np.float64).reshape(6)
+    st = np.array(state, np.float64).reshape(8)
+    sp = np.zeros(6, np.float64)
+    y = _lib.load().cwf_explicit_j2_update(_lib.ptr(Dm), float(yield_stress), float(hardening), float(volume),
+                                           _lib.ptr(e), _lib.ptr(st), _lib.ptr(sp))
+    return bool(y), st, sp
+
+
 def lambda_max(system: MatrixFreeSystem, iterations: int = 60):
     """-> (estimate of the largest eigenvalue of M^-1 K over the free DOFs, the last iteration's relative change)."""
     lam, change = C.c_double(), C.c_double()
@@ -198,7 +232,7 @@ class ExplicitStepper(TransientState):
     implicit scheme's step, so neither sets the explicit step: ``dt`` does (0: safety x the estimated limit).
     State, external force, load pattern, times and close(): cwf.transient.TransientState."""
 
-    DISPLACEMENT, VELOCITY, ACCELERATION, EXTERNAL_FORCE = 0, 1, 2, 4
+    DISPLACEMENT, VELOCITY, ACCELERATION, EXTERNAL_FORCE, PLASTIC_FORCE = 0, 1, 2, 4, 5
     _PREFIX, _HANDLE = "cwf_hip_explicit", "_ex"
 
     def __init__(self, packing, materials, rayleigh: RayleighCoefficients,
@@ -206,6 +240,7 @@ class ExplicitStepper(TransientState):
                  dt: float = 0.0, safety: float = 0.9, power_iterations: int = 60, mode: int = _lib.MODE_PARITY,
                  device: int = 0, system: MatrixFreeSystem | None = None):
         self.packing = packing
+        self.materials = materials
         self.system = system or MatrixFreeSystem.from_packing(packing, materials, 1.0, 0.0, mode, device)
         h = self.system.handle()
         self._f = np.ascontiguousarray(packing.external_force, np.float32)
@@ -320,6 +355,39 @@ class ExplicitStepper(TransientState):
         self._check(_lib.load().cwf_hip_explicit_source_info(self._ex, C.byref(i)))
         return SourceInfo(int(i.source_count), int(i.entry_count), int(i.loaded_nodes), int(i.curve_points),
                           int(i.device_bytes))
+
+    # ---- plasticity (include/cwf_hip.h "Plasticity") ----
+    def set_plasticity(self, yield_stress, hardening=0.0):
+        """J2 plasticity with linear isotropic hardening: a yield stress and a hardening modulus per material (scalars
+        apply to every material); a yield stress of 0 or inf leaves that material elastic. The state starts at zero.
+        Replaces the previous set, which stays in force if this one is refused (RuntimeError)."""
+        sy = np.asarray(yield_stress, np.float64)
+        sy = np.ascontiguousarray(np.broadcast_to(sy, (len(self.materials),)) if sy.ndim == 0 else sy.reshape(-1))
+        H = np.asarray(hardening, np.float64)
+        H = np.ascontiguousarray(np.broadcast_to(H, (sy.size,)) if H.ndim == 0 else H.reshape(-1))
+        if H.size != sy.size:
+            raise ValueError("one hardening modulus per yield stress")
+        d = _lib.ExplicitPlasticityDescC(sy.ctypes.data, H.ctypes.data, sy.size)
+        self._check(_lib.load().cwf_hip_explicit_set_plasticity(self._ex, C.byref(d)))
+
+    def clear_plasticity(self):
+        self._check(_lib.load().cwf_hip_explicit_set_plasticity(self._ex, None))
+
+    def reset_plasticity(self):
+        """The same set: plastic strain, equivalent plastic strain, plastic work and the correction force zeroed."""
+        self._check(_lib.load().cwf_hip_explicit_reset_plasticity(self._ex))
+
+    def plasticity_info(self) -> PlasticityInfo:
+        i = _lib.ExplicitPlasticityInfoC()
+        self._check(_lib.load().cwf_hip_explicit_plasticity_info(self._ex, C.byref(i)))
+        return PlasticityInfo(int(i.plastic_elements), int(i.affected_nodes), int(i.yielded_elements), int(i.bytes))
+
+    def plasticity(self) -> PlasticState:
+        E = self.element_count
+        ep, abar, wp = np.zeros((E, 6), np.float64), np.zeros(E, np.float64), np.zeros(E, np.float64)
+        self._check(_lib.load().cwf_hip_explicit_read_plasticity(self._ex, _lib.ptr(ep), _lib.ptr(abar), _lib.ptr(wp), E))
+        D = np.stack([np.asarray(m.stiffness, np.float64).reshape(6, 6) for m in self.materials])
+        return PlasticState(ep, abar, wp, D[np.asarray(self.packing.material_index, np.int64)])
 
     # ---- monitors (include/cwf_hip.h "Monitors") ----
     def set_monitors(self, receivers=None, receiver_every: int = 1, receiver_capacity: int = 0, peaks: bool = False,

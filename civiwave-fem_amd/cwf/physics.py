@@ -15,6 +15,8 @@ class Material:
     youngs_modulus: float
     poisson_ratio: float
     density: float
+    yield_stress: float = 0.0       # J2 plasticity of the explicit integrator; 0: elastic
+    hardening_modulus: float = 0.0  # linear isotropic hardening H
 
 
 @dataclass

@@ -78,7 +78,7 @@ def compute_derived_fields(packing, materials=None, system: MatrixFreeSystem | N
             system.close()
 
 
-def _frame(packing, derived: DerivedFieldSet, keep: list) -> _lib.FrameViewC:
+def _frame(packing, derived: DerivedFieldSet, keep: list, plastic=None) -> _lib.FrameViewC:
     arrs = [np.ascontiguousarray(np.asarray(packing.position0, np.float32).reshape(-1)),
             np.ascontiguousarray(packing.displacement, np.float32).reshape(-1),
             np.ascontiguousarray(packing.velocity, np.float32).reshape(-1),
@@ -86,16 +86,22 @@ def _frame(packing, derived: DerivedFieldSet, keep: list) -> _lib.FrameViewC:
             np.ascontiguousarray(derived.elements, np.float32),
             np.ascontiguousarray(derived.nodes, np.float32),
             np.ascontiguousarray(packing.connectivity, np.uint32)]
+    if plastic is not None:  # (plastic strain [E,6], equivalent plastic strain [E]): two more cell arrays
+        arrs += [np.ascontiguousarray(plastic[0], np.float32).reshape(-1),
+                 np.ascontiguousarray(plastic[1], np.float32).reshape(-1)]
     keep.extend(arrs)
     p = _lib.ptr
     return _lib.FrameViewC(packing.node_count, packing.element_count, *(p(a) for a in arrs))
 
 
-def write_vtu(path, packing, derived: DerivedFieldSet, simulation_time: float, frame_index: int) -> Expected:
+def write_vtu(path, packing, derived: DerivedFieldSet, simulation_time: float, frame_index: int,
+              plastic=None) -> Expected:
     """vtu_writer.cpp:171 write_vtu(path, mesh, packing, derived, time, frame); the cells are the packed
-    connectivity (the mesh's tet4 elements in mesh order)."""
+    connectivity (the mesh's tet4 elements in mesh order). plastic: (plastic strain [E,6], equivalent plastic strain
+    [E]) of an explicit stepper with plasticity, written as the cell arrays plastic_strain and
+    equivalent_plastic_strain."""
     keep: list = []
-    f = _frame(packing, derived, keep)
+    f = _frame(packing, derived, keep, plastic)
     rc = _lib.load().cwf_write_vtu(os.fsencode(str(path)), C.byref(f), float(simulation_time), int(frame_index))
     if rc:
         msg, ctx = _lib.last_error(None)
@@ -143,13 +149,18 @@ class OutputManager:
         if self._own:
             self.system = MatrixFreeSystem.from_packing(packing, materials, 1.0, 0.0, _lib.MODE_PARITY)
         self.probe_logger = ProbeLogger(os.path.join(self.root, "probes", "probes.csv"), settings.probes)
+        self.plasticity = None  # a callable -> cwf.explicit.PlasticState: its arrays go into the VTU frames
 
     def _write_vtu_frame(self, derived, simulation_time, frame_index) -> Expected:
         stride = int(self.settings.vtu_stride)
         if stride == 0 or frame_index % stride != 0:
             return Expected(True)
         path = os.path.join(self.root, "vtu", f"frame_{frame_index:05d}.vtu")
-        r = write_vtu(path, self.packing, derived, simulation_time, frame_index)
+        plastic = None
+        if self.plasticity is not None:
+            ps = self.plasticity()
+            plastic = (ps.plastic_strain, ps.equivalent_plastic_strain)
+        r = write_vtu(path, self.packing, derived, simulation_time, frame_index, plastic)
         if not r.has_value():
             return Expected(error=PostError("vtu: " + r.error().message, r.error().context))
         return r

@@ -84,6 +84,8 @@ def run_scenario(cfg_path: str, steps: int, out_dir: str | None, mode: int = _li
     cfg, m, P, materials = load_scenario(cfg_path, allow_hex8=mode == _lib.MODE_FAST)
     if cfg.absorbing:
         raise ScenarioError("absorbing boundaries need the explicit integrator")
+    if any(x.yield_stress > 0.0 for x in cfg.materials):
+        raise ScenarioError("plastic materials need the explicit integrator")
     st = Stepper(P, materials, compute_rayleigh(cfg.damping), cfg.solver, cfg.time, mode=mode, device=device)
     om = post.OutputManager(out_dir, m, P, materials, cfg.output, stepper=st) if out_dir else None
     t_sim, total_iters, wall0 = 0.0, 0, time.perf_counter()
@@ -121,13 +123,15 @@ def run_scenario(cfg_path: str, steps: int, out_dir: str | None, mode: int = _li
 def run_scenario_explicit(cfg_path: str, steps: int, out_dir: str | None, mode: int = _lib.MODE_PARITY,
                           device: int = 0, safety: float = 0.9, log=print, trace_every: int = 0, peaks: bool = False,
                           energy_every: int = 0, mass_damping_only: bool = False, envelope_every: int = 0,
-                          gauges=(), gauge_every: int = 1) -> dict:
+                          gauges=(), gauge_every: int = 1, plastic_summary: bool = False) -> dict:
     """`steps` output frames of the explicit stepper, ceil(cfg.time.initial_dt / dt) explicit steps each.
     trace_every / peaks / energy_every: the stepper's monitors (receivers at cfg.output.probes), written under
     out_dir after the last frame; their capacities follow from `steps`. mass_damping_only: the stepper gets the
     scenario's alpha_R and beta_R = 0 (a scenario's damping always has beta_R > 0, which the energy ledger refuses).
     envelope_every / gauges, gauge_every: the stepper's element monitors (all three envelope maps; gauge elements in
-    the mesh's numbering), written under out_dir after the last frame."""
+    the mesh's numbering), written under out_dir after the last frame. Materials with a ``yield_stress`` yield (J2
+    plasticity): the VTU frames then carry plastic_strain and equivalent_plastic_strain per cell, and
+    plastic_summary logs one line with the yielded elements and the total plastic work after the last frame."""
     import math
 
     from .explicit import ExplicitStepper
@@ -144,6 +148,14 @@ def run_scenario_explicit(cfg_path: str, steps: int, out_dir: str | None, mode: 
     wall0, last = time.perf_counter(), None
     try:
         absorbing_nodes = set_absorbing(st, cfg, m, P)
+        plastic = any(x.yield_stress > 0.0 for x in cfg.materials)
+        if plastic:
+            try:
+                st.set_plasticity([x.yield_stress for x in cfg.materials], [x.hardening_modulus for x in cfg.materials])
+            except RuntimeError as e:
+                raise ScenarioError(str(e)) from None
+            if om is not None:
+                om.plasticity = st.plasticity
         info = st.source_info()
         sources = dict(sources=info.source_count, source_nodes=info.loaded_nodes) if info.source_count else {}
         tel = st.telemetry()
@@ -185,6 +197,14 @@ def run_scenario_explicit(cfg_path: str, steps: int, out_dir: str | None, mode: 
             if monitored and out_dir else {}
         if element_monitored:
             written.update(write_element_monitors(st, out_dir, gauges, envelope_every > 0))
+        if plastic:
+            pi = st.plasticity_info()
+            written.update(plastic_elements=pi.plastic_elements, yielded_elements=pi.yielded_elements,
+                           plastic_work=float(st.plasticity().plastic_work.sum()))
+            if plastic_summary:
+                log(json.dumps(dict(plastic_summary=dict(plastic_elements=pi.plastic_elements,
+                                                         yielded_elements=pi.yielded_elements,
+                                                         plastic_work=written["plastic_work"]))))
         wall = time.perf_counter() - wall0
         return dict(scenario=cfg_path, nodes=P.node_count, tets=P.element_count, dofs=P.dof_count, steps=steps,
                     integrator="explicit", explicit_steps=tel.steps, steps_per_frame=per_frame, dt=tel.dt,
@@ -359,6 +379,9 @@ def main(argv=None) -> int:
     ap.add_argument("--gauges", default="", metavar="E0,E1,...",
                     help="explicit: strain / stress / von Mises rows of these elements -> <out>/monitors/gauges.csv")
     ap.add_argument("--gauge-every", type=int, default=1, metavar="K", help="explicit: a gauge row every K steps")
+    ap.add_argument("--plastic-summary", action="store_true",
+                    help="explicit, materials with a yield_stress: one line with the yielded elements and the total "
+                         "plastic work after the last frame")
     a = ap.parse_args(argv)
     try:
         gauges = [int(x) for x in a.gauges.split(",") if x.strip()]
@@ -373,7 +396,7 @@ def main(argv=None) -> int:
                                       _lib.MODE_FAST if a.mode == "fast" else _lib.MODE_PARITY, a.device, a.safety,
                                       trace_every=a.trace_every, peaks=a.peaks, energy_every=a.energy_every,
                                       mass_damping_only=a.mass_damping_only, envelope_every=a.envelope_every,
-                                      gauges=gauges, gauge_every=a.gauge_every)
+                                      gauges=gauges, gauge_every=a.gauge_every, plastic_summary=a.plastic_summary)
             print(json.dumps(dict(summary=s)))
             return 0
         if a.trace_every or a.peaks or a.energy_every or a.mass_damping_only:
@@ -381,6 +404,8 @@ def main(argv=None) -> int:
                                 "integrator")
         if a.envelope_every or gauges or a.gauge_every != 1:
             raise ScenarioError("--envelope-every, --gauges and --gauge-every belong to the explicit integrator")
+        if a.plastic_summary:
+            raise ScenarioError("--plastic-summary belongs to the explicit integrator")
         s = run_scenario(a.scenario, a.steps, a.out, _lib.MODE_FAST if a.mode == "fast" else _lib.MODE_PARITY,
                          a.device, a.paused, a.time_varying_loads)
     except ScenarioError as e:

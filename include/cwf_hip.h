@@ -495,6 +495,58 @@ int cwf_hip_stepper_time(const cwf_hip_stepper *st, double *current_time, double
  * array of 12 bytes per loaded node, which set_external_force refreshes and a removed set writes back. Sources and a
  * load pattern exclude each other. A stepper without sources launches exactly the kernels it launches without this
  * section and allocates nothing for it.
+ *
+ * Plasticity (cwf_hip_explicit_set_plasticity): rate-independent von Mises (J2) plasticity with linear isotropic
+ * hardening on tet4 elements, by radial return, in the initial-stress form: the operator product stays the linear
+ * y = K w on whichever path the handle takes, and the plastic strain enters as a correction force. A material m is
+ * plastic when its yield stress sy_m is finite and > 0; its hardening modulus is H_m >= 0; its D must have the
+ * isotropic Voigt pattern, mu = D[3][3] (engineering shears, as the post stack). An element of a plastic material is a
+ * plastic element and owns a slot, slots in ascending element index; a node with at least one plastic incident element
+ * is an affected node. State per slot, fp64: ep[6] (plastic strain, Voigt, engineering shears), abar (equivalent
+ * plastic strain), wp (plastic work); all zero at set and at reset.
+ * The step that takes the step count from n to n + 1 runs an element pass and a node pass before its operator launch.
+ * The element pass reads u_n, the stored displacement (not the operator's input w). Per plastic element, in fp64
+ * without fused multiply-adds:
+ *     e      = strain of u_n                     the derived-fields element pass's statement order
+ *     ee_r   = e_r - ep_r
+ *     st     = D ee                              its isotropic row fold: a normal row adds its three normal columns
+ *                                                from +0.0, a shear row is 0.0 + D_rr ee_r
+ *     q      = von_mises(st)                     the derived fields' function
+ *     Y      = sy + H * abar
+ *     if q > Y:                                  (a NaN never yields)
+ *         dg   = (q - Y) / (3.0 * mu + H)
+ *         pm   = ((st_0 + st_1) + st_2) / 3.0
+ *         s_r  = st_r - pm (r < 3),  s_r = st_r (r >= 3)
+ *         fac  = (1.5 * dg) / q
+ *         ep_r = ep_r + fac * s_r (r < 3);   ep_r = ep_r + (2.0 * fac) * s_r (r >= 3)
+ *         abar = abar + dg
+ *         wp   = wp + V * ((sy + H * abar) * dg)         abar already updated; V = (double)vol[e]
+ *     sp     = D ep                              the same row fold
+ *     corner a (gradient g = (gx, gy, gz), widened to double):
+ *         c_a0 = V * ((gx*sp_0 + gy*sp_3) + gz*sp_5)
+ *         c_a1 = V * ((gy*sp_1 + gx*sp_3) + gz*sp_4)
+ *         c_a2 = V * ((gz*sp_2 + gy*sp_4) + gx*sp_5)     each stored as f32 (safe_cast)
+ * Per affected node and component k the correction force is p_k = safe_cast(sum over the node's plastic incidences,
+ * ascending element order, from +0.0, of (double)c). The update pass then takes
+ *     g_k = (((double)f_k - (double)y_k) + (double)p_k) / m
+ * in the plain form and in the dashpot form; everything else in the pass is unchanged, so M a = f - (K u - B^T D ep V).
+ * Constrained DOFs are masked as always. An element whose abar is still 0 has ep = 0 and contributes corner forces of
+ * magnitude 0, and adding a zero to a sum that starts at +0.0 leaves +0.0: a plastic material that never yields steps as
+ * the elastic one up to the sign of a zero ((f - y) + 0.0 turns -0.0 into +0.0).
+ * The critical step is unchanged: the elastoplastic tangent D - (3 mu)^2 / (3 mu + H) n n^T (n the unit flow direction)
+ * is D minus a positive-semidefinite matrix, so the tangent stiffness is never stiffer than K and lambda_max of
+ * M^-1 K bounds it; the return map itself is unconditionally stable.
+ * On the device: per slot its element (4 B), 64 B of state, 16 B of corner positions and 48 B of corner forces; 16 B
+ * of {sy, H} per material; 8 B per affected node (the node and its run); and the f32 [3N] vector p, zeroed at set, of
+ * which only the affected rows are rewritten; all in the stepper's arena. The corner forces are stored node-major: an
+ * affected node's plastic incidences are one contiguous run of 12-B entries in ascending element order, the element
+ * pass pushes each corner's force to its position in that run, and the node pass reads runs, consecutive nodes
+ * consecutive runs. No atomics, no second stream. The state is written only where an element yielded in that step,
+ * and an element whose abar is still 0 stores no corner forces (its entries hold the +0.0 they were set to).
+ * The energy ledger and plasticity exclude each other: the ledger's potential term 1/2 u . K u is the linear one, so its
+ * balance would no longer be constant. Element monitors and gauges keep reporting D e, the stress of the total strain;
+ * the stress D (e - ep) is formed on the host from cwf_hip_explicit_read_plasticity. A stepper without plasticity
+ * launches exactly the kernels it launches without this section and allocates nothing for it.
  * ------------------------------------------------------------------------------------- */
 typedef struct cwf_explicit_desc
 {
@@ -530,7 +582,8 @@ void cwf_hip_explicit_destroy(cwf_hip_explicit *ex);
  * returns CWF_ERR_HIP "explicit step produced a non-finite value" {steps=<steps since create>} -- the device reported
  * the failure, not the host -- and so does every later call until set_state rewrites u or v. */
 int cwf_hip_explicit_advance(cwf_hip_explicit *ex, uint64_t n_steps, cwf_explicit_telemetry *tel);
-/* which: 0 = u, 1 = v (half step), 4 = external force at the last step (get only); [3N], the caller's node order */
+/* which: 0 = u, 1 = v (half step), 4 = external force at the last step (get only), 5 = plasticity's correction force p
+ * of the last step (get only, while plasticity is set); [3N], the caller's node order */
 int cwf_hip_explicit_get_state(cwf_hip_explicit *ex, int which, float *out, uint64_t n, int ptr_kind);
 int cwf_hip_explicit_set_state(cwf_hip_explicit *ex, int which, const float *in, uint64_t n, int ptr_kind);
 int cwf_hip_explicit_set_external_force(cwf_hip_explicit *ex, const float *f, uint64_t n, int ptr_kind);
@@ -696,6 +749,44 @@ int cwf_hip_explicit_set_sources(cwf_hip_explicit *ex, const cwf_explicit_source
  * or destroy. */
 int cwf_hip_explicit_get_sources(cwf_hip_explicit *ex, uint32_t *count, cwf_explicit_source_desc *sources);
 int cwf_hip_explicit_source_info(cwf_hip_explicit *ex, cwf_explicit_source_info *info);
+/* Plasticity of the scheme above. yield_stress[m] = +inf or 0: material m is elastic. */
+typedef struct cwf_explicit_plasticity_desc
+{
+    const double *yield_stress; /* [material_count] sy, Pa */
+    const double *hardening;    /* [material_count] H >= 0, Pa */
+    uint64_t material_count;    /* the handle's */
+} cwf_explicit_plasticity_desc;
+
+typedef struct cwf_explicit_plasticity_info
+{
+    uint64_t plastic_elements; /* slots */
+    uint64_t affected_nodes;
+    uint64_t yielded_elements; /* abar > 0, counted on read */
+    uint64_t bytes;            /* what the set holds in the stepper's arena */
+} cwf_explicit_plasticity_info;
+
+/* Replaces the set in force, its state starting at zero; desc NULL, or a desc without a plastic element, removes
+ * plasticity and frees its buffers (the stepper then launches what a stepper that never had it launches). u, v, the step
+ * count, loads, dashpots, sources and monitors are kept. Everything refusable is checked before anything changes, and a
+ * refusal leaves the previous set in force: CWF_ERR_UNSUPPORTED "plasticity needs tet4 elements" (a hex8 handle), "a
+ * plastic material needs an isotropic stiffness" {material=<m>}, "the energy ledger and plasticity exclude each other"
+ * (cwf_hip_explicit_set_monitors answers the same for a ledger while plasticity is in force); CWF_ERR_ARGUMENT
+ * "plasticity material count mismatch" {material_count=<given>, materials=<the handle's>}, "yield stress and hardening
+ * must be non-negative" {material=<m>, yield_stress=<sy>, hardening=<H>} (a NaN too), "null pointer"; CWF_ERR_ALLOC. */
+int cwf_hip_explicit_set_plasticity(cwf_hip_explicit *ex, const cwf_explicit_plasticity_desc *desc);
+/* The same set: ep, abar, wp and p zeroed. set_state leaves them alone. */
+int cwf_hip_explicit_reset_plasticity(cwf_hip_explicit *ex);
+int cwf_hip_explicit_plasticity_info(cwf_hip_explicit *ex, cwf_explicit_plasticity_info *info);
+/* The state in the caller's element numbering into host memory: ep [E][6], abar [E], wp [E], each nullable; n = E.
+ * Elastic elements read as zeros. CWF_ERR_ARGUMENT "no plasticity is set"; CWF_ERR_SIZE "plasticity span size
+ * mismatch" {span=<n>, elements=<E>}. cwf_hip_explicit_get_state(which = 5) returns p of the last step taken, [3N] in
+ * the caller's node order ("unknown state field" without plasticity). */
+int cwf_hip_explicit_read_plasticity(cwf_hip_explicit *ex, double *ep, double *abar, double *wp, uint64_t n);
+/* Host only, no GPU: the element update of the scheme above, the function the device pass runs. D row-major [36] with
+ * the isotropic pattern, strain = e[6], state = ep[6], abar, wp (updated in place where the element yields), sigma_p
+ * = D ep of the updated state. Returns 1 when the element yielded, else 0. */
+int cwf_explicit_j2_update(const double D[36], double yield, double hardening, double volume, const double strain[6],
+                           double state[8], double sigma_p[6]);
 /* Host only, no GPU: P and Q of the scheme above from C (row-major), the node's mass, alpha_R and dt, by the
  * closed-form 3x3 inverse. CWF_ERR_ARGUMENT for a C that is not finite ("dashpot matrix is not finite"), not symmetric
  * (|C_ij - C_ji| > 1e-12 trace: "dashpot matrix is not symmetric") or not positive semidefinite (a principal minor
@@ -890,6 +981,10 @@ typedef struct cwf_frame_view
     const float *element_fields; /* [13E] */
     const float *node_fields;    /* [13N] */
     const uint32_t *connectivity;
+    /* the explicit stepper's plasticity (both NULL: none): two more Float32 cell arrays of the VTU frame,
+     * plastic_strain (6 components) and equivalent_plastic_strain; the probe logger does not read them */
+    const float *plastic_strain;            /* [6E] */
+    const float *equivalent_plastic_strain; /* [E] */
 } cwf_frame_view;
 
 /* cwf::post::write_vtu (vtu_writer.cpp:171-297): binary-appended UnstructuredGrid, byte-identical to

@@ -6,6 +6,7 @@
     python tools/explicit_bench.py --monitors [--configs c2 c3] [--steps 2000]
     python tools/explicit_bench.py --sources [--configs c2 c3] [--steps 2000]
     python tools/explicit_bench.py --envelopes [--configs c2 c3 c2:hex8] [--steps 2000]
+    python tools/explicit_bench.py --plasticity [--plain-only] [--repeats 5] [--configs c2 c3] [--steps 2000]
 
 Per config (a FAST handle of the block, created with scalars (1, 0)), in one process and one JSON line each, appended
 to --out (default profiles/explicit_c2.json):
@@ -43,6 +44,18 @@ clear_element_monitors again; next to them the time of one element pass (the eve
 the estimate from bytes at the 6.25 TB/s copy ceiling: per element its record (tet4: 64 B + 4 B material; hex8: 32 B
 of corner ids + 96 B of gradients + 4 B), the u gathers counted once per node (12 B x nodes / elements: the rest are
 cache hits), and the maps read once and written at most once (4 to 56 B each way).
+
+--plasticity: the cost of J2 plasticity (include/cwf_hip.h "Plasticity"). Per config three lines, appended to
+profiles/explicit_plasticity.json, one stepper on one FAST handle: (a) "plain", no plasticity, the step timed
+--repeats times (the median, and the spread (max - min) / median, which is what a comparison between two builds of the
+library has to exceed); (b) "elastic", every material plastic with a yield stress nothing reaches; (c) "yielding", a
+yield stress of 1 Pa, which the block's own weight passes almost everywhere. (b) and (c) carry the time the two
+plasticity kernels and the update pass's read of p add over (a), next to the estimate from bytes at the 6.25 TB/s copy
+ceiling: per slot the 64-B record, 4 B material, 4 B volume, 4 B slot element, 64 B of state and 16 B of corner positions
+read, 48 B of corner forces read by the node pass; per node 12 B of u gathered once (the rest are cache hits), 8 B of
+the compact CSR, 12 B of p stored and 12 B read by the update pass; per element that has yielded 48 B of corner forces
+and (at most) 64 B of state written. --plain-only: line (a) alone, which a library without the feature can run
+(CWF_LIB_PATH: the same-session comparison with the parent commit's build).
 """
 import argparse
 import ctypes as C
@@ -322,6 +335,43 @@ def measure_envelopes(key, steps, device):
     return out
 
 
+def measure_plasticity(key, steps, device, repeats, plain_only, only=None):
+    import statistics
+
+    name, _, element = key.partition(":")
+    case = scenarios.config_case(name, element=element or "tet4")
+    P = case.packing
+    N, E = P.node_count, P.element_count
+    sysm = pcg.MatrixFreeSystem.from_packing(P, case.materials, 1.0, 0.0, mode=_lib.MODE_FAST, device=device)
+    base = dict(config=key, name=case.name, nodes=N, elements=E, steps=steps, library=_lib.LIB_PATH,
+                kernel=(_lib.load().cwf_hip_system_keff_kernel(sysm.handle()) or b"").decode())
+    ex = ExplicitStepper(P, case.materials, RayleighCoefficients(0.0, 0.0), system=sysm)
+    base["dt"] = ex.telemetry().dt
+    runs = [timed_steps(ex, steps) for _ in range(repeats)]
+    plain = statistics.median(runs)
+    lines = [dict(base, configuration="plain", step_us=plain, step_us_runs=runs,
+                  spread=(max(runs) - min(runs)) / plain)]
+    ceiling = 6.25e12
+    for label, sy in (() if plain_only else (("elastic", 1e30), ("yielding", 1.0))):
+        if only and label != only:
+            continue
+        ex.set_state(ExplicitStepper.DISPLACEMENT, torch.zeros(P.dof_count, device=f"cuda:{device}"))
+        ex.set_state(ExplicitStepper.VELOCITY, torch.zeros(P.dof_count, device=f"cuda:{device}"))
+        ex.set_plasticity(sy, 0.1 * case.cfg.materials[0].youngs_modulus)
+        us = timed_steps(ex, steps)
+        i = ex.plasticity_info()
+        b = i.plastic_elements * (64 + 4 + 4 + 4 + 64 + 16 + 48) + N * (12 + 8 + 12 + 12)
+        hi = b + (48 + 64) * i.yielded_elements  # every yielded element storing its forces and its state every step
+        lines.append(dict(base, configuration=label, yield_stress=sy, step_us=us, plastic_elements=i.plastic_elements,
+                          affected_nodes=i.affected_nodes, yielded_elements=i.yielded_elements, device_bytes=i.bytes,
+                          added_us=us - plain, bytes_low=b, bytes_high=hi, estimate_us_low=1e6 * b / ceiling,
+                          estimate_us_high=1e6 * hi / ceiling))
+        ex.clear_plasticity()
+    ex.close()
+    sysm.close()
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", nargs="+", default=["c2", "c3", "c2:hex8"])
@@ -332,20 +382,31 @@ def main():
     ap.add_argument("--monitors", action="store_true", help="the cost of the monitors (see above)")
     ap.add_argument("--sources", action="store_true", help="the cost of load sources (see above)")
     ap.add_argument("--envelopes", action="store_true", help="the cost of the element monitors (see above)")
+    ap.add_argument("--plasticity", action="store_true", help="the cost of J2 plasticity (see above)")
+    ap.add_argument("--plain-only", action="store_true", help="--plasticity: the plain step alone")
+    ap.add_argument("--repeats", type=int, default=5, help="--plasticity: timings of the plain step")
+    ap.add_argument("--only", choices=["elastic", "yielding"], default=None,
+                    help="--plasticity: that configuration alone after the plain step (profiler runs)")
     ap.add_argument("--out", default=None, help="default profiles/explicit_c2.json (--envelopes: "
                                                  "profiles/explicit_envelopes.json, --absorbing: "
                                                  "profiles/explicit_absorbing.json, --monitors: "
                                                  "profiles/explicit_monitors.json, --sources: "
                                                  "profiles/explicit_sources.json)")
     a = ap.parse_args()
-    a.out = a.out or os.path.join(ROOT, "profiles", "explicit_envelopes.json" if a.envelopes else
+    a.out = a.out or os.path.join(ROOT, "profiles", "explicit_plasticity.json" if a.plasticity else
+                                  "explicit_envelopes.json" if a.envelopes else
                                   "explicit_sources.json" if a.sources else
                                   "explicit_monitors.json" if a.monitors else
                                   "explicit_absorbing.json" if a.absorbing else "explicit_c2.json")
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     if a.configs == ap.get_default("configs") and not a.envelopes:
-        a.configs = ["c2", "c3"] if a.monitors or a.sources else ["c3"] if a.absorbing else a.configs
-    for key in a.configs:
+        a.configs = ["c2", "c3"] if a.monitors or a.sources or a.plasticity else ["c3"] if a.absorbing else a.configs
+    for key in a.configs if a.plasticity else []:
+        for d in measure_plasticity(key, a.steps, a.device, a.repeats, a.plain_only, a.only):
+            print(json.dumps(d), flush=True)
+            with open(a.out, "a") as f:
+                f.write(json.dumps(d) + "\n")
+    for key in [] if a.plasticity else a.configs:
         line = json.dumps(measure_envelopes(key, a.steps, a.device) if a.envelopes else
                           measure_sources(key, a.steps, a.device) if a.sources else
                           measure_monitors(key, a.steps, a.device) if a.monitors else
