@@ -1,5 +1,6 @@
 // abi_internal.hpp -- what the C-ABI translation units (abi.cpp: handles, abi_pcg.cpp: apply_keff / block
-// Jacobi / dot / solve_pcg, abi_stepper.cpp: the Stepper, abi_explicit.cpp: the explicit stepper, comm.cpp, modal.cpp,
+// Jacobi / dot / solve_pcg, abi_stepper.cpp: the Stepper, abi_explicit.cpp and abi_explicit_{loads,monitors,
+// plasticity}.cpp: the explicit stepper (explicit_state.hpp is what those four share), comm.cpp, modal.cpp,
 // refine.cpp) share: the HIP error macro, device allocation and upload from the handle's arena (devmem.hpp: dalloc,
 // upload, Uploader), the operator apply by the handle's mode (keff_apply, keff_apply_ds, stiffness_only), the scope
 // guard of the operator scalars (ScalarScope), vector staging between the caller's layout and the handle's, the PCG
@@ -274,7 +275,7 @@ int transient_set(TransientState &c, const char *what, float *dst, const float *
 int transient_set_load_pattern(TransientState &c, const double *base, const double *pattern, uint64_t n);
 int transient_time(double now, double dt, double *current_time, double *time_step);
 
-// abi_explicit.cpp: what cwf_hip_explicit_set_element_monitors refuses of a desc for a handle of E elements, on the
+// abi_explicit_monitors.cpp: what cwf_hip_explicit_set_element_monitors refuses of a desc for a handle of E elements, on the
 // host alone (no device, no handle): 0, or the error code with the message in *msg and its context lines in *ctx
 int element_monitor_refusal(const cwf_explicit_element_monitor_desc &d, uint64_t E, std::string *msg,
                             std::string *ctx);

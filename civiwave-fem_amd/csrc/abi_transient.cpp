@@ -1,5 +1,5 @@
 // abi_transient.cpp -- the state core the Newmark stepper (abi_stepper.cpp) and the explicit stepper
-// (abi_explicit.cpp) share (TransientState, abi_internal.hpp): the create tail, state and external force in and out
+// (explicit_state.hpp, abi_explicit*.cpp) share (TransientState, abi_internal.hpp): the create tail, state and external force in and out
 // of the handle's node order, the fp64 load pattern, the time getter. Each C entry point checks its own handle for
 // NULL, maps `which` to a pointer of its own and calls in here; a NULL pointer from that table is an unknown field.
 #include "abi_internal.hpp"

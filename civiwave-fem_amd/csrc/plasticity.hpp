@@ -1,7 +1,7 @@
 // plasticity.hpp -- the element update of the explicit stepper's J2 plasticity (include/cwf_hip.h "Plasticity"): one
 // inline function for the device pass (post.hip k_explicit_plastic_elements) and the host-only ABI function
-// cwf_explicit_j2_update (abi_explicit.cpp). Both translation units are built with -ffp-contract=off and IEEE fp64
-// division and square root, so the two give the same bits; the statement order is the header's.
+// cwf_explicit_j2_update (abi_explicit_plasticity.cpp). Both translation units are built with -ffp-contract=off and
+// IEEE fp64 division and square root, so the two give the same bits; the statement order is the header's.
 #pragma once
 
 #include <hip/hip_runtime.h>
