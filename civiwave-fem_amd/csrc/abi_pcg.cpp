@@ -31,7 +31,7 @@ std::string pcg_error_message(int code, int iter, PcgSchedule sch, std::string *
     *ctx = "iteration=" + std::to_string(iter);
     if (code == CWF_ERR_DENOM_ZERO)
         return "CG denominator approached zero";  // pcg.cpp:846-849
-    if (code == CWF_ERR_HIP)  // kernels_parity.hip stream_fail: the chunk partials of a streamed fold never all arrived
+    if (code == CWF_ERR_HIP)  // parity_pcg.hip stream_fail: the chunk partials of a streamed fold never all arrived
         return "PARITY streamed scalar fold timed out";
     return "CG rho approached zero";  // pcg.cpp:889-892
 }
@@ -99,7 +99,7 @@ int pcg_init(PcgSchedule sch, const std::vector<cwf_hip_system *> &g, const std:
     case PcgSchedule::TwoKernel:
         return sharded ? sharded_pcg_init(g, rhs, tol) : (fast_pcg_init(h, rhs[0], tol, h->stream), 0);
     case PcgSchedule::Parity:
-        return sharded ? sharded_parity_init(g, rhs, tol) : (parity_pcg_init(h, rhs[0], tol, h->stream), 0);
+        return parity_pcg_init_group(g, rhs, tol);
     }
     return 0;
 }
@@ -118,7 +118,7 @@ int pcg_iteration(PcgSchedule sch, const std::vector<cwf_hip_system *> &g, const
     case PcgSchedule::TwoKernel:
         return fast_pcg_iteration_group(g, rhs, it, e0, e1);
     case PcgSchedule::Parity:
-        return sharded ? sharded_parity_iteration(g, rhs, e0, e1) : (parity_pcg_iteration(h, rhs[0], h->stream, e0, e1), 0);
+        return parity_pcg_iteration_group(g, rhs, e0, e1);
     case PcgSchedule::Resident:  // (no launch per iteration)
         break;
     }
@@ -445,7 +445,8 @@ int cwf_hip_dot(cwf_hip_system *h, const float *a, const float *b, uint64_t n, i
     else
     {
         count = parity_chunk_count(h);
-        parity_dot_partials(h, da, db, nullptr, h->part0, nullptr, nullptr, h->stream);
+        parity_dot_partials(h->ds.D, (uint32_t)h->reduction_block, da, db, nullptr, h->part0, nullptr, nullptr,
+                            h->stream);
         parity_fold(h->part0, count, res, h->stream);
     }
     HIPTRY(h, hipGetLastError());

@@ -212,11 +212,12 @@ int comm_halo(const std::vector<cwf_hip_system *> &g, float *cwf_hip_system::*ve
     return comm_exchange(g, {}, vec);
 }
 
-// solve_pcg prologue (pcg.cpp:744-828) for a sharded system: owned-row dots, gathered scalars, halos
-int sharded_pcg_init(const std::vector<cwf_hip_system *> &g, const std::vector<const float *> &rhs, double rel_tol)
+namespace
 {
-    for (cwf_hip_system *h : g)
-        fast_block_inverse(h, h->stream);
+// what every sharded FAST prologue starts with, after its block inverse: ghost x, r_0, the owned rows' |rhs|^2 and
+// |r_0|^2 gathered from every rank, and the tolerance
+int sharded_fast_residual(const std::vector<cwf_hip_system *> &g, const std::vector<const float *> &rhs, double rel_tol)
+{
     if (int st = comm_halo(g, &cwf_hip_system::x))  // warm start: ghost x from the owners
         return st;
     for (size_t i = 0; i < g.size(); ++i)
@@ -232,10 +233,20 @@ int sharded_pcg_init(const std::vector<cwf_hip_system *> &g, const std::vector<c
     if (int st = comm_allgather(g, &cwf_hip_system::g_init, 2))
         return st;
     for (cwf_hip_system *h : g)
-    {
         fast_init_scalars_strided(h, h->g_init, h->g_init + 1, (uint32_t)h->nranks, 2u, rel_tol, h->stream);
+    return 0;
+}
+}  // namespace
+
+// solve_pcg prologue (pcg.cpp:744-828) for a sharded system: owned-row dots, gathered scalars, halos
+int sharded_pcg_init(const std::vector<cwf_hip_system *> &g, const std::vector<const float *> &rhs, double rel_tol)
+{
+    for (cwf_hip_system *h : g)
+        fast_block_inverse(h, h->stream);
+    if (int st = sharded_fast_residual(g, rhs, rel_tol))
+        return st;
+    for (cwf_hip_system *h : g)
         launch_precond(h, h->ctl, h->stream);
-    }
     if (int st = comm_halo(g, &cwf_hip_system::z))
         return st;
     for (cwf_hip_system *h : g)
@@ -335,22 +346,8 @@ int sharded_fused_prologue(const std::vector<cwf_hip_system *> &g, const std::ve
             h->cls_global = true;
         }
     }
-    if (int st = comm_halo(g, &cwf_hip_system::x))  // warm start: ghost x from the owners
+    if (int st = sharded_fast_residual(g, rhs, rel_tol))
         return st;
-    for (size_t i = 0; i < g.size(); ++i)
-    {
-        cwf_hip_system *h = g[i];
-        const uint32_t Down = 3u * h->ds.Nown;
-        fast_keff(h, h->x, h->Ap, true, nullptr, nullptr, h->stream);
-        launch_init_residual(h, rhs[i], h->stream);
-        fast_dot(rhs[i], rhs[i], nullptr, Down, h->part0, nullptr, h->stream);
-        fast_dot(h->r, h->r, nullptr, Down, h->part1, nullptr, h->stream);
-        fold_pair(h->part0, h->part1, fast_dot_blocks(Down), h->g_init + 2 * h->rank, h->stream);
-    }
-    if (int st = comm_allgather(g, &cwf_hip_system::g_init, 2))
-        return st;
-    for (cwf_hip_system *h : g)
-        fast_init_scalars_strided(h, h->g_init, h->g_init + 1, (uint32_t)h->nranks, 2u, rel_tol, h->stream);
     return comm_halo(g, &cwf_hip_system::r);
 }
 }  // namespace
@@ -398,9 +395,9 @@ int sharded_fused_end(const std::vector<cwf_hip_system *> &g, PcgSchedule sch)
 // element order, bitwise the single-handle rows. Ghost rows of x / r / z are never read; p is refreshed on the
 // ghosts by one halo after each p update. So every scalar, the residual history and every owned vector entry
 // equal the single-handle PARITY solve bit for bit.
-namespace
-{
-int parity_setup(const std::vector<cwf_hip_system *> &g)
+// The schedule itself is parity_pcg.hip's, the single handle's with the exchanges in between; here, what it needs
+// of the ranks before the first phase: the layout checked, and every rank's slot block.
+int sharded_parity_setup(const std::vector<cwf_hip_system *> &g)
 {
     cwf_hip_system *h0 = g[0];
     const int n = h0->nranks;
@@ -453,84 +450,6 @@ int parity_setup(const std::vector<cwf_hip_system *> &g)
         h->pstride = (uint32_t)stride;
     }
     return 0;
-}
-
-inline uint32_t owned_dofs(const cwf_hip_system *h) { return 3u * h->ds.Nown; }
-inline uint32_t block_of(const cwf_hip_system *h) { return (uint32_t)(h->reduction_block ? h->reduction_block : 1); }
-}  // namespace
-
-int sharded_parity_init(const std::vector<cwf_hip_system *> &g, const std::vector<const float *> &rhs, double rel_tol)
-{
-    if (int st = parity_setup(g))
-        return st;
-    const uint32_t S = g[0]->pstride, total = (uint32_t)g[0]->nranks * S;
-    for (cwf_hip_system *h : g)
-    {
-        parity_block_jacobi(h, h->inv, h->stream);
-        h->inv_fast = false;
-    }
-    if (int st = comm_halo(g, &cwf_hip_system::x))  // warm start: ghost x from the owners
-        return st;
-    for (size_t i = 0; i < g.size(); ++i)
-    {
-        cwf_hip_system *h = g[i];
-        const size_t slot = (size_t)h->rank * S;
-        parity_keff(h, h->x, h->Ap, true, nullptr, h->stream);
-        launch_init_residual(h, rhs[i], h->stream);
-        parity_dot_partials_n(owned_dofs(h), block_of(h), rhs[i], rhs[i], nullptr, h->gp0 + slot, nullptr, nullptr,
-                              h->stream);
-        parity_dot_partials_n(owned_dofs(h), block_of(h), h->r, h->r, nullptr, h->gp1 + slot, nullptr, nullptr,
-                              h->stream);
-    }
-    if (int st = comm_exchange(g, {Gather{&cwf_hip_system::gp0, S}, Gather{&cwf_hip_system::gp1, S}}, nullptr))
-        return st;
-    for (cwf_hip_system *h : g)
-    {
-        parity_init_scalars(h, h->gp0, h->gp1, total, rel_tol, h->stream);
-        launch_precond(h, h->ctl, h->stream);
-        parity_dot_partials_n(owned_dofs(h), block_of(h), h->r, h->z, nullptr, h->gp0 + (size_t)h->rank * S, nullptr,
-                              h->ctl, h->stream);
-    }
-    if (int st = comm_allgather(g, &cwf_hip_system::gp0, S))
-        return st;
-    for (cwf_hip_system *h : g)
-    {
-        parity_init_rho(h, h->gp0, total, h->stream);
-        launch_p_init(h, h->stream);
-    }
-    return comm_halo(g, &cwf_hip_system::p);
-}
-
-int sharded_parity_iteration(const std::vector<cwf_hip_system *> &g, const std::vector<const float *> &rhs,
-                             hipEvent_t e0, hipEvent_t e1)
-{
-    const uint32_t S = g[0]->pstride, total = (uint32_t)g[0]->nranks * S;
-    for (size_t i = 0; i < g.size(); ++i)
-    {
-        cwf_hip_system *h = g[i];
-        if (i == 0 && e0)
-            (void)hipEventRecord(e0, h->stream);
-        parity_keff_dot(h, h->p, h->Ap, h->ctl, h->gp0 + (size_t)h->rank * S, h->stream);
-        if (i == 0 && e1)
-            (void)hipEventRecord(e1, h->stream);
-    }
-    if (int st = comm_allgather(g, &cwf_hip_system::gp0, S))
-        return st;
-    for (size_t i = 0; i < g.size(); ++i)
-    {
-        cwf_hip_system *h = g[i];
-        const size_t slot = (size_t)h->rank * S;
-        parity_alpha(h, h->gp0, total, h->stream);
-        parity_update(h, rhs[i], h->gp0 + slot, h->gp1 + slot, h->stream);
-    }
-    if (int st = comm_exchange(g, {Gather{&cwf_hip_system::gp0, S}, Gather{&cwf_hip_system::gp1, S}}, nullptr))
-        return st;
-    for (cwf_hip_system *h : g)
-    {
-        parity_beta(h, h->gp0, h->gp1, total, h->stream);
-        parity_p_update(h, h->stream);
-    }
-    return comm_halo(g, &cwf_hip_system::p);
 }
 
 }  // namespace cwf
@@ -745,7 +664,7 @@ int cwf_hip_system_attach(cwf_hip_system *h, cwf_hip_comm *cm, int32_t rank, con
     h->gbegin = plan->owned_nodes && plan->node_global ? plan->node_global[0] : 0;
     if (plan->node_global)
         h->node_gid.assign(plan->node_global, plan->node_global + plan->local_nodes);
-    h->owned_contiguous = true;  // PARITY shards fold chunk partials in global order (comm.cpp parity_setup)
+    h->owned_contiguous = true;  // PARITY shards fold chunk partials in global order (sharded_parity_setup)
     if (plan->node_global)
         for (uint64_t i = 1; i < plan->owned_nodes; ++i)
             if (plan->node_global[i] != h->gbegin + i)

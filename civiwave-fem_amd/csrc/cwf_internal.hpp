@@ -287,7 +287,7 @@ struct DevSys
     const uint32_t *mask = nullptr;
     const uint32_t *off = nullptr;
     const uint32_t *inc = nullptr;
-    // node-tile PARITY K_eff (kernels_parity.hip k_keff_parity_tile; built at the first PARITY use): tile b = nodes
+    // node-tile PARITY K_eff (parity_keff.hip k_keff_parity_tile; built at the first PARITY use): tile b = nodes
     // [256 b, 256 b + 256); ptile_tets[ptile_off[b] ..] its incident tets, ascending; pinc[j] = (the tile-local index
     // of incidence j's tet) << 2 | corner, for every incidence j of the node -> incidence CSR (off / inc order)
     const uint32_t *ptile_off = nullptr;
@@ -422,7 +422,7 @@ struct cwf_hip_system
     bool inv_fast = false;
     double inv_sK = 0.0, inv_sM = 0.0;
     double *part0 = nullptr, *part1 = nullptr, *part2 = nullptr;  // chunk / block partials
-    // PARITY streamed scalar folds (kernels_parity.hip, single handle, 256-DOF chunks): tagged 16-B chunk-partial
+    // PARITY streamed scalar folds (parity_pcg.hip, single handle, 256-DOF chunks): tagged 16-B chunk-partial
     // granules [2 chunks] (null: the separate fold kernels) and the tag of the last streamed launch
     double *fgran = nullptr;
     uint32_t fgran_tag = 0;
@@ -511,35 +511,30 @@ namespace cwf
 int set_error(cwf_hip_system *h, int code, const std::string &msg, const std::string &ctx = "");
 int hip_fail(cwf_hip_system *h, hipError_t e, const char *what);
 
-// ---- kernels_parity.hip ----
-uint32_t parity_chunk_count(const cwf_hip_system *h);
+// ---- parity_keff.hip ----
 void parity_keff(const cwf_hip_system *h, const float *x, float *y, bool sanitize, const Ctl *ctl, hipStream_t st);
 void parity_keff_ds(const DevSys &s, const float *x, float *y, bool sanitize, const Ctl *ctl, hipStream_t st);
 void parity_block_jacobi(const cwf_hip_system *h, float *inv, hipStream_t st);
 void hex_block_jacobi(const cwf_hip_system *h, float *inv, hipStream_t st);  // hex8 diagonal blocks -> inverse
-void parity_dot_partials(const cwf_hip_system *h, const float *a, const float *b, const float *c, double *pab,
-                         double *pac, const Ctl *ctl, hipStream_t st);
-void parity_dot_partials_n(uint32_t D, uint32_t B, const float *a, const float *b, const float *c, double *pab,
-                           double *pac, const Ctl *ctl, hipStream_t st);
-void parity_fold(const double *part, uint32_t count, double *out, hipStream_t st);
-void parity_init_scalars(cwf_hip_system *h, const double *p_rhs, const double *p_rr, uint32_t count, double rel_tol,
-                         hipStream_t st);
-void parity_init_rho(cwf_hip_system *h, const double *p_rz, uint32_t count, hipStream_t st);
-void parity_alpha(cwf_hip_system *h, const double *p_pap, uint32_t count, hipStream_t st);
-void parity_update(cwf_hip_system *h, const float *rhs, double *prr, double *prz, hipStream_t st);
-// the PCG loop's K_eff p and the chunk partials of p . Ap over the owned nodes (fused for 256-DOF chunks); and
-// parity_update's r . r / r . z partials likewise
+// the PCG loop's K_eff p and the chunk partials of p . Ap over the owned nodes (fused for 256-DOF chunks)
 void parity_keff_dot(const cwf_hip_system *h, const float *p, float *Ap, const Ctl *ctl, double *pdot, hipStream_t st);
 // cwf_hip_system_keff_kernel's answers: the PCG loop's instantiation as the family's picker names it (keff_pick.hpp)
 const char *parity_keff_kernel_name(const cwf_hip_system *h, bool compact);
 const char *fast_tiles_kernel_name(const DevSys &s);
 const char *pcg_lattice_kernel_name(const DevSys &s, unsigned grid);
 const char *resident_kernel_name(const DevSys &s, const ResidentPlan &rp);
-void parity_beta(cwf_hip_system *h, const double *p_rr, const double *p_rz, uint32_t count, hipStream_t st);
-void parity_p_update(cwf_hip_system *h, hipStream_t st);
-void parity_pcg_init(cwf_hip_system *h, const float *rhs, double rel_tol, hipStream_t st);
-void parity_pcg_iteration(cwf_hip_system *h, const float *rhs, hipStream_t st, hipEvent_t e0 = nullptr,
-                          hipEvent_t e1 = nullptr);
+
+// ---- parity_pcg.hip ----
+uint32_t parity_chunk_count(const cwf_hip_system *h);
+void parity_dot_partials(uint32_t D, uint32_t B, const float *a, const float *b, const float *c, double *pab,
+                         double *pac, const Ctl *ctl, hipStream_t st);
+void parity_fold(const double *part, uint32_t count, double *out, hipStream_t st);
+// the PARITY prologue and iteration of a shard's group, or of a single handle as the group {h}
+int parity_pcg_init_group(const std::vector<cwf_hip_system *> &g, const std::vector<const float *> &rhs,
+                          double rel_tol);
+int parity_pcg_iteration_group(const std::vector<cwf_hip_system *> &g, const std::vector<const float *> &rhs,
+                               hipEvent_t e0, hipEvent_t e1);
+// r_0, z = M^-1 r and p_0 = z on the handle's vectors (the FAST prologues run them too: pure f32 node passes)
 void launch_init_residual(const cwf_hip_system *h, const float *rhs, hipStream_t st);
 void launch_precond(const cwf_hip_system *h, const Ctl *ctl, hipStream_t st);
 void launch_p_init(const cwf_hip_system *h, hipStream_t st);
@@ -763,9 +758,8 @@ int comm_exchange_vecs(const std::vector<cwf_hip_system *> &g, std::initializer_
 int comm_allgather(const std::vector<cwf_hip_system *> &g, double *cwf_hip_system::*buf, size_t count);
 int comm_halo(const std::vector<cwf_hip_system *> &g, float *cwf_hip_system::*vec);
 int sharded_pcg_init(const std::vector<cwf_hip_system *> &g, const std::vector<const float *> &rhs, double rel_tol);
-int sharded_parity_init(const std::vector<cwf_hip_system *> &g, const std::vector<const float *> &rhs, double rel_tol);
-int sharded_parity_iteration(const std::vector<cwf_hip_system *> &g, const std::vector<const float *> &rhs,
-                             hipEvent_t e0, hipEvent_t e1);
+// sharded PARITY's slot blocks gp0 / gp1 (pstride entries per rank), after checking the ranks' owned ranges
+int sharded_parity_setup(const std::vector<cwf_hip_system *> &g);
 int fast_pcg_iteration_group(const std::vector<cwf_hip_system *> &g, const std::vector<const float *> &rhs,
                              unsigned it, hipEvent_t e0, hipEvent_t e1);
 

@@ -1,4 +1,4 @@
-// keff_pick.hpp -- how the K_eff / PCG kernel translation units (the FAST units, resident.hip, kernels_parity.hip) pick
+// keff_pick.hpp -- how the K_eff / PCG kernel translation units (the FAST units, resident.hip, parity_keff.hip) pick
 // a template instantiation. Each kernel family has one picker next to its kernels: a pure function of the handle's facts
 // (no HIP call) that returns a Pick. The launch, the occupancy / grid / LDS queries and cwf_hip_system_keff_kernel all
 // take the instantiation from it, so the reported name is the launched kernel's.

@@ -2,7 +2,7 @@
 //
 // Per element (derived_fields.cpp:157-186): strain from grad(N) . u in fp64 (the reference's
 // per-corner statement order, shear pairs summed before they are added), stress = D strain as the
-// full row fold (structural zeros of an isotropic D skipped, exact -- see kernels_parity.hip),
+// full row fold (structural zeros of an isotropic D skipped, exact -- see parity_common.hpp),
 // von Mises from the fp64 stress, all stored as f32 {strain[6], stress[6], vm} (the 52-B layout of
 // cwf::post::ElementField).
 // Per node (derived_fields.cpp:188-210): the reference scatters V*strain, V*stress and V into fp64

@@ -5,7 +5,7 @@
 // The operator is the reference's (pcg.cpp:505-694), the one k_keff_parity_tile applies: fp64 element math on the f32
 // records widened, the reference's operand order (this file is built with -ffp-contract=off like that one), each
 // node's incident corner forces added in ascending element order from +0.0, then the mass term. Only the vectors
-// differ: x is read as fp64 and nothing is cast to f32. The element helpers below restate kernels_parity.hip's
+// differ: x is read as fp64 and nothing is cast to f32. The element helpers below restate parity_keff.hip's
 // instead of being shared with it: that file's kernels are the bit-exact yardstick, and sharing a __device__ function
 // between instantiations has moved register allocation before (the lattice kernels, DESIGN.md section 3 "Layered
 // blocks"). Their resource usage is unchanged by this file (profiles/refine_kernel_resources.txt).

@@ -125,7 +125,7 @@ def _gather_fold(dist, torch, world, parts):
 
 
 def run_rank_parity(rank, world, port, out_dir, shape=(15, 15, 2), rel_tol=1e-6, max_iterations=400):
-    """The sharded PARITY schedule of csrc/comm.cpp (sharded_parity_*) restated in numpy on the oracle: owned
+    """The sharded PARITY schedule of csrc/parity_pcg.hip (parity_pcg_*_group) restated in numpy on the oracle: owned
     ranges aligned to 256 nodes (a 15 x 15 cross-section is 256 nodes per plane), owned K_eff / block-Jacobi
     rows from the rank's local oracle system, 256-DOF chunk partials of the owned rows all-gathered and folded
     in global chunk order, p refreshed on the ghosts after every p update. Every scalar rounds as pcg.cpp does,

@@ -75,7 +75,7 @@ def test_c2_parity_pcg_25_iterations_bitwise(c2):
 
 def test_c2_parity_streamed_folds_match_fold_kernels(c2, monkeypatch):
     """The default single-handle PARITY loop folds alpha and beta in workgroup 0 of the passes that produce the chunk
-    partials (tagged granules polled while the other workgroups produce: kernels_parity.hip fold_stream); the
+    partials (tagged granules polled while the other workgroups produce: parity_pcg.hip fold_stream); the
     CWF_PARITY_STREAM=0 loop runs the separate fold kernels. Both must give the same bits over a whole solve to
     convergence (the 25-iteration test above pins the default against the oracle): x, r, history, telemetry."""
     rhs = c2.static_rhs()

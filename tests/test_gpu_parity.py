@@ -119,6 +119,39 @@ def test_solve_pcg_bitwise_with_reduction_block_100():
     assert np.array_equal(pcg.residual_history(s), ref["history"])
 
 
+@pytest.fixture(scope="module")
+def jitter_solve():
+    case = CASES["jitter"]()
+    rhs = case.static_rhs()
+    ref = oracle_system(case.packing, case.materials, *case.scalars()).solve_pcg(rhs, 600, 1e-6, history=True)
+    return case, rhs, ref
+
+
+@pytest.mark.parametrize("knob", [None, ("CWF_PARITY_STREAM", "0"), ("CWF_PARITY_TILES", "strip")],
+                         ids=["streamed", "stream_off", "strip_tiles"])
+def test_solve_pcg_bitwise_on_every_256_dof_loop_of_a_single_handle(jitter_solve, knob, monkeypatch):
+    """The three 256-DOF loops one unsharded handle can run, each on a fresh handle and against the oracle: the
+    default (compact tiles, alpha and beta folded inside the streamed passes), CWF_PARITY_STREAM=0 (compact tiles,
+    a separate p . Ap partials pass, k_pcg_alpha / k_pcg_beta) and CWF_PARITY_TILES=strip (strip tiles, the p . Ap
+    partials fused into the K_eff pass, the fold kernels). 336 nodes, 1,008 DOFs: four reduction chunks, two node
+    tiles. (The loop of another chunk size: the reduction_block=100 test above.)"""
+    case, rhs, ref = jitter_solve
+    for name in ("CWF_PARITY_STREAM", "CWF_PARITY_TILES"):
+        monkeypatch.delenv(name, raising=False)
+    if knob:
+        monkeypatch.setenv(*knob)
+    s = gpu_system(case)
+    x, r = np.zeros_like(rhs), np.zeros_like(rhs)
+    t = pcg.solve_pcg(s, rhs, pcg.PcgSettings(600, 1e-6), pcg.PcgVectors(x, r)).value()
+    rt = ref["telemetry"]
+    assert (t.iterations, t.converged) == (rt.iterations, bool(rt.converged))
+    assert (t.residual_norm, t.alpha_last, t.beta_last) == (rt.residual_norm, rt.alpha_last, rt.beta_last)
+    assert_bitwise(x, ref["x"], "x")
+    assert_bitwise(r, ref["r"], "r")
+    assert np.array_equal(pcg.residual_history(s), ref["history"])
+    s.close()
+
+
 def test_solve_pcg_warm_start_bitwise(case):
     s = gpu_system(case)
     o = oracle_system(case.packing, case.materials, *case.scalars())

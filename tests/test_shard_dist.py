@@ -42,7 +42,7 @@ def test_gloo_sharded_pcg_matches_oracle(tmp_path, world):
 def test_gloo_sharded_parity_schedule_is_bitwise_the_single_solve(tmp_path):
     """The PARITY gate of SURVEY.md 8e on two processes: chunk partials of 256-node-aligned owned ranges,
     all-gathered and folded in global chunk order, give x, r and the fp64 residual history of the one-process
-    oracle solve bit for bit (dist_worker.run_rank_parity restates csrc/comm.cpp sharded_parity_*)."""
+    oracle solve bit for bit (dist_worker.run_rank_parity restates csrc/parity_pcg.hip parity_pcg_*_group)."""
     world, shape = 2, (15, 15, 2)
     mp.spawn(dist_worker.run_rank_parity, args=(world, _port(), str(tmp_path), shape), nprocs=world, join=True)
     glob = scenarios.block_case(shape[0], shape[1], shape[2] * world, h=0.1)
