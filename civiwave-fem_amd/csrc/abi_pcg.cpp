@@ -126,15 +126,16 @@ int pcg_iteration(PcgSchedule sch, const std::vector<cwf_hip_system *> &g, const
 }
 
 // after a batch (`it` iterations enqueued in all): the convergence of its last launch (Fused) or last update
-// (TwoKernel), repeated idempotently by the next launch's start. PARITY decides in its own kernels
-void pcg_batch_check(PcgSchedule sch, const std::vector<cwf_hip_system *> &g, unsigned it)
+// (TwoKernel), repeated idempotently by the next launch's start. PARITY decides in its own kernels. last: `it` is the
+// solve's max_iterations (the fused check then leaves alpha_last and beta_last those of the last update made)
+void pcg_batch_check(PcgSchedule sch, const std::vector<cwf_hip_system *> &g, unsigned it, bool last)
 {
     switch (sch)
     {
     case PcgSchedule::Fused:
     case PcgSchedule::FusedPeer:
         for (cwf_hip_system *m : g)
-            fast_fused_check(m, it, m->stream);
+            fast_fused_check(m, it, m->stream, last);
         break;
     case PcgSchedule::TwoKernel:
         for (cwf_hip_system *m : g)
@@ -292,7 +293,7 @@ int run_pcg_group(const std::vector<cwf_hip_system *> &g, const std::vector<cons
             if (int e = pcg_iteration(sch, g, rhs, (unsigned)(enq + i), e0, e1))
                 return e;
         }
-        pcg_batch_check(sch, g, (unsigned)(enq + nb));
+        pcg_batch_check(sch, g, (unsigned)(enq + nb), enq + nb >= set.max_iterations);
         HIPTRY(h, hipGetLastError());
         prev_enq = enq;
         prev_nb = nb;

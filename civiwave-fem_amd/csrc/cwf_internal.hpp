@@ -565,7 +565,7 @@ unsigned pcg_lattice_launch_grid(const DevSys &s, unsigned cap);  // its grid, o
 void fast_fused_init(cwf_hip_system *h, const float *rhs, double rel_tol, hipStream_t st, bool launch0 = true);
 void fast_fused_iteration(cwf_hip_system *h, unsigned it, hipStream_t st, hipEvent_t e0 = nullptr,
                           hipEvent_t e1 = nullptr);
-void fast_fused_check(cwf_hip_system *h, unsigned it, hipStream_t st);
+void fast_fused_check(cwf_hip_system *h, unsigned it, hipStream_t st, bool last);
 void fast_fused_finish(cwf_hip_system *h, hipStream_t st);
 void fast_fused_launch0(cwf_hip_system *h, hipStream_t st);
 float *fast_fused_ap(cwf_hip_system *h, unsigned j);

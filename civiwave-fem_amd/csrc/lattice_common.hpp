@@ -126,8 +126,12 @@ enum
 // pcg.cpp:840-895 from the folded shares v of the launch (or resident phase) before j: alpha_(j-1), beta_j and the
 // convergence of r_(j-1); the one thread of the grid the caller names as `writer` records them (and the history).
 // Every caller holds the same v, so every workgroup takes the same decision. Returns false when the solve is over.
+// last: max_iterations updates are made, so no update follows this decision; alpha_last and beta_last then stay those
+// of update j - 1 (pcg.cpp's telemetry: the alpha of the last update made and the beta formed after it), not the
+// scalars of an update that never runs.
 __device__ __forceinline__ bool fused_decide(Ctl *ctl, double *hist, unsigned j, const CtlPre &pre, bool writer,
-                                             const double v[kFusedShares], float *alpha_out, float *beta_out)
+                                             const double v[kFusedShares], float *alpha_out, float *beta_out,
+                                             bool last)
 {
     const unsigned it = j - 1u;  // the completed updates r_(j-1) carries (launch 0 made none)
     const double res = sqrt(v[kFRR]);
@@ -168,10 +172,13 @@ __device__ __forceinline__ bool fused_decide(Ctl *ctl, double *hist, unsigned j,
         else
         {
             ctl->alpha = alpha;
-            ctl->alpha_last = alpha;
             ctl->rho2[it & 1u] = rho;
             ctl->beta = beta;
-            ctl->beta_last = beta;
+            if (!last)
+            {
+                ctl->alpha_last = alpha;
+                ctl->beta_last = beta;
+            }
         }
     }
     *alpha_out = (float)alpha;

@@ -49,6 +49,7 @@ struct FusedArgs
     double *sout;       // this launch's shares, [kFusedShares][sstride]
     unsigned sstride;
     unsigned j;  // launch index; 0: the prologue's (alpha = beta = 0: r_0, z_0, p_0 = z_0, Ap_0)
+    unsigned last;  // the solve's last check: max_iterations updates are made, no update follows (fused_decide)
     unsigned grid;  // workgroups (host side: the launch's grid; <= the work items, a multiple of 8 below them)
     double *hist;
     const float *rin;
@@ -185,7 +186,8 @@ __device__ __forceinline__ bool fused_scalars(const FusedArgs &fa, const CtlPre 
     fold_k<NT, kFusedShares>(fa.sin, fa.nin, fa.sin_stride, red, v, fa.sis);
     if (!pre.active)
         return false;
-    return fused_decide(fa.ctl, fa.hist, fa.j, pre, blockIdx.x == 0 && threadIdx.x == 0, v, alpha_out, beta_out);
+    return fused_decide(fa.ctl, fa.hist, fa.j, pre, blockIdx.x == 0 && threadIdx.x == 0, v, alpha_out, beta_out,
+                        fa.last != 0u);
 }
 
 // one LDS entry's raw values: r, Ap, p_old of iteration j - 1 and the class byte; the own column's entry also x
@@ -1039,10 +1041,13 @@ const double *fast_fused_shares(const cwf_hip_system *h, unsigned j, unsigned *s
     return h->fsh + (size_t)(j & 1u) * 5 * h->ds.t.lnwork;
 }
 
-// the convergence of the batch's last launch (it iterations enqueued: launch it's r)
-void fast_fused_check(cwf_hip_system *h, unsigned it, hipStream_t st)
+// the convergence of the batch's last launch (it iterations enqueued: launch it's r); last: it is the solve's
+// max_iterations, so no launch follows
+void fast_fused_check(cwf_hip_system *h, unsigned it, hipStream_t st, bool last)
 {
-    k_fused_check<<<1, 256, 0, st>>>(fused_args(h, it + 1u));
+    FusedArgs fa = fused_args(h, it + 1u);
+    fa.last = last ? 1u : 0u;
+    k_fused_check<<<1, 256, 0, st>>>(fa);
 }
 
 void fast_fused_finish(cwf_hip_system *h, hipStream_t st)

@@ -241,7 +241,7 @@ __device__ __forceinline__ void resident_reduce(const ResArgs &ra, double *red2,
         }
         else
         {
-            go = fused_decide(ra.ctl, ra.hist, j, pre, tid == 0, v, &alpha, &beta);
+            go = fused_decide(ra.ctl, ra.hist, j, pre, tid == 0, v, &alpha, &beta, j - 1u == ra.max_it);
             if (go && j - 1u == ra.max_it)  // max_iterations updates made
                 go = false;
         }
@@ -554,7 +554,7 @@ __global__ __launch_bounds__(kResNT) __attribute__((amdgpu_waves_per_eu(2, 2))) 
                 }
             }
             stamp(j, 7);
-            go = fused_decide(ra.ctl, ra.hist, j, pre, b == 0 && tid == 0, v, &alpha, &beta);
+            go = fused_decide(ra.ctl, ra.hist, j, pre, b == 0 && tid == 0, v, &alpha, &beta, j - 1u == ra.max_it);
             if (go && j - 1u == ra.max_it)  // max_iterations updates made (the host loop's last launch)
                 go = false;
             if (!go)
