@@ -294,7 +294,12 @@ int cwf_hip_explicit_advance(cwf_hip_explicit *t, uint64_t n_steps, cwf_explicit
         if (pattern)
             a.scale = t->last_scale = curve_at(t, (double)t->steps * t->dt);
         if (pl.slots)  // the return map at u_n and the affected nodes' correction force, before the operator launch
-            explicit_plasticity(s, t->u, pl, st);
+        {
+            if (t->pl.model == 2)
+                explicit_soil_plasticity(s, t->u, pl, t->pl.soil, t->pl.node_pass, st);
+            else
+                explicit_plasticity(s, t->u, pl, st);
+        }
         if (fast)
             fast_keff_partials_ds(s, t->w, true, st);
         else

@@ -210,9 +210,34 @@ std::string parse_config(const yl::Node &root)
                 throw CfgError{std::string("material.") + key + " must be >= 0", {"materials", idx(i), key}};
             j << ", \"" << key << "\": " << jnum(v);
         }
-        if (m["hardening_modulus"].defined() && !m["yield_stress"].defined())
+        if (m["hardening_modulus"].defined() && !m["yield_stress"].defined() && !m["friction_angle"].defined())
             throw CfgError{"material.hardening_modulus needs material.yield_stress",
                            {"materials", idx(i), "hardening_modulus"}};
+        // soil plasticity of the explicit integrator (optional, emitted only when present): Mohr-Coulomb cohesion (Pa)
+        // and angles in degrees; hardening_modulus then hardens the cohesion
+        double phi = 0.0;
+        for (const char *key : {"cohesion", "friction_angle", "dilation_angle"})
+        {
+            if (!m[key].defined())
+                continue;
+            const bool angle = key[0] != 'c';
+            if (!m["friction_angle"].defined())
+                throw CfgError{std::string("material.") + key + " needs material.friction_angle",
+                               {"materials", idx(i), key}};
+            if (m["yield_stress"].defined())
+                throw CfgError{"material.friction_angle excludes material.yield_stress",
+                               {"materials", idx(i), "friction_angle"}};
+            const double v = guard({"materials", idx(i), key}, [&] { return m[key].as_double(); });
+            if (!(v >= 0.0) || (angle && !(v < 90.0)))
+                throw CfgError{std::string("material.") + key + (angle ? " must be [0, 90)" : " must be >= 0"),
+                               {"materials", idx(i), key}};
+            if (key[0] == 'f')
+                phi = v;
+            if (key[0] == 'd' && v > phi)
+                throw CfgError{"material.dilation_angle must not exceed material.friction_angle",
+                               {"materials", idx(i), "dilation_angle"}};
+            j << ", \"" << key << "\": " << jnum(v);
+        }
         j << "}";
     }
     j << "]";
@@ -503,6 +528,44 @@ std::string parse_config(const yl::Node &root)
             j << "}}";
         }
         j << "]";
+    }
+    // geostatic (optional map; emitted only when the document has it): the stress at rest of the soil materials.
+    // k0: a scalar or one per material; without it the driver takes 1 - sin(friction_angle) per material
+    const yl::Node &geo = root["geostatic"];
+    if (geo.defined())
+    {
+        if (!geo.is_map())
+            throw CfgError{"geostatic must be a map when present", {"geostatic"}};
+        const double g = geo["gravity"].defined()
+                             ? guard({"geostatic", "gravity"}, [&] { return geo["gravity"].as_double(); })
+                             : 9.81;
+        if (!(g >= 0.0))
+            throw CfgError{"geostatic.gravity must be >= 0", {"geostatic", "gravity"}};
+        const double axis =
+            geo["axis"].defined() ? guard({"geostatic", "axis"}, [&] { return geo["axis"].as_double(); }) : 2.0;
+        if (axis != 0.0 && axis != 1.0 && axis != 2.0)
+            throw CfgError{"geostatic.axis must be 0, 1 or 2", {"geostatic", "axis"}};
+        j << ", \"geostatic\": {\"gravity\": " << jnum(g) << ", \"axis\": " << (int)axis;
+        const yl::Node &k0 = geo["k0"];
+        if (k0.defined())
+        {
+            if (k0.is_seq() && k0.size() != mats.size())
+                throw CfgError{"geostatic.k0 must be a scalar or one value per material", {"geostatic", "k0"}};
+            j << ", \"k0\": " << (k0.is_seq() ? "[" : "");
+            for (size_t i = 0; i < (k0.is_seq() ? k0.size() : 1); ++i)
+            {
+                const double v =
+                    guard({"geostatic", "k0"}, [&] { return k0.is_seq() ? k0[i].as_double() : k0.as_double(); });
+                if (!(v >= 0.0))
+                    throw CfgError{"geostatic.k0 must be >= 0", {"geostatic", "k0"}};
+                j << (i ? ", " : "") << jnum(v);
+            }
+            j << (k0.is_seq() ? "]" : "");
+        }
+        if (geo["surface"].defined())
+            j << ", \"surface\": "
+              << jnum(guard({"geostatic", "surface"}, [&] { return geo["surface"].as_double(); }));
+        j << "}";
     }
     j << "}";
     return j.str();

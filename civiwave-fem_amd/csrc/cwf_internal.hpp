@@ -680,6 +680,18 @@ struct ExplicitPlasticity
 };
 // one step's element pass and node pass on u = u_n (the handle's node order): p of the affected nodes is rewritten
 void explicit_plasticity(const DevSys &s, const float *u, const ExplicitPlasticity &a, hipStream_t st);
+// what the Drucker-Prager set (cwf_hip_explicit_set_soil_plasticity) holds beside an ExplicitPlasticity, whose
+// yield_hard it leaves NULL; in the stepper's arena too
+struct ExplicitSoil
+{
+    const double *params;  // [M] 32-B records {alpha, kappa, beta, H} by material
+    const double *sig0;    // [slots] 48-B records: the slot's stress at rest, Voigt; NULL: none was given
+};
+// the same step with the soil set's element pass (k_explicit_dp_elements); node_pass 1: k_explicit_plastic_nodes,
+// 2: the pass that reads its runs cooperatively (k_explicit_plastic_nodes_coop), 3: that pass with rounds of 96 words
+// (tests: many rounds on a small mesh); the same bits every way
+void explicit_soil_plasticity(const DevSys &s, const float *u, const ExplicitPlasticity &a, const ExplicitSoil &soil,
+                              int node_pass, hipStream_t st);
 bool fast_direct_fold(const cwf_hip_system *h);  // unsharded: consumers fold per-workgroup shares
 void fast_fold_pap(cwf_hip_system *h, hipStream_t st);  // local p.Ap shares -> g_pap[rank]
 void fast_fold_rrz(cwf_hip_system *h, unsigned it, hipStream_t st);  // local r.r / r.z shares -> g_rrz[2 rank]

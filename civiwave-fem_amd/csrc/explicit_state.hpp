@@ -203,10 +203,14 @@ struct cwf_hip_explicit : cwf::TransientState
                 gsteps.push_back(steps);
         }
     } emon;
-    // set_plasticity: dev.slots == 0: none; the slots' elements on the host (read_plasticity scatters through them)
+    // set_plasticity and set_soil_plasticity (one set, whichever came last): dev.slots == 0: none; the slots' elements
+    // on the host (read_plasticity scatters through them). model: 0 none, 1 J2, 2 soil, whose further arrays are soil's
     struct Plasticity
     {
         cwf::ExplicitPlasticity dev{};
+        cwf::ExplicitSoil soil{};
+        int model = 0;
+        int node_pass = 1;  // the soil set's node pass, cwf_explicit_soil_desc.node_pass resolved (1, 2 or 3)
         std::vector<uint32_t> elem;
         uint64_t bytes = 0;
         std::vector<void *> held;

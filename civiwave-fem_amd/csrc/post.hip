@@ -12,6 +12,7 @@
 // averaged stress. This TU inherits -ffp-contract=off and IEEE fp64 div/sqrt from the Makefile.
 #include "cwf_internal.hpp"
 #include "plasticity.hpp"
+#include "soil_plasticity.hpp"
 
 namespace cwf
 {
@@ -350,6 +351,101 @@ __global__ __launch_bounds__(kBlock) void k_explicit_plastic_elements(DevSys s, 
     }
 }
 
+// Soil plasticity (include/cwf_hip.h "Soil plasticity"): k_explicit_plastic_elements with soil_plasticity.hpp's return
+// map. The same loads in the same order, the material's {alpha, kappa, beta, H} as two 16-B loads where J2 reads
+// {sy, H}, and with SIG0 the slot's stress at rest as three more (48-B records in a hipMalloc'd array, so 16-B
+// aligned); a set without one runs the instantiation that reads nothing more than J2 does. State and corner forces
+// are stored by J2's rules but for one case: the state where the element yielded, the corner forces where it yielded in
+// this step or abar > 0 (an apex return from a stress without a deviator changes ep and leaves abar at 0).
+template <bool SIG0>
+__global__ __launch_bounds__(kBlock) void k_explicit_dp_elements(DevSys s, const float *__restrict__ u,
+                                                                 ExplicitPlasticity a, ExplicitSoil soil)
+{
+    const uint32_t slot = blockIdx.x * kBlock + threadIdx.x;
+    if (slot >= a.slots)
+        return;
+    const uint32_t e = a.elem[slot];
+    const uint4 q0 = s.erec[4u * e + 0u];
+    const uint4 g0 = s.erec[4u * e + 1u], g1 = s.erec[4u * e + 2u], g2 = s.erec[4u * e + 3u];
+    const uint32_t m = s.mat[e];
+    const float volf = s.vol[e];
+    double2 *sp2 = reinterpret_cast<double2 *>(a.state + 8ull * slot);
+    const double2 s0 = sp2[0], s1 = sp2[1], s2 = sp2[2], s3 = sp2[3];
+    const uint4 cp = reinterpret_cast<const uint4 *>(a.cpos)[slot];
+    double2 z0 = make_double2(0.0, 0.0), z1 = z0, z2 = z0;
+    if constexpr (SIG0)
+    {
+        const double2 *zp = reinterpret_cast<const double2 *>(soil.sig0 + 6ull * slot);
+        z0 = zp[0];
+        z1 = zp[1];
+        z2 = zp[2];
+    }
+    const uint32_t c[4] = {q0.x, q0.y, q0.z, q0.w};
+    float uf[12];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+    {
+        uf[3 * k] = u[3ull * c[k] + 0];
+        uf[3 * k + 1] = u[3ull * c[k] + 1];
+        uf[3 * k + 2] = u[3ull * c[k] + 2];
+    }
+    const double *Dm = s.dmat + 36ull * m;
+    double D[36];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+    {
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            D[6 * r + k] = Dm[6 * r + k];
+        D[7 * (r + 3)] = Dm[7 * (r + 3)];
+    }
+    const double2 ak = reinterpret_cast<const double2 *>(soil.params)[2ull * m];
+    const double2 bh = reinterpret_cast<const double2 *>(soil.params)[2ull * m + 1];
+    const float g[12] = {__uint_as_float(g0.x), __uint_as_float(g0.y), __uint_as_float(g0.z), __uint_as_float(g0.w),
+                         __uint_as_float(g1.x), __uint_as_float(g1.y), __uint_as_float(g1.z), __uint_as_float(g1.w),
+                         __uint_as_float(g2.x), __uint_as_float(g2.y), __uint_as_float(g2.z), __uint_as_float(g2.w)};
+    // element_tensors' strain
+    double e6[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+    {
+        const double ux = (double)uf[3 * k], uy = (double)uf[3 * k + 1], uz = (double)uf[3 * k + 2];
+        const double gx = (double)g[3 * k], gy = (double)g[3 * k + 1], gz = (double)g[3 * k + 2];
+        e6[0] += gx * ux;
+        e6[1] += gy * uy;
+        e6[2] += gz * uz;
+        e6[3] += gy * ux + gx * uy;
+        e6[4] += gz * uy + gy * uz;
+        e6[5] += gz * ux + gx * uz;
+    }
+    double ep[6] = {s0.x, s0.y, s1.x, s1.y, s2.x, s2.y}, abar = s3.x, wp = s3.y, sp[6];
+    const double par[4] = {ak.x, ak.y, bh.x, bh.y};
+    const double sig0[6] = {z0.x, z0.y, z1.x, z1.y, z2.x, z2.y};
+    const double V = (double)volf;
+    const int branch = dp_update(D, par, SIG0 ? sig0 : nullptr, V, e6, ep, abar, wp, sp);
+    if (branch)
+    {
+        sp2[0] = make_double2(ep[0], ep[1]);
+        sp2[1] = make_double2(ep[2], ep[3]);
+        sp2[2] = make_double2(ep[4], ep[5]);
+        sp2[3] = make_double2(abar, wp);
+    }
+    // an apex return from a stress without a deviator changes ep and leaves abar at 0: that step pushes too
+    if (!(branch || abar > 0.0))
+        return;
+    const uint32_t pos[4] = {cp.x, cp.y, cp.z, cp.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+    {
+        const double gx = (double)g[3 * k], gy = (double)g[3 * k + 1], gz = (double)g[3 * k + 2];
+        P3 o;
+        o.c[0] = safe_cast(V * ((gx * sp[0] + gy * sp[3]) + gz * sp[5]));
+        o.c[1] = safe_cast(V * ((gy * sp[1] + gx * sp[3]) + gz * sp[4]));
+        o.c[2] = safe_cast(V * ((gz * sp[2] + gy * sp[4]) + gx * sp[5]));
+        *reinterpret_cast<P3 *>(a.corner + 3ull * pos[k]) = o;
+    }
+}
+
 // One thread per affected node: its run of the node-major corner forces (ascending element, built at set time), each
 // widened to double and added from +0.0 in that order, safe_cast, one 12-B store into the correction vector p the
 // update pass reads. Consecutive nodes read consecutive runs. Rows of other nodes stay at the zero they were set to.
@@ -367,6 +463,60 @@ __global__ __launch_bounds__(kBlock) void k_explicit_plastic_nodes(ExplicitPlast
         acc1 = acc1 + (double)c.c[1];
         acc2 = acc2 + (double)c.c[2];
     }
+    P3 o;
+    o.c[0] = safe_cast(acc0);
+    o.c[1] = safe_cast(acc1);
+    o.c[2] = safe_cast(acc2);
+    *reinterpret_cast<P3 *>(a.p + 3ull * a.anode[i]) = o;
+}
+
+// The node pass read cooperatively (the soil set's; J2 keeps the pass above). A wavefront owns 64 consecutive affected
+// nodes, whose runs are one contiguous span of the corner array: its lanes copy the span into the wave's share of LDS
+// as consecutive words, WORDS at a time (a multiple of 3, so no 12-B entry straddles two rounds; kCoopWords: 4 waves x
+// 20,472 B = 81,888 B per workgroup, two workgroups in a CU's 160 KiB), and each lane then folds the part of its own
+// run that the round holds, from +0.0 in ascending element order: the sums, and so the bits of p, are those of
+// k_explicit_plastic_nodes. Only the wave's own lanes touch its share, and a wave's LDS accesses complete in order,
+// so a wavefront-scope fence between the copy and the fold is all the ordering there is to keep.
+// WORDS is a template parameter so that a test can run many short rounds on a small mesh (kCoopTestWords: a run of 24
+// entries is 72 words, so most runs straddle a round's end and the accumulators are carried over).
+constexpr uint32_t kCoopWords = 5118, kCoopTestWords = 96;
+template <uint32_t WORDS>
+__global__ __launch_bounds__(kBlock) void k_explicit_plastic_nodes_coop(ExplicitPlasticity a)
+{
+    static_assert(WORDS % 3u == 0u, "a round holds whole 12-B entries");
+    __shared__ float lds[(kBlock / 64) * WORDS];
+    float *mine = lds + (threadIdx.x / 64u) * WORDS;
+    const uint32_t lane = threadIdx.x % 64u;
+    const uint32_t first = (blockIdx.x * kBlock + threadIdx.x) - lane;  // the wave's first node
+    if (first >= a.affected)
+        return;
+    const uint32_t i = first + lane;
+    const bool live = i < a.affected;
+    const uint32_t last = min(first + 63u, a.affected - 1u);
+    const uint32_t w0 = 3u * a.aoff[first], w1 = 3u * a.aoff[last + 1u];
+    const uint32_t my0 = live ? 3u * a.aoff[i] : w1, my1 = live ? 3u * a.aoff[i + 1u] : w1;
+    double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0;
+    for (uint32_t base = w0; base < w1; base += WORDS)
+    {
+        const uint32_t n = min(WORDS, w1 - base);
+        for (uint32_t k = lane; k < n; k += 64u)
+            mine[k] = a.corner[base + k];
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const uint32_t lo = max(my0, base), hi = min(my1, base + n);
+        for (uint32_t j = lo; j < hi; j += 3u)
+        {
+            acc0 = acc0 + (double)mine[j - base];
+            acc1 = acc1 + (double)mine[j - base + 1u];
+            acc2 = acc2 + (double)mine[j - base + 2u];
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+    if (!live)
+        return;
     P3 o;
     o.c[0] = safe_cast(acc0);
     o.c[1] = safe_cast(acc1);
@@ -423,6 +573,23 @@ void explicit_plasticity(const DevSys &s, const float *u, const ExplicitPlastici
         return;
     k_explicit_plastic_elements<<<grid_for(a.slots), kBlock, 0, st>>>(s, u, a);
     k_explicit_plastic_nodes<<<grid_for(a.affected), kBlock, 0, st>>>(a);
+}
+
+void explicit_soil_plasticity(const DevSys &s, const float *u, const ExplicitPlasticity &a, const ExplicitSoil &soil,
+                              int node_pass, hipStream_t st)
+{
+    if (!a.slots)
+        return;
+    if (soil.sig0)
+        k_explicit_dp_elements<true><<<grid_for(a.slots), kBlock, 0, st>>>(s, u, a, soil);
+    else
+        k_explicit_dp_elements<false><<<grid_for(a.slots), kBlock, 0, st>>>(s, u, a, soil);
+    if (node_pass == 2)
+        k_explicit_plastic_nodes_coop<kCoopWords><<<grid_for(a.affected), kBlock, 0, st>>>(a);
+    else if (node_pass == 3)
+        k_explicit_plastic_nodes_coop<kCoopTestWords><<<grid_for(a.affected), kBlock, 0, st>>>(a);
+    else
+        k_explicit_plastic_nodes<<<grid_for(a.affected), kBlock, 0, st>>>(a);
 }
 
 void derived_fields(cwf_hip_system *h, const float *u, float *elem_out, float *node_out, hipStream_t st)

@@ -154,6 +154,12 @@ class ExplicitPlasticityInfoC(C.Structure):
                 ("bytes", C.c_uint64)]
 
 
+class ExplicitSoilDescC(C.Structure):
+    _fields_ = [("alpha", C.c_void_p), ("kappa", C.c_void_p), ("beta", C.c_void_p), ("hardening", C.c_void_p),
+                ("material_count", C.c_uint64), ("initial_stress", C.c_void_p), ("element_count", C.c_uint64),
+                ("node_pass", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class ShardInfoC(C.Structure):
     _fields_ = [
         ("owned_nodes", C.c_uint64), ("local_nodes", C.c_uint64), ("local_elements", C.c_uint64),
@@ -279,6 +285,11 @@ def load() -> C.CDLL:
         "cwf_hip_explicit_plasticity_info": ([P, P], i32),
         "cwf_hip_explicit_read_plasticity": ([P, P, P, P, u64], i32),
         "cwf_explicit_j2_update": ([P, f64, f64, f64, P, P, P], i32),
+        "cwf_hip_explicit_set_soil_plasticity": ([P, P], i32),
+        "cwf_hip_explicit_plasticity_model": ([P, P], i32),
+        "cwf_explicit_dp_update": ([P, P, P, f64, P, P, P], i32),
+        "cwf_soil_dp_from_mohr_coulomb": ([f64, f64, f64, i32, P], i32),
+        "cwf_soil_geostatic_stress": ([u64, P, P, u64, P, P, f64, i32, P, u64, P, P], i32),
         "cwf_explicit_dashpot_update": ([P, f64, f64, f64, P, P], i32),
         "cwf_absorbing_dashpots": ([u64, P, u64, C.c_uint32, P, P, u64, P, P, P, u64, C.c_uint32, P, P, P, P], i32),
         "cwf_absorbing_incident_plane": ([u64, P, u64, C.c_uint32, P, P, u64, P, P, P, u64, C.c_uint32, P, P, P, P, P, P,

@@ -14,8 +14,8 @@ from dataclasses import dataclass, field
 
 from . import _lib
 from .pcg import Expected
-from .physics import (AbsorbingBoundary, Assignment, Config, Curve, Damping, DirichletFix, IncidentWave, Loads,
-                      Material, OutputSettings, PointLoad, PrecisionSettings, SolverSettings, SurfaceTraction,
+from .physics import (AbsorbingBoundary, Assignment, Config, Curve, Damping, DirichletFix, Geostatic, IncidentWave,
+                      Loads, Material, OutputSettings, PointLoad, PrecisionSettings, SolverSettings, SurfaceTraction,
                       TimeSettings)
 
 
@@ -29,12 +29,22 @@ def _f3(v):
     return tuple(float(x) for x in v)
 
 
+def _geostatic(g: dict, materials: int) -> Geostatic:
+    k0 = g.get("k0")
+    if k0 is not None and not isinstance(k0, list):
+        k0 = [k0] * materials
+    return Geostatic(float(g["gravity"]), None if k0 is None else [float(x) for x in k0], int(g["axis"]),
+                     None if g.get("surface") is None else float(g["surface"]))
+
+
 def _from_json(d: dict) -> Config:
     f = float
     return Config(
         mesh_path=d["mesh_path"],
         materials=[Material(m["name"], f(m["E"]), f(m["nu"]), f(m["rho"]), f(m.get("yield_stress", 0.0)),
-                            f(m.get("hardening_modulus", 0.0))) for m in d["materials"]],
+                            f(m.get("hardening_modulus", 0.0)), f(m.get("cohesion", 0.0)),
+                            f(m["friction_angle"]) if "friction_angle" in m else None,
+                            f(m.get("dilation_angle", 0.0))) for m in d["materials"]],
         assignments=[Assignment(a["group"], a["material"]) for a in d["assignments"]],
         damping=Damping(f(d["damping"]["xi"]), f(d["damping"]["w1"]), f(d["damping"]["w2"])),
         time=TimeSettings(f(d["time"]["initial_dt"]), bool(d["time"]["adaptive"]), f(d["time"]["min_dt"]),
@@ -54,6 +64,7 @@ def _from_json(d: dict) -> Config:
                                                   *(_f3(a["incident"][k]) if k in a["incident"] else None
                                                     for k in ("propagation", "origin"))))
                    for a in d.get("absorbing", [])],
+        geostatic=_geostatic(d["geostatic"], len(d["materials"])) if "geostatic" in d else None,
     )
 
 

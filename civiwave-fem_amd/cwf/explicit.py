@@ -184,10 +184,12 @@ class PlasticState:
     plastic_work: np.ndarray               # f64 [E], J
     stiffness: np.ndarray                  # f64 [E,6,6] each element's D
 
-    def stress(self, strain) -> np.ndarray:
-        """D (e - ep) of total strains [E,6] (float64, host): the stress the material carries."""
+    def stress(self, strain, initial_stress=None) -> np.ndarray:
+        """D (e - ep) of total strains [E,6] (float64, host): the stress the material carries; with initial_stress
+        [E,6] (the soil set's stress at rest) sig0 + D (e - ep)."""
         ee = np.asarray(strain, np.float64) - self.plastic_strain
-        return np.einsum("eij,ej->ei", self.stiffness, ee)
+        st = np.einsum("eij,ej->ei", self.stiffness, ee)
+        return st if initial_stress is None else np.asarray(initial_stress, np.float64).reshape(-1, 6) + st
 
 
 def j2_update(D, yield_stress: float, hardening: float, volume: float, strain, state):
@@ -200,6 +202,22 @@ def j2_update(D, yield_stress: float, hardening: float, volume: float, strain, s
     y = _lib.load().cwf_explicit_j2_update(_lib.ptr(Dm), float(yield_stress), float(hardening), float(volume),
                                            _lib.ptr(e), _lib.ptr(st), _lib.ptr(sp))
     return bool(y), st, sp
+
+
+def dp_update(D, alpha: float, kappa: float, beta: float, hardening: float, volume: float, strain, state,
+              initial_stress=None):
+    """The element update of the soil plasticity scheme by the library (host only). D [6,6] isotropic, strain [6],
+    state [8] = ep[6], abar, wp, initial_stress [6] or None -> (0 elastic / 1 cone / 2 apex, the new state [8],
+    sigma_p = D ep [6])."""
+    Dm = np.ascontiguousarray(D, np.float64).reshape(36)
+    par = np.array([alpha, kappa, beta, hardening], np.float64)
+    e = np.ascontiguousarray(strain, np.float64).reshape(6)
+    st = np.array(state, np.float64).reshape(8)
+    sp = np.zeros(6, np.float64)
+    s0 = None if initial_stress is None else np.ascontiguousarray(initial_stress, np.float64).reshape(6)
+    b = _lib.load().cwf_explicit_dp_update(_lib.ptr(Dm), _lib.ptr(par), _lib.ptr(s0), float(volume), _lib.ptr(e),
+                                           _lib.ptr(st), _lib.ptr(sp))
+    return int(b), st, sp
 
 
 def lambda_max(system: MatrixFreeSystem, iterations: int = 60):
@@ -370,7 +388,39 @@ class ExplicitStepper(TransientState):
         d = _lib.ExplicitPlasticityDescC(sy.ctypes.data, H.ctypes.data, sy.size)
         self._check(_lib.load().cwf_hip_explicit_set_plasticity(self._ex, C.byref(d)))
 
+    def set_soil_plasticity(self, alpha, kappa, beta=0.0, hardening=0.0, initial_stress=None, node_pass: int = 0):
+        """Drucker-Prager plasticity (include/cwf_hip.h "Soil plasticity"): friction alpha, cohesion kappa, dilation
+        beta and hardening per material (scalars apply to every material; cwf.soil.from_mohr_coulomb gives them); a
+        kappa of inf leaves that material elastic. initial_stress: the stress at rest [E,6] in the caller's element
+        order (cwf.soil.geostatic_stress), or None for zeros. Replaces the previous set, J2 or soil, which stays in
+        force if this one is refused (RuntimeError). node_pass: 0 leaves the choice of the node pass to the library;
+        1 (plain), 2 (cooperative) and 3 (cooperative, short LDS rounds) are for tests and measurements, the results are
+        the same bit for bit."""
+        given = [np.asarray(x, np.float64) for x in (alpha, kappa, beta, hardening)]
+        # scalars take the length of the arrays given with them, or the stepper's material count
+        M = next((x.size for x in given if x.ndim), len(self.materials))
+        al, ka, be, H = (np.ascontiguousarray(np.broadcast_to(x, (M,)) if x.ndim == 0 else x.reshape(-1))
+                         for x in given)
+        if not al.size == ka.size == be.size == H.size:
+            raise ValueError("one alpha, kappa, beta and hardening per material")
+        s0, rows = None, 0
+        if initial_stress is not None:
+            s0 = np.ascontiguousarray(initial_stress, np.float64)
+            if s0.size % 6:
+                raise ValueError("initial_stress is [E,6]")
+            rows = s0.size // 6
+        d = _lib.ExplicitSoilDescC(al.ctypes.data, ka.ctypes.data, be.ctypes.data, H.ctypes.data, al.size,
+                                   s0.ctypes.data if s0 is not None else None, rows, int(node_pass), 0)
+        self._check(_lib.load().cwf_hip_explicit_set_soil_plasticity(self._ex, C.byref(d)))
+
+    def plasticity_model(self) -> int:
+        """0: no plasticity set, 1: J2 (set_plasticity), 2: soil (set_soil_plasticity)."""
+        m = C.c_int(0)
+        self._check(_lib.load().cwf_hip_explicit_plasticity_model(self._ex, C.byref(m)))
+        return int(m.value)
+
     def clear_plasticity(self):
+        """Removes the set in force, J2 or soil."""
         self._check(_lib.load().cwf_hip_explicit_set_plasticity(self._ex, None))
 
     def reset_plasticity(self):

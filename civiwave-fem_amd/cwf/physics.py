@@ -16,7 +16,10 @@ class Material:
     poisson_ratio: float
     density: float
     yield_stress: float = 0.0       # J2 plasticity of the explicit integrator; 0: elastic
-    hardening_modulus: float = 0.0  # linear isotropic hardening H
+    hardening_modulus: float = 0.0  # linear isotropic hardening H (J2), or of the cohesion (soil)
+    cohesion: float = 0.0                   # soil plasticity of the explicit integrator (Mohr-Coulomb c, Pa)
+    friction_angle: Optional[float] = None  # degrees; None: no soil model on this material
+    dilation_angle: float = 0.0             # degrees, 0 <= psi <= phi
 
 
 @dataclass
@@ -109,6 +112,15 @@ class AbsorbingBoundary:
 
 
 @dataclass
+class Geostatic:
+    """The stress at rest of a layered deposit for the soil plasticity (cwf.soil.geostatic_stress)."""
+    gravity: float = 9.81
+    k0: Optional[list] = None  # per material; None: 1 - sin(phi) of each material (Jaky), 1 where it has no phi
+    axis: int = 2
+    surface: Optional[float] = None  # None: the highest node
+
+
+@dataclass
 class Config:
     mesh_path: str = ""
     materials: list = field(default_factory=list)
@@ -122,6 +134,7 @@ class Config:
     dirichlet: list = field(default_factory=list)
     output: OutputSettings = field(default_factory=OutputSettings)
     absorbing: list = field(default_factory=list)  # [AbsorbingBoundary] (explicit integrator only)
+    geostatic: Optional[Geostatic] = None  # explicit integrator only, with soil materials
 
 
 # ---- materials.hpp -----------------------------------------------------------------------

@@ -31,6 +31,11 @@ element (``monitors/envelope_von_mises.npy``, ``envelope_shear_strain.npy`` [E];
 ``envelope_stress_max.npy`` [E,6]), and the strain / stress / von Mises rows of the gauge elements
 (``monitors/gauges.csv``, one line per sample and gauge).
 
+Materials with a ``yield_stress`` yield by J2 plasticity (explicit only); materials with a ``friction_angle`` (degrees;
+``cohesion``, ``dilation_angle``, ``hardening_modulus``) by the Drucker-Prager soil model, with the stress at rest of a
+top-level ``geostatic: {gravity, k0, axis, surface}``. Either way the VTU frames carry ``plastic_strain`` and
+``equivalent_plastic_strain`` per cell, and ``--plastic-summary`` logs the yielded elements and the plastic work.
+
 Mesh paths are resolved like the reference (relative to the working directory) and, failing that,
 relative to the YAML file's directory. One JSON line per step is printed; the last line is a summary.
 """
@@ -84,7 +89,7 @@ def run_scenario(cfg_path: str, steps: int, out_dir: str | None, mode: int = _li
     cfg, m, P, materials = load_scenario(cfg_path, allow_hex8=mode == _lib.MODE_FAST)
     if cfg.absorbing:
         raise ScenarioError("absorbing boundaries need the explicit integrator")
-    if any(x.yield_stress > 0.0 for x in cfg.materials):
+    if any(x.yield_stress > 0.0 or x.friction_angle is not None for x in cfg.materials):
         raise ScenarioError("plastic materials need the explicit integrator")
     st = Stepper(P, materials, compute_rayleigh(cfg.damping), cfg.solver, cfg.time, mode=mode, device=device)
     om = post.OutputManager(out_dir, m, P, materials, cfg.output, stepper=st) if out_dir else None
@@ -120,6 +125,45 @@ def run_scenario(cfg_path: str, steps: int, out_dir: str | None, mode: int = _li
         st.system.close()
 
 
+def set_soil_plasticity(st, cfg, P):
+    """The scenario's soil model on an explicit stepper: materials with a ``friction_angle`` become Drucker-Prager
+    cones through the Mohr-Coulomb compression corners, ``hardening_modulus`` hardening the cohesion; materials
+    without one stay elastic. A stepper holds one plasticity set, so J2 materials (``yield_stress``) of the same
+    scenario enter as the cone without friction that is the same surface (alpha = beta = 0, kappa = sy / sqrt3,
+    H / 3), which is said on stderr. ``geostatic:`` gives the stress at rest; without it there is none."""
+    import math
+
+    import numpy as np
+
+    from . import soil
+
+    alpha, kappa, beta, H = [], [], [], []
+    for x in cfg.materials:
+        if x.friction_angle is not None:
+            a, k, b = soil.from_mohr_coulomb(x.cohesion, x.friction_angle, x.dilation_angle)
+            h = x.hardening_modulus
+        elif x.yield_stress > 0.0:
+            a, k, b, h = 0.0, x.yield_stress / math.sqrt(3.0), 0.0, x.hardening_modulus / 3.0
+            print(f"material {x.name}: yield_stress {x.yield_stress:g} enters the soil plasticity set as "
+                  f"alpha = beta = 0, kappa = {k:g}, hardening = {h:g}", file=sys.stderr)
+        else:
+            a, k, b, h = 0.0, math.inf, 0.0, 0.0
+        alpha.append(a), kappa.append(k), beta.append(b), H.append(h)
+    sig0 = None
+    if cfg.geostatic is not None:
+        g = cfg.geostatic
+        k0 = g.k0 if g.k0 is not None else [1.0 - math.sin(math.radians(x.friction_angle or 0.0))
+                                            for x in cfg.materials]
+        sig0 = soil.geostatic_stress(P, cfg.materials, gravity=g.gravity, k0=k0, axis=g.axis, surface=g.surface)
+        mat = np.asarray(P.material_index, np.int64)
+        soft = np.isfinite(np.asarray(kappa))[mat]
+        bad = soil.overstressed(sig0[soft], np.asarray(alpha)[mat][soft], np.asarray(kappa)[mat][soft])
+        if bad.size:
+            print(f"geostatic: the stress at rest of {bad.size} elements lies outside their cone (K0 too far from 1 "
+                  f"for the friction angle); they yield in the first step", file=sys.stderr)
+    st.set_soil_plasticity(alpha, kappa, beta, H, initial_stress=sig0)
+
+
 def run_scenario_explicit(cfg_path: str, steps: int, out_dir: str | None, mode: int = _lib.MODE_PARITY,
                           device: int = 0, safety: float = 0.9, log=print, trace_every: int = 0, peaks: bool = False,
                           energy_every: int = 0, mass_damping_only: bool = False, envelope_every: int = 0,
@@ -148,11 +192,18 @@ def run_scenario_explicit(cfg_path: str, steps: int, out_dir: str | None, mode: 
     wall0, last = time.perf_counter(), None
     try:
         absorbing_nodes = set_absorbing(st, cfg, m, P)
-        plastic = any(x.yield_stress > 0.0 for x in cfg.materials)
+        soil_model = any(x.friction_angle is not None for x in cfg.materials)
+        plastic = soil_model or any(x.yield_stress > 0.0 for x in cfg.materials)
+        if cfg.geostatic is not None and not soil_model:
+            raise ScenarioError("geostatic needs a material with a friction_angle")
         if plastic:
             try:
-                st.set_plasticity([x.yield_stress for x in cfg.materials], [x.hardening_modulus for x in cfg.materials])
-            except RuntimeError as e:
+                if soil_model:
+                    set_soil_plasticity(st, cfg, P)
+                else:
+                    st.set_plasticity([x.yield_stress for x in cfg.materials],
+                                      [x.hardening_modulus for x in cfg.materials])
+            except (RuntimeError, ValueError) as e:
                 raise ScenarioError(str(e)) from None
             if om is not None:
                 om.plasticity = st.plasticity

@@ -547,6 +547,58 @@ int cwf_hip_stepper_time(const cwf_hip_stepper *st, double *current_time, double
  * balance would no longer be constant. Element monitors and gauges keep reporting D e, the stress of the total strain;
  * the stress D (e - ep) is formed on the host from cwf_hip_explicit_read_plasticity. A stepper without plasticity
  * launches exactly the kernels it launches without this section and allocates nothing for it.
+ *
+ * Soil plasticity (cwf_hip_explicit_set_soil_plasticity): rate-independent Drucker-Prager plasticity with linear
+ * hardening of the cohesion on tet4 elements, in the same initial-stress form: the operator product stays y = K w,
+ * plasticity enters through the correction force p alone, and the update pass, the node pass, slots, affected nodes and
+ * the 64-B state record ep[6], abar, wp are those of "Plasticity". Small strain, tension positive, Voigt order with
+ * engineering shears. A stepper holds one plasticity set: either setter replaces whichever is in force.
+ * Per material m: an isotropic D (mu = D[3][3], lambda = D[0][1], Kb = lambda + (2/3) mu), alpha >= 0 (friction),
+ * kappa >= 0 (cohesion), 0 <= beta <= alpha (dilation), H >= 0 (hardening of kappa with abar). kappa = +inf: the
+ * material is elastic. alpha = 0 with kappa = 0 has no strength at all and is refused.
+ * Per plastic element an optional stress at rest sig0[6] (fp64, Pa; zeros when no array is given). The dynamic run
+ * models no gravity; sig0 is in equilibrium with the gravity that is not modelled, so it adds no force and enters the
+ * yield function alone.
+ * Per plastic element, in fp64 without fused multiply-adds, with e and ee as in "Plasticity":
+ *     st     = D ee                              the same isotropic row fold
+ *     st_r   = sig0_r + st_r                     every r, only when a stress at rest was given
+ *     pm     = ((st_0 + st_1) + st_2) / 3.0
+ *     s_r    = st_r - pm (r < 3),  s_r = st_r (r >= 3)
+ *     j2     = 0.5 * ((s_0*s_0 + s_1*s_1) + s_2*s_2) + ((s_3*s_3 + s_4*s_4) + s_5*s_5)
+ *     J      = sqrt(j2 < 0 ? 0 : j2)
+ *     kc     = kappa + H * abar
+ *     f      = (J + (3.0 * alpha) * pm) - kc
+ *     if f > 0:                                  (a NaN never yields)
+ *         Kb   = D_01 + (2.0 / 3.0) * mu
+ *         dl   = f / ((mu + ((9.0 * Kb) * alpha) * beta) + H)
+ *         Jn   = J - mu * dl
+ *         if Jn >= 0 or not alpha > 0:           the cone (return value 1)
+ *             half = (0.5 * dl) / J ;  bdl = beta * dl
+ *             ep_r = ep_r + (half * s_r + bdl) (r < 3);   ep_r = ep_r + (2.0 * half) * s_r (r >= 3)
+ *             abar = abar + dl
+ *             wp   = wp + V * (dl * (Jn + (3.0 * beta) * (pm - ((3.0 * Kb) * beta) * dl)))
+ *         else:                                  the apex (return value 2)
+ *             pa   = kc / (3.0 * alpha) ;  dv = (pm - pa) / Kb ;  third = dv / 3.0
+ *             ep_r = ep_r + (s_r / (2.0 * mu) + third) (r < 3);   ep_r = ep_r + s_r / mu (r >= 3)
+ *             abar = abar + J / mu
+ *             wp   = wp + V * (pa * dv)
+ *     sp     = D ep                              then the corner forces and the node fold of "Plasticity"
+ * With alpha = 0 the apex does not exist; "not alpha > 0" keeps a return whose Jn rounds below zero on the cone. The
+ * apex branch holds kc at its value from the start of the step (the hardening during an apex return is not iterated):
+ * a simplification. An apex return from a stress without a deviator changes ep and leaves abar at 0, so the element
+ * pass stores corner forces where the element yielded in this step or abar > 0.
+ * The device function, cwf_explicit_dp_update and the tests' numpy restatement each follow the lines above, not each
+ * other.
+ * Critical step: for beta = alpha (associated flow) the tangent is D minus a positive-semidefinite matrix and the
+ * elastic critical step holds as for J2. For beta < alpha the tangent is unsymmetric; the elastic step is kept, and
+ * its stability there is supposed, not proven.
+ * On the device, beside what "Plasticity" lists: 32 B of {alpha, kappa, beta, H} per material in place of J2's 16 B,
+ * and 48 B of sig0 per slot when one was given (slot-major, 16-B aligned; a set without it runs an instantiation of
+ * the element kernel that reads nothing more than J2's). The soil set launches k_explicit_dp_elements and the node
+ * pass k_explicit_plastic_nodes_coop: a wavefront copies the contiguous span of its 64 nodes' runs into LDS as
+ * consecutive words, then each lane folds its own run from there, from +0.0 in ascending element order, so p has the
+ * bits k_explicit_plastic_nodes gives (cwf_explicit_soil_desc.node_pass picks either for tests). J2 keeps its node pass.
+ * A stepper without soil plasticity launches what it launched before this section.
  * ------------------------------------------------------------------------------------- */
 typedef struct cwf_explicit_desc
 {
@@ -787,6 +839,63 @@ int cwf_hip_explicit_read_plasticity(cwf_hip_explicit *ex, double *ep, double *a
  * = D ep of the updated state. Returns 1 when the element yielded, else 0. */
 int cwf_explicit_j2_update(const double D[36], double yield, double hardening, double volume, const double strain[6],
                            double state[8], double sigma_p[6]);
+/* Soil plasticity of the scheme above. kappa[m] = +inf: material m is elastic. */
+typedef struct cwf_explicit_soil_desc
+{
+    const double *alpha;          /* [material_count] friction coefficient, >= 0 */
+    const double *kappa;          /* [material_count] cohesion, Pa, >= 0 */
+    const double *beta;           /* [material_count] dilation coefficient, 0 <= beta <= alpha */
+    const double *hardening;      /* [material_count] H >= 0, Pa */
+    uint64_t material_count;      /* the handle's */
+    const double *initial_stress; /* nullable; [element_count][6] the stress at rest, Pa, the caller's element order;
+                                     rows of elastic elements are ignored */
+    uint64_t element_count;       /* the handle's E (read only with initial_stress) */
+    uint32_t node_pass;           /* 0: the library's choice; for tests and measurements 1: k_explicit_plastic_nodes,
+                                     2: k_explicit_plastic_nodes_coop, 3: the latter with LDS rounds of 96 words, so
+                                     that a small mesh takes many rounds (the same p, bit for bit, every way) */
+    uint32_t reserved;
+} cwf_explicit_soil_desc;
+/* As cwf_hip_explicit_set_plasticity, for the Drucker-Prager set: replaces the set in force (J2 or soil), its state
+ * starting at zero; desc NULL, or a desc without a plastic element, removes it. A refusal leaves the previous set in
+ * force. Those of cwf_hip_explicit_set_plasticity with their codes and texts ("plasticity needs tet4 elements", "a
+ * plastic material needs an isotropic stiffness", "the energy ledger and plasticity exclude each other", "plasticity
+ * material count mismatch", "null pointer"), and CWF_ERR_ARGUMENT "soil plasticity parameters out of range"
+ * {material=<m>, alpha=, kappa=, beta=, hardening=} (a NaN too; alpha = kappa = 0), "initial stress is not finite"
+ * {element=<e>, component=<c>} (a plastic element's row); CWF_ERR_SIZE "initial stress span size mismatch"
+ * {span=<element_count>, elements=<E>}, CWF_ERR_ARGUMENT "unknown node pass" {node_pass=<n>}; CWF_ERR_ALLOC. cwf_hip_explicit_reset_plasticity, _plasticity_info,
+ * _read_plasticity and cwf_hip_explicit_get_state(which = 5) serve both models. For a soil set
+ * cwf_explicit_plasticity_info.yielded_elements counts the elements with abar > 0 or a plastic strain that is not zero
+ * (an apex return from a stress without a deviator leaves abar at 0). */
+int cwf_hip_explicit_set_soil_plasticity(cwf_hip_explicit *ex, const cwf_explicit_soil_desc *desc);
+/* *model: 0 no plasticity set, 1 J2, 2 soil */
+int cwf_hip_explicit_plasticity_model(cwf_hip_explicit *ex, int *model);
+/* Host only, no GPU: the element update of "Soil plasticity", the function the device pass runs. params = {alpha,
+ * kappa, beta, H}; sig0 nullable; the other arguments as cwf_explicit_j2_update. Returns 0 when the element stayed
+ * elastic, 1 when it returned to the cone, 2 to the apex. */
+int cwf_explicit_dp_update(const double D[36], const double params[4], const double *sig0, double volume,
+                           const double strain[6], double state[8], double sigma_p[6]);
+/* Host only: Drucker-Prager parameters out = {alpha, kappa, beta} from a Mohr-Coulomb cohesion c (Pa), friction angle
+ * phi and dilation angle psi (radians, 0 <= psi <= phi < pi/2). match 0, the compression cone: alpha = 2 sin phi /
+ * (sqrt3 (3 - sin phi)), kappa = 6 c cos phi / (sqrt3 (3 - sin phi)); match 1, the extension cone: 3 + sin phi in the
+ * denominators; match 2, plane strain: alpha = tan phi / sqrt(9 + 12 tan^2 phi), kappa = 3 c / sqrt(9 + 12 tan^2 phi).
+ * beta is alpha's formula at psi. CWF_ERR_ARGUMENT "Mohr-Coulomb parameters out of range", "unknown Drucker-Prager
+ * match". */
+int cwf_soil_dp_from_mohr_coulomb(double cohesion, double phi, double psi, int match, double out[3]);
+/* Host only: the stress at rest sig0 [element_count][6] of a horizontally layered deposit under its own weight, for
+ * cwf_explicit_soil_desc.initial_stress. centroids [element_count][3]; material [element_count] indexes density and
+ * k0 [material_count]; axis (0, 1, 2) is the vertical, pointing up; surface: the elevation of the free surface (NULL:
+ * the largest coordinate along axis of coords [node_count][3], which is read in that case only). Elements whose
+ * centroid elevations lie within 1e-9 of the deposit's height of each other form a bin; runs of bins of one material
+ * from the top down are the layers, two layers meeting midway between their adjacent bins. Per element
+ *     sigma_v = -gravity * (sum over the layers above of rho_l * thickness_l + rho * (top of its layer - centroid))
+ * on the vertical component, sigma_h = k0 * sigma_v on the two others, zero shears: for one material exactly
+ * -gravity * (rho * depth). CWF_ERR_ARGUMENT "the deposit is not horizontally layered" {element=, material=,
+ * layer_material=} for a bin of two materials, "a centroid lies above the surface", "null pointer" and non-finite or
+ * negative inputs; CWF_ERR_INDEX "material index out of range". */
+int cwf_soil_geostatic_stress(uint64_t element_count, const double *centroids, const uint32_t *material,
+                              uint64_t material_count, const double *density, const double *k0, double gravity,
+                              int axis, const double *surface, uint64_t node_count, const double *coords,
+                              double *sig0);
 /* Host only, no GPU: P and Q of the scheme above from C (row-major), the node's mass, alpha_R and dt, by the
  * closed-form 3x3 inverse. CWF_ERR_ARGUMENT for a C that is not finite ("dashpot matrix is not finite"), not symmetric
  * (|C_ij - C_ji| > 1e-12 trace: "dashpot matrix is not symmetric") or not positive semidefinite (a principal minor

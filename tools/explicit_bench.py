@@ -7,6 +7,7 @@
     python tools/explicit_bench.py --sources [--configs c2 c3] [--steps 2000]
     python tools/explicit_bench.py --envelopes [--configs c2 c3 c2:hex8] [--steps 2000]
     python tools/explicit_bench.py --plasticity [--plain-only] [--repeats 5] [--configs c2 c3] [--steps 2000]
+    python tools/explicit_bench.py --soil-plasticity [--repeats 5] [--configs c2 c3] [--steps 2000]
 
 Per config (a FAST handle of the block, created with scalars (1, 0)), in one process and one JSON line each, appended
 to --out (default profiles/explicit_c2.json):
@@ -56,6 +57,14 @@ read, 48 B of corner forces read by the node pass; per node 12 B of u gathered o
 the compact CSR, 12 B of p stored and 12 B read by the update pass; per element that has yielded 48 B of corner forces
 and (at most) 64 B of state written. --plain-only: line (a) alone, which a library without the feature can run
 (CWF_LIB_PATH: the same-session comparison with the parent commit's build).
+
+--soil-plasticity: the cost of the soil plasticity (include/cwf_hip.h "Soil plasticity"). Per config seven lines, appended
+to profiles/explicit_soil_plasticity.json, one stepper on one FAST handle: "plain" as above; "j2_elastic", --plasticity's
+(b); "soil_elastic", the soil set without a stress at rest and a cohesion nothing reaches; "soil_rest_elastic", the same
+with a geostatic stress; "soil_rest_yielding", a geostatic stress with K0 = 0.2 that lies outside the cone and next to
+no cohesion, so that every element yields; and the last two once more with node_pass = 1, the plain node pass in place
+of the cooperative one the soil set launches ("..._plain_nodes"). The estimate is --plasticity's, plus 48 B of stress at
+rest per slot where there is one.
 """
 import argparse
 import ctypes as C
@@ -372,6 +381,54 @@ def measure_plasticity(key, steps, device, repeats, plain_only, only=None):
     return lines
 
 
+def measure_soil_plasticity(key, steps, device, repeats):
+    import statistics
+
+    from cwf import soil
+
+    name, _, element = key.partition(":")
+    case = scenarios.config_case(name, element=element or "tet4")
+    P = case.packing
+    N, E = P.node_count, P.element_count
+    sysm = pcg.MatrixFreeSystem.from_packing(P, case.materials, 1.0, 0.0, mode=_lib.MODE_FAST, device=device)
+    base = dict(config=key, name=case.name, nodes=N, elements=E, steps=steps, library=_lib.LIB_PATH,
+                kernel=(_lib.load().cwf_hip_system_keff_kernel(sysm.handle()) or b"").decode())
+    ex = ExplicitStepper(P, case.materials, RayleighCoefficients(0.0, 0.0), system=sysm)
+    base["dt"] = ex.telemetry().dt
+    runs = [timed_steps(ex, steps) for _ in range(repeats)]
+    plain = statistics.median(runs)
+    lines = [dict(base, configuration="plain", step_us=plain, step_us_runs=runs,
+                  spread=(max(runs) - min(runs)) / plain)]
+    ceiling = 6.25e12
+    H = 0.1 * case.cfg.materials[0].youngs_modulus
+    rest = soil.geostatic_stress(P, case.cfg.materials, k0=0.2)  # K0 = 0.2 lies outside a cone of alpha = 0.05
+    configurations = (("j2_elastic", lambda: ex.set_plasticity(1e30, H), False),
+                      ("soil_elastic", lambda: ex.set_soil_plasticity(0.05, 1e30, 0.0, H), False),
+                      ("soil_rest_elastic", lambda: ex.set_soil_plasticity(0.05, 1e30, 0.0, H, initial_stress=rest), True),
+                      ("soil_rest_yielding", lambda: ex.set_soil_plasticity(0.05, 1e-3, 0.0, H, initial_stress=rest), True),
+                      # the last two again with the plain node pass: what the choice of the cooperative one rests on
+                      ("soil_rest_elastic_plain_nodes",
+                       lambda: ex.set_soil_plasticity(0.05, 1e30, 0.0, H, initial_stress=rest, node_pass=1), True),
+                      ("soil_rest_yielding_plain_nodes",
+                       lambda: ex.set_soil_plasticity(0.05, 1e-3, 0.0, H, initial_stress=rest, node_pass=1), True))
+    for label, setter, with_rest in configurations:
+        ex.set_state(ExplicitStepper.DISPLACEMENT, torch.zeros(P.dof_count, device=f"cuda:{device}"))
+        ex.set_state(ExplicitStepper.VELOCITY, torch.zeros(P.dof_count, device=f"cuda:{device}"))
+        setter()
+        us = timed_steps(ex, steps)
+        i = ex.plasticity_info()
+        b = i.plastic_elements * (64 + 4 + 4 + 4 + 64 + 16 + 48 + (48 if with_rest else 0)) + N * (12 + 8 + 12 + 12)
+        hi = b + (48 + 64) * i.yielded_elements
+        lines.append(dict(base, configuration=label, model=ex.plasticity_model(), step_us=us,
+                          plastic_elements=i.plastic_elements, affected_nodes=i.affected_nodes,
+                          yielded_elements=i.yielded_elements, device_bytes=i.bytes, added_us=us - plain, bytes_low=b,
+                          bytes_high=hi, estimate_us_low=1e6 * b / ceiling, estimate_us_high=1e6 * hi / ceiling))
+        ex.clear_plasticity()
+    ex.close()
+    sysm.close()
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", nargs="+", default=["c2", "c3", "c2:hex8"])
@@ -383,6 +440,7 @@ def main():
     ap.add_argument("--sources", action="store_true", help="the cost of load sources (see above)")
     ap.add_argument("--envelopes", action="store_true", help="the cost of the element monitors (see above)")
     ap.add_argument("--plasticity", action="store_true", help="the cost of J2 plasticity (see above)")
+    ap.add_argument("--soil-plasticity", action="store_true", help="the cost of the soil plasticity (see above)")
     ap.add_argument("--plain-only", action="store_true", help="--plasticity: the plain step alone")
     ap.add_argument("--repeats", type=int, default=5, help="--plasticity: timings of the plain step")
     ap.add_argument("--only", choices=["elastic", "yielding"], default=None,
@@ -393,14 +451,23 @@ def main():
                                                  "profiles/explicit_monitors.json, --sources: "
                                                  "profiles/explicit_sources.json)")
     a = ap.parse_args()
-    a.out = a.out or os.path.join(ROOT, "profiles", "explicit_plasticity.json" if a.plasticity else
+    a.out = a.out or os.path.join(ROOT, "profiles", "explicit_soil_plasticity.json" if a.soil_plasticity else
+                                  "explicit_plasticity.json" if a.plasticity else
                                   "explicit_envelopes.json" if a.envelopes else
                                   "explicit_sources.json" if a.sources else
                                   "explicit_monitors.json" if a.monitors else
                                   "explicit_absorbing.json" if a.absorbing else "explicit_c2.json")
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     if a.configs == ap.get_default("configs") and not a.envelopes:
-        a.configs = ["c2", "c3"] if a.monitors or a.sources or a.plasticity else ["c3"] if a.absorbing else a.configs
+        a.configs = ["c2", "c3"] if a.monitors or a.sources or a.plasticity or a.soil_plasticity else \
+            ["c3"] if a.absorbing else a.configs
+    for key in a.configs if a.soil_plasticity else []:
+        for d in measure_soil_plasticity(key, a.steps, a.device, a.repeats):
+            print(json.dumps(d), flush=True)
+            with open(a.out, "a") as f:
+                f.write(json.dumps(d) + "\n")
+    if a.soil_plasticity:
+        return
     for key in a.configs if a.plasticity else []:
         for d in measure_plasticity(key, a.steps, a.device, a.repeats, a.plain_only, a.only):
             print(json.dumps(d), flush=True)
