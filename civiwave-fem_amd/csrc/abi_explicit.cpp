@@ -280,15 +280,20 @@ int cwf_hip_explicit_advance(cwf_hip_explicit *t, uint64_t n_steps, cwf_explicit
     a.beta = t->beta;
     a.non_finite = t->non_finite;
     const bool dash = !t->dash_ids.empty();
-    a.dslot = dash ? t->dslot : nullptr;
-    a.dpq = dash ? t->dpq.get() : nullptr;
+    const ExplicitTies &tie = t->slots.tie;  // groups == 0: no set, no gather launch, the passes without TIE
+    a.dslot = t->slots.dslot;
+    a.dpq = t->slots.dpq;
     a.dC = dash ? t->dC : nullptr;
+    a.tg = tie.groups ? tie.tg : nullptr;
+    a.dgroup = t->slots.dgroup;
+    a.dash_slots = t->slots.dash_slots;
     a.alpha = t->alpha;
     const ExplicitPlasticity &pl = t->pl.dev;
     a.p = pl.slots ? pl.p : nullptr;
     const uint32_t blocks = explicit_update_blocks(s.N);
     ExplicitElementPass ep{};
-    // the launch order of a step: plasticity, operator, sources, update, energy fold, receiver record, element monitors
+    // the launch order of a step: plasticity, operator, sources, tie gather, update, energy fold, receiver record,
+    // element monitors
     for (uint64_t i = 0; i < n_steps; ++i)
     {
         if (pattern)
@@ -306,6 +311,8 @@ int cwf_hip_explicit_advance(cwf_hip_explicit *t, uint64_t n_steps, cwf_explicit
             parity_keff_ds(s, t->w, t->y, true, nullptr, st);
         if (t->src.dev.loaded)  // f_n of the loaded nodes into the force buffer the update pass reads
             explicit_sources(t->src.dev, (double)t->steps * t->dt, t->f, st);
+        if (tie.groups)  // g_G of every tie group from what the update pass is about to read
+            explicit_tie_gather(s, a, tie, st);
         const bool ledger_sampled = t->mon.arm(a, t->steps + 1);
         explicit_update(s, a, st);
         ++t->steps;
@@ -358,6 +365,8 @@ int cwf_hip_explicit_set_state(cwf_hip_explicit *t, int which, const float *in, 
     t->input_stale = true;
     HIPTRY(h, hipMemsetAsync(t->non_finite, 0, sizeof(uint32_t), h->stream));
     HIPTRY(h, hipStreamSynchronize(h->stream));
+    if (which == 1)  // a tie group keeps one velocity
+        return t->project_tied_velocity();
     return 0;
 }
 

@@ -18,53 +18,28 @@ int cwf_hip_explicit_set_dashpots(cwf_hip_explicit *t, uint64_t count, const uin
     if (count && (!node_ids || !C))
         return set_error(h, CWF_ERR_ARGUMENT, "null pointer");
     const uint64_t N = h->ds.N;
-    hipStream_t s = h->stream;
     const bool ledger = t->mon.ecum != nullptr;
-    if (count == 0)
-    {
-        HIPTRY(h, hipStreamSynchronize(s));
-        t->dpq.reset();
-        t->dash_ids.clear();
-        t->dash_C.clear();
-        return t->sync_ledger_C(ledger, t->dash_C, "explicit set_dashpots");
-    }
     // everything that can be refused, on the host, before anything changes
-    std::vector<uint32_t> slot(std::max<uint64_t>(N, 4), kNoDashpot);
-    if (int st = nodes_listed_once(h, "dashpot node", "", node_ids, count, slot, 0))
-        return st;
-    for (uint64_t i = 0; i < count; ++i)
-        slot[node_ids[i]] = (uint32_t)i;
-    std::vector<float> mass(std::max<uint64_t>(N, 4));  // the f32 lumped mass in the caller's order
-    if (int st = vec_out(h, h->ds.mass, mass.data(), CWF_PTR_HOST, 1))
-        return st;
-    HIPTRY(h, hipStreamSynchronize(s));
-    std::vector<double> pq(18 * count);
-    for (uint64_t i = 0; i < count; ++i)
-        if (const char *why = dashpot_update(C + 9 * i, (double)mass[node_ids[i]], t->alpha, t->dt, &pq[18 * i],
-                                             &pq[18 * i + 9]))
-            return set_error(h, CWF_ERR_ARGUMENT, why, "index=" + std::to_string(i));
-    DevicePtr<double> rec;  // the new set's records: the stepper's once everything else went well
-    if (rec.alloc(pq.size()) != hipSuccess)
-        return set_error(h, CWF_ERR_ALLOC, t->alloc_error);
-    if (!t->dslot)
-        if (int st = t->alloc(&t->dslot, slot.size()))
+    if (count)
+    {
+        std::vector<uint32_t> seen(std::max<uint64_t>(N, 4), kNoDashpot);
+        if (int st = nodes_listed_once(h, "dashpot node", "", node_ids, count, seen, 0))
             return st;
+    }
+    std::vector<uint32_t> ids(node_ids, node_ids + count);
     std::vector<double> given(C, C + 9 * count);
+    // the slots and records of the new dashpots and the ties in force (a refused matrix, a node's or a group's)
+    cwf_hip_explicit::SlotPlan plan;
+    if (int st = t->plan_slots(ids, given, t->tie_offsets, t->tie_ids, &plan))
+        return st;
     if (int st = t->sync_ledger_C(ledger, given, "explicit set_dashpots"))  // a ledger reads C as given
         return st;
-    // from here on a failure may leave the slot array half written: no dashpots until the next set
-    hipError_t e = hipMemcpyAsync(rec, pq.data(), pq.size() * sizeof(double), hipMemcpyHostToDevice, s);
-    const int st = e == hipSuccess ? slots_to_internal(*t, slot, t->dslot, nullptr) : 0;
-    if (e != hipSuccess || st)
+    if (int st = t->adopt_slots(plan, "explicit set_dashpots"))
     {
-        (void)hipStreamSynchronize(s);
-        t->dash_ids.clear();
-        t->dash_C.clear();
-        (void)t->sync_ledger_C(ledger, t->dash_C, "explicit set_dashpots");
-        return st ? st : hip_fail(h, e, "explicit set_dashpots");
+        (void)t->sync_ledger_C(ledger, t->dash_C, "explicit set_dashpots");  // the previous set's, with its slots
+        return st;
     }
-    t->dpq = std::move(rec);
-    t->dash_ids.assign(node_ids, node_ids + count);
+    t->dash_ids = std::move(ids);
     t->dash_C = std::move(given);
     return 0;
 }

@@ -567,6 +567,47 @@ std::string parse_config(const yl::Node &root)
               << jnum(guard({"geostatic", "surface"}, [&] { return geo["surface"].as_double(); }));
         j << "}";
     }
+    // tied (optional list; the key is emitted only when the document has it): tied lateral boundaries of the
+    // explicit stepper, an entry either {group, axis} (the group's nodes tied level by level along axis) or
+    // {pair: [A, B], axis} (the nodes of two opposite faces normal to axis tied pairwise)
+    const yl::Node &td = root["tied"];
+    if (td.defined())
+    {
+        if (!td.is_seq())
+            throw CfgError{"tied must be a sequence when present", {"tied"}};
+        j << ", \"tied\": [";
+        for (size_t i = 0; i < td.size(); ++i)
+        {
+            const yl::Node &e = td[i];
+            if (!e.is_map())
+                throw CfgError{"tied entry must be a map", {"tied", idx(i)}};
+            if (e["group"].defined() == e["pair"].defined())
+                throw CfgError{"tied entry needs either group or pair", {"tied", idx(i)}};
+            const double axis = e["axis"].defined()
+                                    ? guard({"tied", idx(i), "axis"}, [&] { return e["axis"].as_double(); })
+                                    : -1.0;
+            if (axis != 0.0 && axis != 1.0 && axis != 2.0)
+                throw CfgError{"tied.axis must be 0, 1 or 2", {"tied", idx(i), "axis"}};
+            j << (i ? ", " : "");
+            if (e["group"].defined())
+            {
+                if (!e["group"].is_scalar())
+                    throw CfgError{"tied.group must be a group name", {"tied", idx(i), "group"}};
+                j << "{\"group\": "
+                  << jstr(guard({"tied", idx(i), "group"}, [&] { return e["group"].as_string(); }));
+            }
+            else
+            {
+                const yl::Node &pr = e["pair"];
+                if (!pr.is_seq() || pr.size() != 2 || !pr[0].is_scalar() || !pr[1].is_scalar())
+                    throw CfgError{"tied.pair must be a sequence of two group names", {"tied", idx(i), "pair"}};
+                j << "{\"pair\": [" << jstr(guard({"tied", idx(i), "pair", idx(0)}, [&] { return pr[0].as_string(); }))
+                  << ", " << jstr(guard({"tied", idx(i), "pair", idx(1)}, [&] { return pr[1].as_string(); })) << "]";
+            }
+            j << ", \"axis\": " << (int)axis << "}";
+        }
+        j << "]";
+    }
     j << "}";
     return j.str();
 }

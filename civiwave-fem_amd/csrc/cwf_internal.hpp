@@ -810,9 +810,25 @@ struct ExplicitPass
     uint32_t esample;          // this step is sampled: ecur is written
     const float *p;            // plasticity's correction force (NULL: none, the instantiations without it run): the
                                // pass takes g = ((f - y) + p) / m in both forms
+    // tied boundaries (cwf_hip_explicit_set_ties). tg NULL: none, the instantiations without TIE run. With a set in
+    // force dslot and dpq cover the tied nodes too, and a slot below dash_slots carries a dashpot (the ledger's dC)
+    const double *tg;          // [3 groups] g_G of this step (explicit_tie_gather)
+    const uint32_t *dgroup;    // [slots] a slot's tie group, kNoDashpot for an untied dashpot node
+    uint32_t dash_slots;
 };
 constexpr uint32_t kNoDashpot = 0xFFFFFFFFu;
 void explicit_update(const DevSys &s, const ExplicitPass &a, hipStream_t st);
+// explicit_ties.hip: g_G = (sum over the members of ((f - y) + p)) / M_G of every tie group into tg, from what the
+// update pass of the same step is about to read (a: that pass's arguments); one wavefront per group
+struct ExplicitTies
+{
+    uint32_t groups;        // 0: no set
+    const uint32_t *toff;   // [groups + 1] a group's members
+    const uint32_t *tnode;  // [members] internal node, list order
+    const double *tmass;    // [groups] M_G
+    double *tg;             // [3 groups]
+};
+void explicit_tie_gather(const DevSys &s, const ExplicitPass &a, const ExplicitTies &t, hipStream_t st);
 inline uint32_t explicit_update_blocks(uint32_t N) { return (N + 255u) / 256u; }  // the update pass's workgroups
 // one sampled step's ledger row {kinetic, potential, work_cum, dissipated_cum} from the per-workgroup shares
 void explicit_energy_fold(uint32_t blocks, const double *ecum, const double *ecur, double *row, hipStream_t st);

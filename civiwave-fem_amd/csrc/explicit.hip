@@ -47,7 +47,12 @@ __device__ __forceinline__ float safe_cast(double v)
 // (72 B); per workgroup 16 B read and written every step, 16 B more written on a sampled step.
 // PLAS: plasticity (include/cwf_hip.h "Plasticity"): the node's correction force p (+12 B) enters g = ((f - y) + p) / m
 // in both forms; a stepper without plasticity launches the instantiations without it, whose code is what it was.
-template <bool FOLD, bool PATTERN, bool DAMP, bool DASH, bool MON, bool PLAS>
+// TIE: tied boundaries (include/cwf_hip.h "Tied boundaries"), only together with DASH: a tied node has a slot, whose
+// record holds its group's P_G | Q_G, and a.dgroup names the group (+4 B, a load that depends on the slot); its g is
+// the group's, three f64 from a.tg (explicit_tie_gather wrote them this step), instead of the node's own quotient. A
+// slot at or past a.dash_slots carries no dashpot, so the ledger reads no C for it. Launched only while a tie set is in
+// force; the instantiations without TIE are what they were.
+template <bool FOLD, bool PATTERN, bool DAMP, bool DASH, bool MON, bool PLAS, bool TIE = false>
 __global__ __launch_bounds__(kBlock) void k_explicit_update(DevSys s, ExplicitPass a)
 {
     const uint32_t gid = blockIdx.x * kBlock + threadIdx.x;
@@ -123,6 +128,14 @@ __global__ __launch_bounds__(kBlock) void k_explicit_update(DevSys s, ExplicitPa
             else
                 g[k] = ((double)f.c[k] - (double)y.c[k]) / m;
         }
+        if constexpr (TIE)
+        {
+            const uint32_t grp = a.dgroup[slot];
+            if (grp != kNoDashpot)
+#pragma unroll
+                for (int k = 0; k < 3; ++k)
+                    g[k] = a.tg[3ull * grp + k];
+        }
 #pragma unroll
         for (int k = 0; k < 3; ++k)
         {
@@ -195,7 +208,7 @@ __global__ __launch_bounds__(kBlock) void k_explicit_update(DevSys s, ExplicitPa
 #pragma unroll
             for (int k = 0; k < 3; ++k)
                 vb[k] = 0.5 * ((double)vn.c[k] + (double)v.c[k]);
-            const bool dashed = DASH && slot != kNoDashpot && a.dC;
+            const bool dashed = DASH && slot != kNoDashpot && a.dC && (!TIE || slot < a.dash_slots);
             double Cn[9];
             if (dashed)
 #pragma unroll
@@ -473,7 +486,21 @@ void launch_update(const DevSys &s, const ExplicitPass &a, hipStream_t st)
 {
     // a stepper without dashpots, and one without peak maps and ledger, launches the instantiations it always did
     const uint32_t grid = explicit_update_blocks(s.N);
-    if (a.peak || a.ecum)
+    if (a.tg)  // a tie set is in force: the slots cover its nodes
+    {
+        if (a.peak || a.ecum)
+        {
+            if (a.w != a.u)
+                k_explicit_update<FOLD, PATTERN, true, true, true, PLAS, true><<<grid, kBlock, 0, st>>>(s, a);
+            else
+                k_explicit_update<FOLD, PATTERN, false, true, true, PLAS, true><<<grid, kBlock, 0, st>>>(s, a);
+        }
+        else if (a.w != a.u)
+            k_explicit_update<FOLD, PATTERN, true, true, false, PLAS, true><<<grid, kBlock, 0, st>>>(s, a);
+        else
+            k_explicit_update<FOLD, PATTERN, false, true, false, PLAS, true><<<grid, kBlock, 0, st>>>(s, a);
+    }
+    else if (a.peak || a.ecum)
     {
         if (a.dslot)
         {

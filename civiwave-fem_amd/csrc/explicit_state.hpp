@@ -1,12 +1,14 @@
 // explicit_state.hpp -- what the explicit stepper's translation units share: the stepper itself (abi_explicit.cpp: the
 // core and advance) with its attachments (abi_explicit_loads.cpp: dashpots and load sources,
-// abi_explicit_monitors.cpp: node and element monitors, abi_explicit_plasticity.cpp), the staging helper every
+// abi_explicit_monitors.cpp: node and element monitors, abi_explicit_plasticity.cpp, abi_explicit_ties.cpp: tied
+// boundaries and the slot arrays they share with the dashpots), the staging helper every
 // set_* builds its device arrays with, and the two node-list helpers.
 #pragma once
 
 #include <cstdio>
 
 #include "abi_internal.hpp"
+#include "ties_tables.hpp"
 
 namespace cwf
 {
@@ -120,12 +122,43 @@ struct cwf_hip_explicit : cwf::TransientState
     uint32_t *non_finite = nullptr;
     std::vector<double> ctimes, cvalues;  // set_load_curve
     double last_scale = 0.0;              // c(t) of the last step taken (get_state 4 with a pattern)
-    // set_dashpots: the caller's ids and matrices as given; on the device a u32 slot per node (internal order,
-    // allocated at the first set) and the P | Q records of the current set. Empty ids: no dashpots.
+    // set_dashpots: the caller's ids and matrices as given. Empty ids: no dashpots.
     std::vector<uint32_t> dash_ids;
     std::vector<double> dash_C;
-    uint32_t *dslot = nullptr;
-    cwf::DevicePtr<double> dpq;
+    // set_ties: the groups as given (offsets [groups + 1], ids). Empty ids: no ties.
+    std::vector<uint64_t> tie_offsets;
+    std::vector<uint32_t> tie_ids;
+    // What the update pass reads of dashpots and ties, one set of arrays for both (ties_tables.hpp has the layout): a
+    // u32 slot per node (internal order), the slots' P | Q records, and with ties the slots' group words, the groups'
+    // CSR, their masses and g_G. plan_slots / adopt_slots are its only owners: set_dashpots and set_ties each call
+    // them with what they are about to put in force (their own new set and the other's current one), so either call
+    // order ends in the same arrays. plan_slots refuses on the host and changes nothing; adopt_slots stages the new
+    // arrays before the old ones go, and a failure (reported as `what`) leaves the old ones.
+    struct Slots
+    {
+        uint32_t *dslot = nullptr;
+        double *dpq = nullptr;
+        uint32_t *dgroup = nullptr;
+        uint32_t slots = 0, dash_slots = 0;
+        cwf::ExplicitTies tie{};
+        uint64_t members = 0, dashed_groups = 0, bytes = 0;
+        std::vector<void *> held;
+        void release(cwf::DeviceArena &mem) { cwf::ArenaStage::release(mem, *this); }
+    } slots;
+    struct SlotPlan  // the host side of a new set of slot arrays
+    {
+        cwf::TieSlots tab;
+        std::vector<double> pq;     // [18 slots]
+        std::vector<double> tmass;  // [groups]
+        std::vector<uint64_t> offsets;
+        std::vector<uint32_t> ids;
+        uint64_t dashed_groups = 0;
+    };
+    int plan_slots(const std::vector<uint32_t> &dash, const std::vector<double> &C, const std::vector<uint64_t> &offsets,
+                   const std::vector<uint32_t> &ids, SlotPlan *plan);
+    int adopt_slots(SlotPlan &plan, const char *what);
+    // v of every tie group replaced by its mass-weighted mean (set_ties, and set_state(1) while a set is in force)
+    int project_tied_velocity();
     // The ledger's slot-indexed copy of the dashpot matrices (arena): present iff a ledger and dashpots are both set.
     // sync_ledger_C is its only owner: set_dashpots and set_monitors call it with what they are about to put in force
     // (a ledger or not, the matrices as given), before they change anything else. The new copy is staged before the

@@ -219,6 +219,8 @@ void build(cwf_scenario &sc, const std::string &cfg_path)
     sc.cfg = yl::parse(json);
     if (sc.cfg["absorbing"].defined())  // the scenario driver steps by Newmark, whose K_eff carries no dashpots
         throw ScenErr{CWF_ERR_UNSUPPORTED, "absorbing boundaries need the explicit integrator", "absorbing"};
+    if (sc.cfg["tied"].defined())  // ... nor ties
+        throw ScenErr{CWF_ERR_UNSUPPORTED, "tied boundaries need the explicit integrator", "tied"};
     for (size_t i = 0; i < sc.cfg["materials"].size(); ++i)  // ... and whose materials are linear elastic
         if (sc.cfg["materials"][i]["yield_stress"].defined() || sc.cfg["materials"][i]["friction_angle"].defined())
             throw ScenErr{CWF_ERR_UNSUPPORTED, "plastic materials need the explicit integrator", "materials"};

@@ -145,6 +145,11 @@ class ExplicitSourceInfoC(C.Structure):
                 ("loaded_nodes", C.c_uint64), ("curve_points", C.c_uint64), ("device_bytes", C.c_uint64)]
 
 
+class ExplicitTieInfoC(C.Structure):
+    _fields_ = [("group_count", C.c_uint64), ("member_count", C.c_uint64), ("dashed_groups", C.c_uint64),
+                ("device_bytes", C.c_uint64)]
+
+
 class ExplicitPlasticityDescC(C.Structure):
     _fields_ = [("yield_stress", C.c_void_p), ("hardening", C.c_void_p), ("material_count", C.c_uint64)]
 
@@ -266,6 +271,9 @@ def load() -> C.CDLL:
         "cwf_hip_explicit_time": ([P, P, P], i32),
         "cwf_hip_explicit_set_dashpots": ([P, u64, P, P], i32),
         "cwf_hip_explicit_get_dashpots": ([P, P, P, P], i32),
+        "cwf_hip_explicit_set_ties": ([P, u64, P, P], i32),
+        "cwf_hip_explicit_get_ties": ([P, P, P, P, P], i32),
+        "cwf_hip_explicit_tie_info": ([P, P], i32),
         "cwf_hip_explicit_set_monitors": ([P, P], i32),
         "cwf_hip_explicit_reset_monitors": ([P], i32),
         "cwf_hip_explicit_monitor_info": ([P, P], i32),
@@ -291,6 +299,9 @@ def load() -> C.CDLL:
         "cwf_soil_dp_from_mohr_coulomb": ([f64, f64, f64, i32, P], i32),
         "cwf_soil_geostatic_stress": ([u64, P, P, u64, P, P, f64, i32, P, u64, P, P], i32),
         "cwf_explicit_dashpot_update": ([P, f64, f64, f64, P, P], i32),
+        "cwf_tie_levels": ([u64, P, u64, P, i32, f64, P, P, P], i32),
+        "cwf_tie_periodic": ([u64, P, u64, P, u64, P, i32, f64, P, P, P], i32),
+        "cwf_tie_merge": ([u64, u64, P, P, P, P, P], i32),
         "cwf_absorbing_dashpots": ([u64, P, u64, C.c_uint32, P, P, u64, P, P, P, u64, C.c_uint32, P, P, P, P], i32),
         "cwf_absorbing_incident_plane": ([u64, P, u64, C.c_uint32, P, P, u64, P, P, P, u64, C.c_uint32, P, P, P, P, P, P,
                                           P, P, P], i32),

@@ -16,7 +16,7 @@ from . import _lib
 from .pcg import Expected
 from .physics import (AbsorbingBoundary, Assignment, Config, Curve, Damping, DirichletFix, Geostatic, IncidentWave,
                       Loads, Material, OutputSettings, PointLoad, PrecisionSettings, SolverSettings, SurfaceTraction,
-                      TimeSettings)
+                      TiedBoundary, TimeSettings)
 
 
 @dataclass
@@ -65,6 +65,8 @@ def _from_json(d: dict) -> Config:
                                                     for k in ("propagation", "origin"))))
                    for a in d.get("absorbing", [])],
         geostatic=_geostatic(d["geostatic"], len(d["materials"])) if "geostatic" in d else None,
+        tied=[TiedBoundary(int(t["axis"]), t.get("group"), tuple(t["pair"]) if "pair" in t else None)
+              for t in d.get("tied", [])],
     )
 
 

@@ -169,6 +169,14 @@ class SourceInfo:
 
 
 @dataclass
+class TieInfo:
+    group_count: int
+    member_count: int
+    dashed_groups: int
+    device_bytes: int
+
+
+@dataclass
 class PlasticityInfo:
     plastic_elements: int
     affected_nodes: int
@@ -323,6 +331,36 @@ class ExplicitStepper(TransientState):
 
     def clear_dashpots(self):
         self._check(_lib.load().cwf_hip_explicit_set_dashpots(self._ex, 0, None, None))
+
+    # ---- tied boundaries (include/cwf_hip.h "Tied boundaries") ----
+    def set_ties(self, offsets, node_ids):
+        """Tie groups (cwf.ties.levels / periodic / merge): group g holds node_ids[offsets[g]:offsets[g + 1]], disjoint
+        groups of at least two nodes with equal constraint masks, which then share one velocity. Replaces the previous
+        set, which stays in force if this one is refused (RuntimeError); every member's v becomes its group's
+        mass-weighted mean. u, the step count, loads, dashpots, monitors and plasticity are kept."""
+        off = np.ascontiguousarray(offsets, np.uint64).reshape(-1)
+        ids = np.ascontiguousarray(node_ids, np.uint32).reshape(-1)
+        if off.size == 0 or int(off[-1]) != ids.size:
+            raise ValueError("offsets must hold one entry more than there are groups and end at len(node_ids)")
+        self._check(_lib.load().cwf_hip_explicit_set_ties(self._ex, off.size - 1, _lib.ptr(off), _lib.ptr(ids)))
+
+    def get_ties(self):
+        """-> (offsets u64 [groups + 1], node_ids u32 [members]) as they were set; ([0], []) without a set."""
+        g, m = C.c_uint64(), C.c_uint64()
+        self._check(_lib.load().cwf_hip_explicit_get_ties(self._ex, C.byref(g), C.byref(m), None, None))
+        off, ids = np.zeros(g.value + 1, np.uint64), np.zeros(m.value, np.uint32)
+        if g.value:
+            self._check(_lib.load().cwf_hip_explicit_get_ties(self._ex, C.byref(g), C.byref(m), _lib.ptr(off),
+                                                              _lib.ptr(ids)))
+        return off, ids
+
+    def clear_ties(self):
+        self._check(_lib.load().cwf_hip_explicit_set_ties(self._ex, 0, None, None))
+
+    def tie_info(self) -> TieInfo:
+        i = _lib.ExplicitTieInfoC()
+        self._check(_lib.load().cwf_hip_explicit_tie_info(self._ex, C.byref(i)))
+        return TieInfo(int(i.group_count), int(i.member_count), int(i.dashed_groups), int(i.device_bytes))
 
     # ---- load sources (include/cwf_hip.h "Load sources") ----
     def set_sources(self, sources):

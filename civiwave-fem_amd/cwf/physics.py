@@ -112,6 +112,15 @@ class AbsorbingBoundary:
 
 
 @dataclass
+class TiedBoundary:
+    """One entry of a scenario's ``tied:`` list (cwf.ties): the nodes of ``group`` tied level by level along ``axis``, or
+    the nodes of the two opposite faces ``pair`` (normal to ``axis``) tied pairwise."""
+    axis: int
+    group: Optional[str] = None
+    pair: Optional[tuple] = None
+
+
+@dataclass
 class Geostatic:
     """The stress at rest of a layered deposit for the soil plasticity (cwf.soil.geostatic_stress)."""
     gravity: float = 9.81
@@ -135,6 +144,7 @@ class Config:
     output: OutputSettings = field(default_factory=OutputSettings)
     absorbing: list = field(default_factory=list)  # [AbsorbingBoundary] (explicit integrator only)
     geostatic: Optional[Geostatic] = None  # explicit integrator only, with soil materials
+    tied: list = field(default_factory=list)  # [TiedBoundary] (explicit integrator only)
 
 
 # ---- materials.hpp -----------------------------------------------------------------------

@@ -21,6 +21,9 @@ A scenario's ``absorbing:`` entries (explicit only) put viscous dashpots on thei
 ``incident: {direction, velocity_curve}`` feeds that curve in through the dashpots as an incident wave. With
 ``propagation: [x, y, z]`` (and ``origin``) the wave is a plane wave travelling obliquely along it, each boundary node
 with its own arrival delay; such entries, and entries naming different curves, run as the stepper's load sources.
+A top-level ``tied:`` list (explicit only) ties lateral boundaries: ``{group: NAME, axis: k}`` ties the group's nodes
+level by level along axis k (a laminar box), ``{pair: [A, B], axis: k}`` the nodes of two opposite faces normal to axis
+k pairwise (periodic); all entries are merged into one set, applied after the dashpots.
 ``--trace-every K``, ``--peaks`` and ``--energy-every K`` (explicit only) turn on the stepper's monitors: receiver
 traces at ``output.probes`` every K explicit steps (``probes/traces.csv``), the peak |u|, |v|, |a| maps
 (``monitors/peaks.npy``, [N,3]) and the energy ledger (``monitors/energy.csv``), written after the last frame. The
@@ -89,6 +92,8 @@ def run_scenario(cfg_path: str, steps: int, out_dir: str | None, mode: int = _li
     cfg, m, P, materials = load_scenario(cfg_path, allow_hex8=mode == _lib.MODE_FAST)
     if cfg.absorbing:
         raise ScenarioError("absorbing boundaries need the explicit integrator")
+    if cfg.tied:
+        raise ScenarioError("tied boundaries need the explicit integrator")
     if any(x.yield_stress > 0.0 or x.friction_angle is not None for x in cfg.materials):
         raise ScenarioError("plastic materials need the explicit integrator")
     st = Stepper(P, materials, compute_rayleigh(cfg.damping), cfg.solver, cfg.time, mode=mode, device=device)
@@ -192,6 +197,7 @@ def run_scenario_explicit(cfg_path: str, steps: int, out_dir: str | None, mode: 
     wall0, last = time.perf_counter(), None
     try:
         absorbing_nodes = set_absorbing(st, cfg, m, P)
+        tied = set_tied(st, cfg, m, P)  # dashpots first, ties second; either order gives the same arrays
         soil_model = any(x.friction_angle is not None for x in cfg.materials)
         plastic = soil_model or any(x.yield_stress > 0.0 for x in cfg.materials)
         if cfg.geostatic is not None and not soil_model:
@@ -261,7 +267,7 @@ def run_scenario_explicit(cfg_path: str, steps: int, out_dir: str | None, mode: 
                     integrator="explicit", explicit_steps=tel.steps, steps_per_frame=per_frame, dt=tel.dt,
                     critical_dt=tel.critical_dt, lambda_max=tel.lambda_max, wall_s=wall, final_time=tel.time,
                     last=last, mode="fast" if mode == _lib.MODE_FAST else "parity", absorbing_nodes=absorbing_nodes,
-                    **sources, **written)
+                    **tied, **sources, **written)
     finally:
         if om is not None:
             om.close()
@@ -385,6 +391,44 @@ def absorbing_setup(cfg, m, P):
         return out
     base = pack.assemble_load_vector(m, cfg, P.lumped_mass64)
     return AbsorbingSetup((ids, Cn, base, pattern, cfg.curves[names[0]]))
+
+
+def tied_setup(cfg, m, P):
+    """The scenario's ``tied:`` entries merged into one tie set -> (offsets, node_ids): a ``group`` entry by levels
+    along its axis, a ``pair`` entry pairwise across the two faces; groups that share nodes (the edges of an x pair and a
+    y pair) become one."""
+    import numpy as np
+
+    from . import ties
+
+    def nodes_of(i, name):
+        gid = m.group_names.get(name)
+        if gid is None or gid not in m.node_groups:
+            raise ScenarioError(f"tied [{i}]: unknown group '{name}'")
+        return np.asarray(m.node_groups[gid], np.uint32)
+
+    sets = []
+    for i, entry in enumerate(cfg.tied):
+        try:
+            if entry.group is not None:
+                sets.append(ties.levels(m.coords, nodes_of(i, entry.group), entry.axis))
+            else:
+                sets.append(ties.periodic(m.coords, nodes_of(i, entry.pair[0]), nodes_of(i, entry.pair[1]), entry.axis))
+        except ValueError as e:
+            raise ScenarioError(f"tied [{i}]: {e.args[0] if e.args else e}") from None
+    return ties.merge(P.node_count, *sets)
+
+
+def set_tied(st, cfg, m, P) -> dict:
+    """Put the scenario's tied boundaries on an ExplicitStepper -> the summary's entries ({} without ``tied:``)."""
+    if not cfg.tied:
+        return {}
+    off, ids = tied_setup(cfg, m, P)
+    try:
+        st.set_ties(off, ids)
+    except RuntimeError as e:
+        raise ScenarioError(f"tied: {e}") from None
+    return dict(tie_groups=int(off.size - 1), tied_nodes=int(ids.size))
 
 
 def set_absorbing(st, cfg, m, P) -> int:

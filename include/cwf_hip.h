@@ -443,6 +443,44 @@ int cwf_hip_stepper_time(const cwf_hip_stepper *st, double *current_time, double
  * (-1, 1]. So critical_dt and lambda_max are those of the stepper without dashpots, and dashpots scaled by 1e4 run at
  * the same step (tests/test_gpu_absorbing.py).
  *
+ * Tied boundaries (cwf_hip_explicit_set_ties): the lateral boundary of a soil model. A tie set is a list of disjoint
+ * groups of at least two nodes; the members of a group share one velocity in all three components -- every boundary
+ * node of one elevation (a laminar shear box), or a node and its partner on the opposite face (periodic). With the
+ * lumped mass the constraint has a closed form: the group moves as one node of mass M_G = sum m_i, net force
+ * F_G = sum ((f_i - y_i) + p_i) and dashpot matrix C_G = sum C_i (p_i: plasticity's correction force where a set is in
+ * force; C_i = 0 for a member without a dashpot). Per step, in fp64 without fused multiply-adds:
+ *     term_j = ((double)f_j - (double)y_j) + (double)p_j     per member j and component (no "+ p" without plasticity);
+ *                                                            f, y and p exactly as the update pass of the step reads them;
+ *                                                            0 for a constrained component (the group has one mask), so
+ *                                                            g_G is 0 there and no constrained row reaches a free one
+ *     S      = the sum of the group's terms                  in the order below
+ *     g_G    = S / M_G                                       M_G = (double)m_0, then M_G + (double)m_j in member order
+ *     v_new_k = f32(((P_k0 v_0 + P_k1 v_1) + P_k2 v_2) + ((Q_k0 g_G0 + Q_k1 g_G1) + Q_k2 g_G2))     per member, v its own
+ *     u_new_k = f32(u_k + dt v_new_k)                        then constrained DOFs as above
+ * with P | Q = cwf_explicit_dashpot_update(C_G, M_G, alpha_R, dt), the rows associated as the dashpot rows above; C_G is
+ * summed entry by entry in member order from the first member that has a dashpot. A group without dashpot members takes
+ * the same rows with C_G = 0, P = c1 I and Q = c2 I up to the rounding of that function's products (the library's values
+ * are the scheme's, not c1 and c2). Members that hold equal v run the same operations on the same operands, so they
+ * keep bitwise equal v, and u_i - u_j stays what it was when the set was put in force: the tie constrains velocity.
+ * The members of a group must have the same constraint mask; the mask wins on constrained components, as for dashpots.
+ * Summation order of S, a function of the member count c alone (members in the order they were listed):
+ *     c <= 8:  acc = 0, then acc = acc + term_j for j = 0 .. c - 1;
+ *     c > 8:   64 lane sums L_l = 0, L_l = L_l + term_j for j = l, l + 64, ... (a lane without members keeps 0), then
+ *              L_l = L_l + L_(l + s) for l < s, s = 32, 16, 8, 4, 2, 1; S = L_0.
+ * One gather kernel per step forms g_G (one 64-lane wavefront per group, no atomics) after the operator launch, the
+ * plasticity passes and the load sources' kernel and before the update pass, which then reads three f64 per tied node
+ * instead of forming the node's own quotient. set_ties replaces every member's v by the group's mass-weighted mean
+ * f32((sum (double)m_i (double)v_i) / M_G), the sum from the first term in member order (constrained components stay
+ * 0), on the host; cwf_hip_explicit_set_state(1) does the same while a set is in force, which costs it three more
+ * device round trips (mass, mask and v out, v in again). set_ties and set_dashpots read the mass back and rebuild and
+ * upload every slot and tie array while a tie set is in force: set-time costs, none per step.
+ * The critical step is unchanged: the tied system is (T^T K T, T^T M T) for the 0/1 map T from group DOFs to node DOFs,
+ * whose eigenvalues are Rayleigh quotients of (K, M) on range(T), so its lambda_max does not exceed the untied one and
+ * the stepper's dt stays valid without a new power iteration; C_G enters implicitly, as C_n does. The constraint
+ * forces sum to zero within a group and its members share vbar, so they do no work: the energy ledger's per-node terms
+ * stand as they are, and a member's dissipation term uses its own C_i as given to set_dashpots, never C_G.
+ * A stepper without ties launches exactly the kernels it launches without this section.
+ *
  * Monitors (cwf_hip_explicit_set_monitors): what a wave run takes home, recorded on the device while advance() queues
  * its steps. "Step count n" is the number of steps since create; after the update that makes it n the state is u_n and
  * v_(n-1/2). A stepper without monitors launches exactly the kernels it launches without this section.
@@ -659,6 +697,32 @@ int cwf_hip_explicit_time(const cwf_hip_explicit *ex, double *current_time, doub
 int cwf_hip_explicit_set_dashpots(cwf_hip_explicit *ex, uint64_t count, const uint32_t *node_ids, const double *C);
 /* The set in force as it was given; node_ids and C are nullable (count only). */
 int cwf_hip_explicit_get_dashpots(cwf_hip_explicit *ex, uint64_t *count, uint32_t *node_ids, double *C);
+/* Tied boundaries of the scheme above: group g holds the nodes node_ids[offsets[g] .. offsets[g + 1]) (the caller's
+ * numbering); group_count == 0 removes the set (the stepper then launches what a stepper that never had ties launches).
+ * u, the step count, the load state, dashpots, monitors and plasticity are kept; v is projected as stated above. A tied
+ * node owns a slot as a dashpot node does: the u32 slot per node and the 144-byte P | Q records are one set of arrays
+ * for both (slots of the dashpot nodes first, in their order, then the other tied nodes in list order), with a u32
+ * group word per slot, the groups' CSR in the handle's node order (4 B per group and per member), M_G and g_G (8 + 24 B
+ * per group); set_dashpots and set_ties rebuild them together, so either call order gives the same arrays. Everything
+ * refusable is checked on the host before anything changes; all refusals are CWF_ERR_ARGUMENT and leave the previous
+ * set in force: "tie offsets must ascend from 0" {group=<g>}, "tie group needs at least two nodes" {group=<g>,
+ * nodes=<n>}, "tied node out of range" / "tied node listed twice" {index=<i>, node=<id>} (across all groups), "tied
+ * nodes differ in their constraints" {group=<g>, node=<id>, mask=<m>, first_mask=<m0>}, and what
+ * cwf_explicit_dashpot_update refuses of a group's C_G {group=<g>} (set_dashpots answers the same while ties are in
+ * force). */
+typedef struct cwf_explicit_tie_info
+{
+    uint64_t group_count;
+    uint64_t member_count;
+    uint64_t dashed_groups; /* groups with at least one dashpot member */
+    uint64_t device_bytes;  /* the slot arrays, records and tie arrays in the stepper's arena; 0 without a set */
+} cwf_explicit_tie_info;
+int cwf_hip_explicit_set_ties(cwf_hip_explicit *ex, uint64_t group_count, const uint64_t *offsets /* [group_count + 1] */,
+                              const uint32_t *node_ids);
+/* The set in force as it was given; offsets [group_count + 1] and node_ids [member_count] are nullable (counts only). */
+int cwf_hip_explicit_get_ties(cwf_hip_explicit *ex, uint64_t *group_count, uint64_t *member_count, uint64_t *offsets,
+                              uint32_t *node_ids);
+int cwf_hip_explicit_tie_info(cwf_hip_explicit *ex, cwf_explicit_tie_info *out);
 /* Monitors of the scheme above. Replaces the previous set; desc NULL or all zero removes everything and frees the
  * buffers (the stepper then launches what a stepper that never had monitors launches). u, v, the step count, loads and
  * dashpots are kept; peaks, cumulative sums and sample counts start at zero. May be called between advance calls. All
@@ -902,6 +966,27 @@ int cwf_soil_geostatic_stress(uint64_t element_count, const double *centroids, c
  * below -1e-12 in units of the trace: "dashpot matrix is not positive semidefinite"), for mass <= 0 ("dashpot node
  * mass must be positive") and for a negative or non-finite alpha or dt. */
 int cwf_explicit_dashpot_update(const double C[9], double mass, double alpha, double dt, double P[9], double Q[9]);
+/* Host only, no GPU: tie sets for cwf_hip_explicit_set_ties from the node coordinates (f64 [3 node_count]). The
+ * results go to *group_count, offsets (room for one more than the largest possible group count) and out_ids. tolerance
+ * is relative to the model's extent along the axis compared; 0 means 1e-9. Errors are CWF_ERR_ARGUMENT in the thread's
+ * record: "tied node out of range" / "tied node listed twice" {index, node}, "tie axis must be 0, 1 or 2" {axis},
+ * "tie tolerance must be finite and not negative", "null pointer".
+ * cwf_tie_levels (the laminar box): the listed nodes (distinct) are sorted by their coordinate along `axis`; a level is
+ * the run of nodes within the tolerance of its lowest node, and each level of at least two nodes becomes one group.
+ * Groups ascend in coordinate, members in node id. offsets [count / 2 + 1], out_ids [count].
+ * cwf_tie_periodic: each node of face A is paired with the one node of face B whose coordinates in the two axes other
+ * than `axis` agree within the tolerance; group i is {ids_a[i], its partner}. A node of either face without exactly one
+ * partner is refused: "periodic faces do not match" {node, face=A|B}. offsets [count_a + 1], out_ids [2 count_a].
+ * cwf_tie_merge: groups that may share nodes (the edges that an x-pair set and a y-pair set share) become the disjoint
+ * groups of their union (union-find): groups ordered by smallest member, members ascending, a group of one node
+ * dropped. offsets [members / 2 + 1], out_ids [members]; also "tie offsets must ascend from 0" {group}. */
+int cwf_tie_levels(uint64_t node_count, const double *coords, uint64_t count, const uint32_t *node_ids, int axis,
+                   double tolerance, uint64_t *group_count, uint64_t *offsets, uint32_t *out_ids);
+int cwf_tie_periodic(uint64_t node_count, const double *coords, uint64_t count_a, const uint32_t *ids_a,
+                     uint64_t count_b, const uint32_t *ids_b, int axis, double tolerance, uint64_t *group_count,
+                     uint64_t *offsets, uint32_t *out_ids);
+int cwf_tie_merge(uint64_t node_count, uint64_t in_groups, const uint64_t *in_offsets, const uint32_t *in_ids,
+                  uint64_t *group_count, uint64_t *offsets, uint32_t *out_ids);
 /* Host only, no GPU: the viscous-boundary matrices of a face list. coords f64 [3 node_count]; connectivity u32
  * [nodes_per_element (4: tet4, 8: hex8 in Gmsh corner order) x element_count]; element_material [element_count] indexes
  * rho, lame_lambda, lame_mu [material_count]; faces u32 [nodes_per_face (3 or 4) x face_count]. Every face must be a

@@ -6,6 +6,7 @@
     python tools/explicit_bench.py --monitors [--configs c2 c3] [--steps 2000]
     python tools/explicit_bench.py --sources [--configs c2 c3] [--steps 2000]
     python tools/explicit_bench.py --envelopes [--configs c2 c3 c2:hex8] [--steps 2000]
+    python tools/explicit_bench.py --ties [--configs c2 c3] [--steps 2000]
     python tools/explicit_bench.py --plasticity [--plain-only] [--repeats 5] [--configs c2 c3] [--steps 2000]
     python tools/explicit_bench.py --soil-plasticity [--repeats 5] [--configs c2 c3] [--steps 2000]
 
@@ -37,6 +38,12 @@ wave as a source on the base, with an oblique plane-wave source on the five face
 zero delay (a three-component record), and after the set is removed; next to the loaded nodes, the entries and the bytes
 the source kernel moves by its layout (per loaded node 4 B node + 8 B offsets + 12 B f_ext + 12 B stored, per entry a
 32-B record + 8 B curve directory; the curve's knots are shared and stay in L2).
+
+--ties: the cost of tied lateral boundaries (include/cwf_hip.h "Tied boundaries"). Per config one line, appended to
+profiles/explicit_ties_c2_c3.json, one stepper on one FAST handle of the unconstrained block: step_us of the plain step,
+with the four lateral faces tied by level (one group per node plane), with the two face pairs tied periodically (pairs
+and the vertical edges' groups of 4), and after clear_ties again; next to them the groups, members, the largest group,
+the set's device bytes and the host time of building and of setting each set.
 
 --envelopes: the cost of the element monitors (include/cwf_hip.h "Element monitors"). Per config one line, appended to
 profiles/explicit_envelopes.json, one stepper on one FAST handle: step_us without element monitors, with each envelope
@@ -184,6 +191,50 @@ def measure_absorbing(key, steps, device):
     out["absorbing_over_plain"] = out["step_us_absorbing"] / out["step_us"]
     out["update_bytes_per_node"] = 80
     out["update_bytes_per_node_absorbing"] = 84 + 144 * out["dashpot_share"]
+    ex.close()
+    sysm.close()
+    return out
+
+
+def measure_ties(key, steps, device):
+    """--ties: the plain step, the step with the four lateral faces tied by level (a laminar box: one large group per
+    node plane) and the step with the two face pairs tied periodically (pairs, and the vertical edges' groups of 4),
+    all in one run on one handle. The block is run unconstrained, so that every group has one mask."""
+    import dataclasses
+
+    import numpy as np
+
+    from cwf import ties
+
+    name, _, element = key.partition(":")
+    case = scenarios.config_case(name, element=element or "tet4")
+    P = dataclasses.replace(case.packing, bc_mask=np.zeros_like(case.packing.bc_mask))
+    X = case.mesh.coords
+    lo, hi = X.min(0), X.max(0)
+    face = {(a, e): np.nonzero(X[:, a] == (lo, hi)[e][a])[0] for a in (0, 1) for e in (0, 1)}
+    side = np.unique(np.concatenate(list(face.values())))
+    t0 = time.perf_counter()
+    level = ties.levels(X, side, 2)
+    pairs = ties.merge(P.node_count, ties.periodic(X, face[0, 0], face[0, 1], 0), ties.periodic(X, face[1, 0], face[1, 1], 1))
+    out = dict(config=key, name=case.name, nodes=P.node_count, steps=steps, tie_sets_s=time.perf_counter() - t0)
+    sysm = pcg.MatrixFreeSystem.from_packing(P, case.materials, 1.0, 0.0, mode=_lib.MODE_FAST, device=device)
+    out["kernel"] = (_lib.load().cwf_hip_system_keff_kernel(sysm.handle()) or b"").decode()
+    ex = ExplicitStepper(P, case.materials, RayleighCoefficients(0.0, 0.0), system=sysm)
+    out["dt"] = ex.telemetry().dt
+    out["step_us"] = timed_steps(ex, steps)
+    for tag, (off, ids) in (("levels", level), ("periodic", pairs)):
+        t0 = time.perf_counter()
+        ex.set_ties(off, ids)
+        out[f"set_ties_s_{tag}"] = time.perf_counter() - t0
+        info = ex.tie_info()
+        sizes = np.diff(off.astype(np.int64))
+        out[f"groups_{tag}"], out[f"members_{tag}"] = info.group_count, info.member_count
+        out[f"largest_group_{tag}"], out[f"device_bytes_{tag}"] = int(sizes.max()), info.device_bytes
+        out[f"tied_share_{tag}"] = info.member_count / P.node_count
+        out[f"step_us_{tag}"] = timed_steps(ex, steps)
+        out[f"{tag}_over_plain"] = out[f"step_us_{tag}"] / out["step_us"]
+    ex.clear_ties()
+    out["step_us_cleared"] = timed_steps(ex, steps)
     ex.close()
     sysm.close()
     return out
@@ -438,6 +489,7 @@ def main():
     ap.add_argument("--absorbing", action="store_true", help="the cost of dashpots on five faces (see above)")
     ap.add_argument("--monitors", action="store_true", help="the cost of the monitors (see above)")
     ap.add_argument("--sources", action="store_true", help="the cost of load sources (see above)")
+    ap.add_argument("--ties", action="store_true", help="the cost of tied lateral boundaries: by level and periodic")
     ap.add_argument("--envelopes", action="store_true", help="the cost of the element monitors (see above)")
     ap.add_argument("--plasticity", action="store_true", help="the cost of J2 plasticity (see above)")
     ap.add_argument("--soil-plasticity", action="store_true", help="the cost of the soil plasticity (see above)")
@@ -455,11 +507,12 @@ def main():
                                   "explicit_plasticity.json" if a.plasticity else
                                   "explicit_envelopes.json" if a.envelopes else
                                   "explicit_sources.json" if a.sources else
+                                  "explicit_ties_c2_c3.json" if a.ties else
                                   "explicit_monitors.json" if a.monitors else
                                   "explicit_absorbing.json" if a.absorbing else "explicit_c2.json")
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     if a.configs == ap.get_default("configs") and not a.envelopes:
-        a.configs = ["c2", "c3"] if a.monitors or a.sources or a.plasticity or a.soil_plasticity else \
+        a.configs = ["c2", "c3"] if a.monitors or a.sources or a.plasticity or a.soil_plasticity or a.ties else \
             ["c3"] if a.absorbing else a.configs
     for key in a.configs if a.soil_plasticity else []:
         for d in measure_soil_plasticity(key, a.steps, a.device, a.repeats):
@@ -476,6 +529,7 @@ def main():
     for key in [] if a.plasticity else a.configs:
         line = json.dumps(measure_envelopes(key, a.steps, a.device) if a.envelopes else
                           measure_sources(key, a.steps, a.device) if a.sources else
+                          measure_ties(key, a.steps, a.device) if a.ties else
                           measure_monitors(key, a.steps, a.device) if a.monitors else
                           measure_absorbing(key, a.steps, a.device) if a.absorbing else
                           measure(key, a.steps, a.newmark_steps, a.device))
