@@ -1,6 +1,6 @@
 """Shared by the absorbing-boundary tests: the 1-D soil column, the scheme of include/cwf_hip.h with dashpots in
-numpy (float32 state as the stepper keeps it, or all-float64 with the dense K), the update matrices by the library,
-and the energy of a state."""
+all-float64 numpy with the dense K (the float32 restatement is explicit_common.scheme_steps), the update matrices by
+the library, and the energy of a state."""
 import functools
 import math
 from dataclasses import replace
@@ -9,14 +9,10 @@ import numpy as np
 
 from cwf import _lib, absorbing, meshgen, pack, scenarios
 from cwf.physics import Assignment, DirichletFix, compute_lame
+from explicit_common import constrained, dashpot_rows  # this module's own uses
 from helpers import dense_stiffness
 
-DOF_BITS = np.array([1, 2, 4], np.uint32)
 SOIL = scenarios.LAYER_MATERIALS[1]  # m1: E 3 GPa, nu 0.3, rho 1800
-
-
-def constrained(P):
-    return (np.repeat(P.bc_mask, 3) & np.tile(DOF_BITS, P.node_count)) != 0
 
 
 def wave_speed(material, kind):
@@ -34,40 +30,6 @@ def update_matrices(Cn, mass32, alpha, dt):
                                            float(dt), _lib.ptr(P[i]), _lib.ptr(Q[i]))
         assert rc == 0, (i, _lib.last_error(None))
     return P, Q
-
-
-def dashpot_rows(P, Q, V, G):
-    """The header's matrix rows in its association order: V, G [n,3] float64 -> v_new [n,3] float64."""
-    out = np.empty_like(V)
-    for k in range(3):
-        out[:, k] = ((P[:, k, 0] * V[:, 0] + P[:, k, 1] * V[:, 1]) + P[:, k, 2] * V[:, 2]) + \
-                    ((Q[:, k, 0] * G[:, 0] + Q[:, k, 1] * G[:, 1]) + Q[:, k, 2] * G[:, 2])
-    return out
-
-
-def host_scheme(apply, mass, fixed, bcv, force_at, alpha, beta, dt, u0, v0, first_step, steps, dash=None):
-    """The header's scheme, steps first_step .. first_step + steps - 1: float32 state, float64 math, rounded where
-    stored. apply(w) -> y (float32); force_at(n) -> f_n (float32); dash: (node ids, P, Q) or None. Nodes without a
-    dashpot take the scalar expression, dashpot nodes the matrix rows; then the mask. Returns (u, v)."""
-    u, v = u0.astype(np.float32), v0.astype(np.float32)
-    half = alpha * dt / 2.0
-    c1, c2 = (1.0 - half) / (1.0 + half), dt / (1.0 + half)
-    m = mass.astype(np.float64)
-    for n in range(first_step, first_step + steps):
-        w = (u.astype(np.float64) + beta * v.astype(np.float64)).astype(np.float32) if beta != 0.0 else u
-        y = apply(w)
-        f = force_at(n)
-        g = (f.astype(np.float64) - y.astype(np.float64)) / m
-        vn = (c1 * v.astype(np.float64) + c2 * g).astype(np.float32)
-        if dash is not None and len(dash[0]):
-            ids, P, Q = dash
-            rows = dashpot_rows(P, Q, v.astype(np.float64).reshape(-1, 3)[ids], g.reshape(-1, 3)[ids])
-            vn.reshape(-1, 3)[ids] = rows.astype(np.float32)
-        un = (u.astype(np.float64) + dt * vn.astype(np.float64)).astype(np.float32)
-        un[fixed] = bcv[fixed]
-        vn[fixed] = 0.0
-        u, v = un, vn
-    return u, v
 
 
 def scheme_f64(K, mass, fixed, dt, steps, force_at=None, dash=None, u0=None, v0=None, round_operator=False,

@@ -1,35 +1,11 @@
-"""Shared by the monitor tests: the loop of absorbing_common.host_scheme restated so that it yields what one update
-pass holds, and the monitors' per-DOF terms of include/cwf_hip.h ("Monitors") in numpy float64 in the stated
-association (numpy fuses nothing, so every term has the device's bits; only the order of the sums differs)."""
+"""Shared by the monitor tests: the monitors' per-DOF terms of include/cwf_hip.h ("Monitors") in numpy float64 in the
+stated association (numpy fuses nothing, so every term has the device's bits; only the order of the sums differs), fed
+with what explicit_common.scheme_steps yields of one update pass."""
 import numpy as np
 
 import absorbing_common as ac
 
 EPS = 2.0 ** -53
-
-
-def scheme_steps(apply, mass, fixed, bcv, force_at, alpha, beta, dt, u0, v0, first_step, steps, dash=None):
-    """absorbing_common.host_scheme, one step at a time: yields (n, u, v, y, f, un, vn) for the update that takes the
-    step count from n to n + 1 -- u_n, v_(n-1/2), y = K w, f_n, and the stored u_(n+1), v_(n+1/2); float32 each."""
-    u, v = u0.astype(np.float32), v0.astype(np.float32)
-    half = alpha * dt / 2.0
-    c1, c2 = (1.0 - half) / (1.0 + half), dt / (1.0 + half)
-    m = mass.astype(np.float64)
-    for n in range(first_step, first_step + steps):
-        w = (u.astype(np.float64) + beta * v.astype(np.float64)).astype(np.float32) if beta != 0.0 else u
-        y = apply(w)
-        f = force_at(n)
-        g = (f.astype(np.float64) - y.astype(np.float64)) / m
-        vn = (c1 * v.astype(np.float64) + c2 * g).astype(np.float32)
-        if dash is not None and len(dash[0]):
-            ids, P, Q = dash
-            rows = ac.dashpot_rows(P, Q, v.astype(np.float64).reshape(-1, 3)[ids], g.reshape(-1, 3)[ids])
-            vn.reshape(-1, 3)[ids] = rows.astype(np.float32)
-        un = (u.astype(np.float64) + dt * vn.astype(np.float64)).astype(np.float32)
-        un[fixed] = bcv[fixed]
-        vn[fixed] = 0.0
-        yield n, u, v, y, f, un, vn
-        u, v = un, vn
 
 
 def norm3(a):

@@ -1,12 +1,17 @@
 """Shared by the plasticity tests (include/cwf_hip.h "Plasticity"): the header's element update, corner forces and node
 fold restated in numpy float64 in their statement order (numpy fuses nothing, so every term has the device's bits),
-vectorised over elements, and the stepper's scheme with the correction force."""
+vectorised over elements. A Restatement enters the stepper's scheme (explicit_common.scheme_steps) as its correction
+force, p_at = lambda n, u: R.step(u)."""
 import numpy as np
 
 import element_monitors_common as ec
+import explicit_common as xc
 from cwf import pack
 
 FLT_MAX = 3.4028234663852886e38
+KINDS = {k: xc.KINDS[k] for k in ("parity", "lattice", "groups")}  # plasticity is tet4 only
+VARIANTS = {k: xc.VARIANTS[k] for k in ("undamped", "damped")}
+HARDENING = 3.0e9  # the J2 cases' hardening modulus: a tenth of the block's Young's modulus
 
 
 def von_mises(s):
@@ -91,6 +96,10 @@ class Restatement:
         """The element pass and the node fold at u = u_n (f32 [3N]) -> p f32 [3N]; the state advances."""
         _, self.ep, self.abar, self.wp, sp = j2_update(self.D, self.sy, self.H, self.V, self.strain(u), self.ep,
                                                        self.abar, self.wp)
+        return self.correction(sp)
+
+    def correction(self, sp):
+        """The corner forces of the slots' plastic stresses sp [n,6] (kept as self.corner) and their node fold -> p."""
         p = np.zeros((self.N, 3), np.float64)
         V = self.V
         c = np.empty((self.elem.size, 4, 3), np.float32)
@@ -113,35 +122,31 @@ class Restatement:
         return ep, abar, wp
 
 
-def host_scheme(apply, R, mass, fixed, bcv, force_at, alpha, beta, dt, u0, v0, first_step, steps, dash=None):
-    """tests/test_gpu_explicit.py's host_scheme with the plastic pass R (a Restatement, or None): float32 state,
-    float64 math, rounded where stored. -> (u, v, p of the last step)."""
-    u, v = u0.astype(np.float32), v0.astype(np.float32)
-    half = alpha * dt / 2.0
-    c1, c2 = (1.0 - half) / (1.0 + half), dt / (1.0 + half)
-    m = mass.astype(np.float64)
-    p = np.zeros(u.size, np.float32)
-    for n in range(first_step, first_step + steps):
-        if R is not None:
-            p = R.step(u)
-        w = (u.astype(np.float64) + beta * v.astype(np.float64)).astype(np.float32) if beta != 0.0 else u
-        y = apply(w)
-        f = force_at(n)
-        g = (f.astype(np.float64) - y.astype(np.float64))
-        if R is not None:
-            g = g + p.astype(np.float64)
-        g = g / m
-        vn = (c1 * v.astype(np.float64) + c2 * g).astype(np.float32)
-        if dash is not None:  # (node ids, P [n,3,3], Q [n,3,3]): the matrix form at the dashpot nodes
-            ids, Pm, Qm = dash
-            v3, g3 = v.astype(np.float64).reshape(-1, 3)[ids], g.reshape(-1, 3)[ids]
-            vd = np.empty((len(ids), 3))
-            for k in range(3):
-                vd[:, k] = ((Pm[:, k, 0] * v3[:, 0] + Pm[:, k, 1] * v3[:, 1]) + Pm[:, k, 2] * v3[:, 2]) + \
-                    ((Qm[:, k, 0] * g3[:, 0] + Qm[:, k, 1] * g3[:, 1]) + Qm[:, k, 2] * g3[:, 2])
-            vn.reshape(-1, 3)[ids] = vd.astype(np.float32)
-        un = (u.astype(np.float64) + dt * vn.astype(np.float64)).astype(np.float32)
-        un[fixed] = bcv[fixed]
-        vn[fixed] = 0.0
-        u, v = un, vn
-    return u, v, p
+def plastic_scheme(P, apply, R, force_at, alpha, beta, dt, u0, v0, first_step, steps, dash=None):
+    """explicit_common.host_scheme on the packing P with the plastic pass R (a Restatement, or None: the elastic
+    scheme) -> (u, v, p of the last step)."""
+    return xc.host_scheme(apply, np.repeat(P.lumped_mass, 3), xc.constrained(P), P.bc_value, force_at, alpha, beta, dt,
+                          u0, v0, first_step, steps, dash, p_at=None if R is None else (lambda n, u: R.step(u)),
+                          with_p=True)
+
+
+def bits64(a):
+    return np.ascontiguousarray(a, np.float64).reshape(-1).view(np.uint64)
+
+
+def assert_state(st, state, what):
+    """ep, abar, wp of the stepper against the restatement's `state` (Restatement.full()), bit for bit."""
+    ps = st.plasticity()
+    for name, a, b in (("ep", ps.plastic_strain, state[0]), ("abar", ps.equivalent_plastic_strain, state[1]),
+                       ("wp", ps.plastic_work, state[2])):
+        bad = np.flatnonzero(bits64(a) != bits64(b))
+        assert bad.size == 0, (what, name, bad[:5], np.asarray(a).reshape(-1)[bad[:5]], b.reshape(-1)[bad[:5]])
+
+
+def plastic_scenario(tmp_path, yield_stress):
+    """explicit_common.block_scenario (216 tets held at x = 0, a traction on the far face) with a yield stress on its
+    material and a frame in every VTU. The explicit driver holds the load of t = 0 (the traction's curve starts at 0),
+    so the block moves under its own weight: stresses of some kPa near the held face."""
+    return xc.block_scenario(tmp_path, name="plastic.yaml", replacements=(
+        ("vtu_stride: 10", "vtu_stride: 1"),
+        ("    rho: 2500.0\n", f"    rho: 2500.0\n    yield_stress: {yield_stress!r}\n    hardening_modulus: 3.0e9\n")))

@@ -1,11 +1,10 @@
 """Shared by the soil plasticity tests (include/cwf_hip.h "Soil plasticity"): the header's return map restated in
 numpy float64 in its statement order (numpy fuses nothing, so every term has the device's bits), vectorised over
-elements, and plasticity_common's Restatement with that map in place of the J2 one. Corner forces, the node fold and
-the host scheme are plasticity_common's, by import."""
+elements, and plasticity_common's Restatement with that map in place of the J2 one. Corner forces and the node fold
+are that Restatement's."""
 import numpy as np
 
 import plasticity_common as pc
-from plasticity_common import host_scheme, iso_row_fold, safe_cast  # noqa: F401  (re-exported)
 
 
 def dp_update(D, par, sig0, V, e, ep, abar, wp):
@@ -13,7 +12,7 @@ def dp_update(D, par, sig0, V, e, ep, abar, wp):
     [n], e, ep [n,6], abar, wp [n] -> (branch int [n]: 0 elastic, 1 cone, 2 apex; ep, abar, wp, sp), new arrays."""
     alpha, kappa, beta, H = par[:, 0], par[:, 1], par[:, 2], par[:, 3]
     ee = e - ep
-    st = iso_row_fold(D, ee)
+    st = pc.iso_row_fold(D, ee)
     if sig0 is not None:
         st = sig0 + st
     with np.errstate(all="ignore"):
@@ -58,7 +57,7 @@ def dp_update(D, par, sig0, V, e, ep, abar, wp):
     ep2 = np.where(cone[:, None], epc, np.where(apex[:, None], epa, ep))
     abar2 = np.where(cone, abarc, np.where(apex, abara, abar))
     wp2 = np.where(cone, wpc, np.where(apex, wpa, wp))
-    return branch, ep2, abar2, wp2, iso_row_fold(D, ep2)
+    return branch, ep2, abar2, wp2, pc.iso_row_fold(D, ep2)
 
 
 class SoilRestatement(pc.Restatement):
@@ -82,15 +81,4 @@ class SoilRestatement(pc.Restatement):
         self.branch, self.ep, self.abar, self.wp, sp = dp_update(self.D, self.par, self.sig0, self.V, self.strain(u),
                                                                  self.ep, self.abar, self.wp)
         self.seen |= self.branch
-        p = np.zeros((self.N, 3), np.float64)
-        V = self.V
-        c = np.empty((self.elem.size, 4, 3), np.float32)
-        for a in range(4):
-            gx, gy, gz = self.grad[:, a, 0], self.grad[:, a, 1], self.grad[:, a, 2]
-            c[:, a, 0] = safe_cast(V * ((gx * sp[:, 0] + gy * sp[:, 3]) + gz * sp[:, 5]))
-            c[:, a, 1] = safe_cast(V * ((gy * sp[:, 1] + gx * sp[:, 3]) + gz * sp[:, 4]))
-            c[:, a, 2] = safe_cast(V * ((gz * sp[:, 2] + gy * sp[:, 4]) + gx * sp[:, 5]))
-        self.corner = c
-        for q in range(self.elem.size):
-            p[self.conn[q]] = p[self.conn[q]] + c[q].astype(np.float64)
-        return safe_cast(p.reshape(-1))
+        return self.correction(sp)

@@ -8,6 +8,7 @@ from dataclasses import replace
 import numpy as np
 
 import absorbing_common as ac
+import explicit_common as xc
 from cwf import absorbing, explicit, meshgen, pack, scenarios
 from cwf.explicit import LoadSource
 from cwf.physics import Assignment, DirichletFix, compute_lame
@@ -44,14 +45,10 @@ def source_force(fext32, sources, n, dt, reverse=False):
 
 
 # ---- the sets of the bit-for-bit cases ------------------------------------------------------------------------------
-def _group(case, name):
-    return case.mesh.node_groups[case.mesh.group_names[name]].astype(np.int64)
-
-
 def mixed_sources(rng, case, dt):
     """Eight sources on 65 nodes of the 80-node block; see mixed_facts for what they cover between them."""
     N = case.packing.node_count
-    fixed = _group(case, "FIXED")
+    fixed = xc.group(case, "FIXED")
     over = int(fixed[3])
     free = np.setdiff1d(np.arange(N), fixed)
     hub = int(free[rng.integers(free.size)])
@@ -269,7 +266,7 @@ def slab_dense(nx, nz):
     P = case.packing
     D = P.dof_count
     K = dense_stiffness(P, case.mesh.coords, case.mesh.tets, case.materials[0].stiffness).reshape(D, D)
-    fixed = ac.constrained(P)
+    fixed = xc.constrained(P)
     mass = np.repeat(P.lumped_mass.astype(np.float64), 3)
     for a in (K, fixed, mass):
         a.setflags(write=False)

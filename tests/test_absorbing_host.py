@@ -11,12 +11,11 @@ import numpy as np
 import pytest
 
 from cwf import _lib, absorbing, config, meshgen, pack, scenarios
-from cwf.physics import AbsorbingBoundary, IncidentWave, compute_lame
+from cwf.physics import AbsorbingBoundary, IncidentWave
+from explicit_common import ABSORBING, BASE_YAML, H, face_geometry, raw_json, speeds
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = {"cwf_hip_explicit_set_dashpots", "cwf_hip_explicit_get_dashpots", "cwf_explicit_dashpot_update",
            "cwf_absorbing_dashpots"}
-H = 0.25
 
 
 def test_library_declares_and_exports_the_entry_points():
@@ -27,22 +26,6 @@ def test_library_declares_and_exports_the_entry_points():
         assert getattr(L, n).argtypes is not None, n
     assert L.cwf_hip_abi_version() == 1
     assert C.sizeof(_lib.ExplicitDescC) == 56
-
-
-def speeds(mat):
-    l = compute_lame(mat.youngs_modulus, mat.poisson_ratio)
-    return mat.density, math.sqrt((l.lambda_ + 2.0 * l.mu) / mat.density), math.sqrt(l.mu / mat.density)
-
-
-def face_geometry(X, face):
-    """(area, unit normal) of a triangle or of a quad as its triangles (0,1,2) + (0,2,3)."""
-    p = X[np.asarray(face, np.int64)]
-    c1 = np.cross(p[1] - p[0], p[2] - p[0])
-    area, s = 0.5 * np.linalg.norm(c1), c1
-    if len(face) == 4:
-        c2 = np.cross(p[2] - p[0], p[3] - p[0])
-        area, s = area + 0.5 * np.linalg.norm(c2), c1 + c2
-    return area, s / np.linalg.norm(s)
 
 
 def share_rule(X, faces, material_of_face):
@@ -229,24 +212,6 @@ def test_incident_pattern_rows_are_twice_c_times_d():
 
 
 # ---- config ---------------------------------------------------------------------------------------------------------
-BASE_YAML = open(os.path.join(ROOT, "tests", "golden", "data", "cantilever.yaml")).read()
-ABSORBING = """absorbing:
-  - group: BASE
-    incident: {direction: [1, 0, 0.5], velocity_curve: load_curve1}
-  - group: SIDES
-"""
-
-
-def raw_json(text):
-    L = _lib.load()
-    h = C.c_void_p()
-    assert L.cwf_config_load_string(text.encode(), C.byref(h)) == 0, _lib.last_error(None)
-    try:
-        return L.cwf_config_json(h).decode()
-    finally:
-        L.cwf_config_destroy(h)
-
-
 def test_config_block_parses_into_the_dataclasses():
     r = config.load_config_from_string(BASE_YAML + ABSORBING)
     assert r.has_value(), r.error()

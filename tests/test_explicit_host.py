@@ -2,13 +2,13 @@
 and the load curve's evaluation."""
 import ctypes as C
 import math
-import re
 
 import numpy as np
 import pytest
 
 from cwf import _lib, explicit, scenarios
 from cwf.physics import Curve, evaluate_curve
+from explicit_common import header_struct_size
 
 SYMBOLS = {
     "cwf_hip_explicit_create", "cwf_hip_explicit_destroy", "cwf_hip_explicit_advance", "cwf_hip_explicit_get_state",
@@ -30,28 +30,9 @@ def test_library_declares_and_exports_the_entry_points():
     assert L.cwf_hip_abi_version() == 1
 
 
-def _header_struct(name):
-    text = open(_lib.HEADER_PATH).read()
-    m = re.search(r"typedef struct " + name + r"\s*\{(.*?)\}\s*" + name + ";", text, re.S)
-    assert m, name
-    body = re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S)
-    size = {"double": 8, "uint64_t": 8, "uint32_t": 4, "int32_t": 4}
-    total = 0
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        names = decl.split(",")
-        if "*" in decl:
-            total += 8 * len(names)
-            continue
-        total += size[decl.split()[0]] * len(names)
-    return total  # every member here is naturally aligned in declaration order: no padding
-
-
 def test_struct_sizes_match_the_header():
-    assert C.sizeof(_lib.ExplicitDescC) == _header_struct("cwf_explicit_desc") == 4 * 8 + 2 * 4 + 2 * 8 == 56
-    assert C.sizeof(_lib.ExplicitTelemetryC) == _header_struct("cwf_explicit_telemetry") == 4 * 8 + 8 + 2 * 4 == 48
+    assert C.sizeof(_lib.ExplicitDescC) == header_struct_size("cwf_explicit_desc") == 4 * 8 + 2 * 4 + 2 * 8 == 56
+    assert C.sizeof(_lib.ExplicitTelemetryC) == header_struct_size("cwf_explicit_telemetry") == 4 * 8 + 8 + 2 * 4 == 48
     assert _lib.ExplicitDescC.external_force.offset == 40
     assert _lib.ExplicitTelemetryC.steps.offset == 32 and _lib.ExplicitTelemetryC.finite.offset == 40
 

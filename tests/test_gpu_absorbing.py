@@ -2,7 +2,7 @@
 cwf.absorbing).
 
 1. The stepper is the scheme, bit for bit: the numpy restatement of the header's arithmetic with the matrix rows of
-   the dashpot nodes (absorbing_common.host_scheme; P, Q from cwf_explicit_dashpot_update, y from cwf_hip_apply_keff
+   the dashpot nodes (explicit_common.host_scheme; P, Q from cwf_explicit_dashpot_update, y from cwf_hip_apply_keff
    on a second handle) against ExplicitStepper.advance, on a PARITY handle and the three FAST operator kinds, undamped,
    damped, and with a load curve, non-zero constraints and a seeded state.
 2. More than one workgroup: 392 nodes, dashpots on five faces and on every node.
@@ -31,153 +31,44 @@ import numpy as np
 import pytest
 
 import absorbing_common as ac
+import explicit_common as xc
 from cwf import _lib, absorbing, meshgen, pack, pcg, run, scenarios
 from cwf.explicit import ExplicitStepper
-from cwf.physics import RayleighCoefficients, compute_rayleigh, evaluate_curve
+from cwf.physics import RayleighCoefficients, compute_rayleigh
+from explicit_common import (CHECKPOINTS, KINDS, ROOT, U, V, VARIANTS, applier, big_case, constrained, deviation,
+                             group, mesh_case, new_system, random_spd)
 from helpers import assert_bitwise
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RUNNER = os.path.join(os.path.dirname(_lib.LIB_PATH), "cwf_run")
-U, V = ExplicitStepper.DISPLACEMENT, ExplicitStepper.VELOCITY
-KINDS = {
-    "parity": dict(mode=_lib.MODE_PARITY),
-    "lattice": dict(mode=_lib.MODE_FAST),
-    "groups": dict(mode=_lib.MODE_FAST, jitter=True),
-    "hex8": dict(mode=_lib.MODE_FAST, element="hex8"),
-}
-VARIANTS = {
-    "undamped": dict(alpha=0.0, beta=0.0),
-    "damped": dict(alpha=5.0, beta=2e-5),
-    "curve_bc_state": dict(alpha=0.0, beta=0.0, curve=True),
-}
-CHECKPOINTS = (1, 2, 3, 53)
-
-
-@functools.lru_cache(maxsize=None)
-def mesh_case(jitter=False, element="tet4", harmonic=None):
-    return scenarios.block_case(4, 3, 3, h=0.25, jitter=jitter, element=element, harmonic=harmonic)
-
-
-@functools.lru_cache(maxsize=None)
-def big_case():
-    return scenarios.block_case(7, 6, 6)
-
-
-def new_system(case, kind, scalars=(1.0, 0.0)):
-    return pcg.MatrixFreeSystem.from_packing(case.packing, case.materials, scalars[0], scalars[1],
-                                             mode=KINDS[kind]["mode"])
-
-
-def group(case, name):
-    return case.mesh.node_groups[case.mesh.group_names[name]].astype(np.int64)
-
-
-def random_spd(rng, mass32, dt):
-    """Full symmetric positive-definite matrices of the size m / dt, where B = C dt / (2 m) is of order one."""
-    G = rng.standard_normal((len(mass32), 3, 3))
-    Cn = G @ G.transpose(0, 2, 1) + 0.5 * np.eye(3)
-    Cn = 0.5 * (Cn + Cn.transpose(0, 2, 1))
-    return Cn * (mass32.astype(np.float64) / dt)[:, None, None]
-
-
-def applier(sys_b, D):
-    def apply(w):
-        y = np.zeros(D, np.float32)
-        r = pcg.apply_keff(sys_b, np.ascontiguousarray(w, np.float32), y)
-        assert r.has_value(), r.error()
-        return y
-
-    return apply
-
-
-def with_bc(P, bcv):
-    from dataclasses import replace
-
-    return replace(P, bc_value=bcv)
 
 
 def check_scheme(case, kind, variant, ids, checkpoints, what):
     """ExplicitStepper with random dashpots on `ids` against the restatement at every checkpoint, u and v bitwise."""
-    Vt = VARIANTS[variant]
-    curve = Vt.get("curve", False)
-    P = case.packing
-    D = P.dof_count
-    fixed = ac.constrained(P)
-    mass = np.repeat(P.lumped_mass, 3)
-    rng = np.random.Generator(np.random.PCG64(7))
-    bcv = P.bc_value.copy()
-    u0, v0 = np.zeros(D, np.float32), np.zeros(D, np.float32)
-    if curve:
-        bcv[fixed] = np.float32(1e-4)
-        u0 = (1e-6 * rng.standard_normal(D)).astype(np.float32)
-        v0 = (1e-3 * rng.standard_normal(D)).astype(np.float32)
-        u0[fixed] = bcv[fixed]
-        v0[fixed] = 0.0
-    sys_a = new_system(case, kind, case.scalars())  # a Newmark step's scalars: the stepper runs (1, 0) regardless
-    sys_b = new_system(case, kind, (1.0, 0.0))
-    st = ExplicitStepper(P if not curve else with_bc(P, bcv), case.materials,
-                         RayleighCoefficients(Vt["alpha"], Vt["beta"]), system=sys_a)
-    try:
-        dt = st.telemetry().dt
-        ids = rng.permutation(np.asarray(ids, np.int64))  # the caller's order is not ascending
-        Cn = random_spd(rng, P.lumped_mass[ids], dt)
+    with xc.SchemeRun(case, kind, variant) as S:
+        P = case.packing
+        ids = S.rng.permutation(np.asarray(ids, np.int64))  # the caller's order is not ascending
+        Cn = random_spd(S.rng, P.lumped_mass[ids], S.dt)
         assert np.abs(Cn[:, 0, 1]).min() > 0.0
-        Pm, Qm = ac.update_matrices(Cn, P.lumped_mass[ids], Vt["alpha"], dt)
-        st.set_dashpots(ids, Cn)
-        if curve:
-            base, pattern = case.load_pattern()
-            _, c = case.load_curve
-            st.set_load_pattern(base, pattern)
-            st.set_load_curve(c)
-            st.set_state(U, u0)
-            st.set_state(V, v0)
-
-            def force_at(n):
-                return pack._safe_f32(base + evaluate_curve(c, n * dt) * pattern)
-        else:
-            f = P.external_force.copy()
-
-            def force_at(n):
-                return f
-
-        apply = applier(sys_b, D)
-        u, v, done = u0, v0, 0
-        for upto in checkpoints:
-            r = st.advance(upto - done)
-            assert r.has_value(), r.error()
-            t = r.value()
-            assert t.steps == upto and t.time == upto * dt and t.finite
-            u, v = ac.host_scheme(apply, mass, fixed, bcv, force_at, Vt["alpha"], Vt["beta"], dt, u, v, done,
-                                  upto - done, (ids, Pm, Qm))
-            done = upto
-            assert_bitwise(st.get_state(U), u, f"{what} after {upto} steps: u")
-            assert_bitwise(st.get_state(V), v, f"{what} after {upto} steps: v")
-        assert np.abs(u[~fixed]).max() > 0.0 and np.abs(v[~fixed]).max() > 0.0
+        dash = (ids,) + ac.update_matrices(Cn, P.lumped_mass[ids], S.alpha, S.dt)
+        S.st.set_dashpots(ids, Cn)
+        S.load()
+        S.check(checkpoints, what, dash)
         # the dashpots did something: the scalar scheme alone gives other bits at the dashpot nodes
-        u_plain, v_plain = ac.host_scheme(apply, mass, fixed, bcv, force_at, Vt["alpha"], Vt["beta"], dt, u0, v0, 0, 1)
-        u_dash, v_dash = ac.host_scheme(apply, mass, fixed, bcv, force_at, Vt["alpha"], Vt["beta"], dt, u0, v0, 0, 1,
-                                        (ids, Pm, Qm))
-        free_dash = ~fixed.reshape(-1, 3)[ids]
+        u_plain, v_plain = S.host(S.u0, S.v0, 0, 1)
+        u_dash, v_dash = S.host(S.u0, S.v0, 0, 1, dash)
+        free_dash = ~S.fixed.reshape(-1, 3)[ids]
         if free_dash.any() and np.abs(v_plain).max() > 0.0:
             assert not np.array_equal(v_plain.reshape(-1, 3)[ids][free_dash], v_dash.reshape(-1, 3)[ids][free_dash])
-        # a constrained dashpot node: the mask wins
-        held = fixed.reshape(-1, 3)[ids]
-        assert np.array_equal(st.get_state(U).reshape(-1, 3)[ids][held], bcv.reshape(-1, 3)[ids][held])
-        assert np.all(st.get_state(V).reshape(-1, 3)[ids][held] == 0.0)
-    finally:
-        st.close()
-        sys_a.close()
-        sys_b.close()
+        S.check_mask_wins(ids)  # a constrained dashpot node
 
 
 # ---- 1. the stepper is the scheme -----------------------------------------------------------------------------------
 @pytest.mark.parametrize("variant", list(VARIANTS))
 @pytest.mark.parametrize("kind", list(KINDS))
 def test_stepper_with_dashpots_is_the_scheme_bit_for_bit(kind, variant):
-    k = KINDS[kind]
-    case = mesh_case(k.get("jitter", False), k.get("element", "tet4"), 5.0 if VARIANTS[variant].get("curve") else None)
+    case = xc.case_of(kind, 5.0 if VARIANTS[variant].get("curve") else None)
     ids = np.concatenate([group(case, "TIP"), group(case, "FIXED")[[0, 7, 13]]])
     check_scheme(case, kind, variant, ids, CHECKPOINTS, f"{kind}/{variant}")
 
@@ -205,7 +96,7 @@ def test_set_replace_clear_and_refusals(kind):
     case = mesh_case()
     P = case.packing
     D, N = P.dof_count, P.node_count
-    fixed = ac.constrained(P)
+    fixed = constrained(P)
     mass = np.repeat(P.lumped_mass, 3)
     bcv = P.bc_value
     f = P.external_force.copy()
@@ -218,7 +109,7 @@ def test_set_replace_clear_and_refusals(kind):
         apply = applier(sys_b, D)
 
         def host(u, v, first, steps, dash):
-            return ac.host_scheme(apply, mass, fixed, bcv, lambda n: f, 5.0, 0.0, dt, u, v, first, steps, dash)
+            return xc.host_scheme(apply, mass, fixed, bcv, lambda n: f, 5.0, 0.0, dt, u, v, first, steps, dash)
 
         def dash_of(ids):
             Cn = random_spd(rng, P.lumped_mass[ids], dt)
@@ -295,10 +186,6 @@ def gpu_energies(states, apply, mass, at):
 
 def top_dofs(wave):
     return 3 * group(ac.column_case(wave), "TOP") + ac.column_axis(wave)
-
-
-def deviation(a, ref):
-    return float(np.abs(np.asarray(a, np.float64) - ref).max() / np.abs(ref).max())
 
 
 @functools.lru_cache(maxsize=None)
@@ -453,7 +340,7 @@ def test_outgoing_pulse_leaves_through_the_base(wave):
                 try:
                     if not fixed_base:
                         st.set_dashpots(R["ids"], R["Cn"])
-                    free = ~ac.constrained(c.packing)
+                    free = ~constrained(c.packing)
                     st.set_state(U, np.where(free, R["u0"], 0.0).astype(np.float32))
                     st.set_state(V, np.where(free, R["v0"], 0.0).astype(np.float32))
                     first = gpu_states(st, 1)
@@ -494,7 +381,7 @@ def limit_dashpots():
     vp, vs = ac.wave_speed(mat, "P"), ac.wave_speed(mat, "S")
     Cn = 1e4 * mat.density * 0.1 * 0.1 * (vp * nn + vs * (np.eye(3) - nn))
     u0 = (1e-6 * rng.standard_normal(case.packing.dof_count)).astype(np.float32)
-    u0[ac.constrained(case.packing)] = 0.0
+    u0[constrained(case.packing)] = 0.0
     return ids, Cn, u0
 
 

@@ -27,34 +27,27 @@ import sys
 import numpy as np
 import pytest
 
-import absorbing_common as ac
 import element_monitors_common as ec
+import explicit_common as xc
 import materials_common as MC
 from cwf import _lib, pcg, post, run, scenarios
 from cwf.explicit import ExplicitStepper
 from cwf.physics import RayleighCoefficients, compute_rayleigh
+from explicit_common import ROOT, U, V, YAML, advance, block_scenario, run_cli
 from helpers import assert_bitwise
-from test_gpu_absorbing import with_bc
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-YAML = os.path.join(ROOT, "tests", "golden", "data", "cantilever.yaml")
-U, V = ExplicitStepper.DISPLACEMENT, ExplicitStepper.VELOCITY
 STEPS, EXTRA = 53, 5
-KINDS = {
-    "parity": dict(mode=_lib.MODE_PARITY, block=(6, 3, 4)),
-    "lattice": dict(mode=_lib.MODE_FAST, block=(6, 3, 4)),
-    "groups": dict(mode=_lib.MODE_FAST, block=(6, 3, 4), jitter=True),
-    "hex8": dict(mode=_lib.MODE_FAST, block=(8, 6, 6), element="hex8"),
-    "small": dict(mode=_lib.MODE_PARITY, block=(4, 3, 3)),
-    "mixed": dict(mode=_lib.MODE_PARITY, block=(6, 3, 4), materials=True),
+KINDS = {  # the shared operator kinds on this file's blocks, and two more PARITY cases
+    "parity": dict(xc.KINDS["parity"], block=(6, 3, 4)),
+    "lattice": dict(xc.KINDS["lattice"], block=(6, 3, 4)),
+    "groups": dict(xc.KINDS["groups"], block=(6, 3, 4)),
+    "hex8": dict(xc.KINDS["hex8"], block=(8, 6, 6)),
+    "small": dict(xc.KINDS["parity"], block=(4, 3, 3)),
+    "mixed": dict(xc.KINDS["parity"], block=(6, 3, 4), materials=True),
 }
-CONFIGS = {
-    "undamped": dict(alpha=0.0, beta=0.0),
-    "damped": dict(alpha=5.0, beta=2e-5),
-    "curve_bc_state": dict(alpha=0.0, beta=0.0, curve=True, state=True),
-}
+CONFIGS = dict(xc.VARIANTS, curve_bc_state=dict(xc.VARIANTS["curve_bc_state"], state=True))
 CASES = [(k, v) for k in ("parity", "lattice", "groups", "hex8") for v in CONFIGS] + \
     [("small", "undamped"), ("mixed", "undamped"), ("mixed", "curve_bc_state")]
 
@@ -70,14 +63,7 @@ def case_of(kind, curve):
 
 
 def new_system(case, kind):
-    return pcg.MatrixFreeSystem.from_packing(case.packing, case.materials, 1.0, 0.0, mode=KINDS[kind]["mode"])
-
-
-def advance(st, n):
-    r = st.advance(n)
-    assert r.has_value(), r.error()
-    assert r.value().finite
-    return r.value()
+    return xc.new_system(case, kind, kinds=KINDS)
 
 
 class Reference:
@@ -89,21 +75,13 @@ def reference(kind, config):
     cfg = CONFIGS[config]
     case = case_of(kind, bool(cfg.get("curve")))
     P = case.packing
-    D, E = P.dof_count, P.element_count
+    E = P.element_count
     S = Reference()
     S.case, S.kind, S.cfg, S.E = case, kind, cfg, E
     S.alpha, S.beta = cfg["alpha"], cfg["beta"]
     rng = np.random.Generator(np.random.PCG64(5))
-    fixed = ac.constrained(P)
-    S.bcv = P.bc_value.copy()
-    S.u0, S.v0 = np.zeros(D, np.float32), np.zeros(D, np.float32)
-    if cfg.get("state"):
-        S.bcv[fixed] = np.float32(1e-4)
-        S.u0 = (1e-6 * rng.standard_normal(D)).astype(np.float32)
-        S.v0 = (1e-3 * rng.standard_normal(D)).astype(np.float32)
-        S.u0[fixed] = S.bcv[fixed]
-        S.v0[fixed] = 0.0
-    S.packing = with_bc(P, S.bcv) if cfg.get("state") else P
+    S.bcv, S.u0, S.v0 = xc.seeded_state(P, xc.constrained(P), rng if cfg.get("state") else None)
+    S.packing = xc.with_bc(P, S.bcv) if cfg.get("state") else P
     if cfg.get("curve"):
         S.base, S.pattern = case.load_pattern()
         _, S.curve = case.load_curve
@@ -518,29 +496,6 @@ def test_kernel_names_and_launch_counts(tmp_path):
 
 
 # ---- 6. the scenario run --------------------------------------------------------------------------------------------
-def run_cli(args):
-    return subprocess.run([sys.executable, "-m", "cwf.run", *args], capture_output=True, text=True, cwd=ROOT,
-                          env=dict(os.environ, PYTHONPATH=os.path.join(ROOT, "civiwave-fem_amd")))
-
-
-def block_scenario(tmp_path):
-    """The cantilever scenario of the monitors test on a mesh that has an element 5: that scenario's own mesh is a
-    single tet (its run is test_run_reports_a_gauge_the_mesh_does_not_have). Its text with another mesh, 216 tets held
-    at x = 0 and loaded at the far face, and a shorter output interval."""
-    from cwf import meshgen
-
-    tm = meshgen.kuhn_block(4, 3, 3, 0.25)
-    x = tm.coords[:, 0]
-    tm.node_groups = {"FIXED_BASE": np.nonzero(x == x.min())[0].astype(np.uint32),
-                      "LOAD_FACE": np.nonzero(x == x.max())[0].astype(np.uint32)}
-    meshgen.write_gmsh(tm, str(tmp_path / "block.msh"), surface_groups=("FIXED_BASE", "LOAD_FACE"))
-    text = open(YAML).read()
-    assert "path: tests/data/cantilever.msh" in text and "dt: 0.01111" in text
-    y = tmp_path / "block.yaml"
-    y.write_text(text.replace("path: tests/data/cantilever.msh", "path: block.msh").replace("dt: 0.01111", "dt: 0.001"))
-    return str(y)
-
-
 def test_run_reports_a_gauge_the_mesh_does_not_have(capsys, tmp_path):
     assert run.main([YAML, "--integrator", "explicit", "--steps", "1", "--gauges", "0,5", "--out",
                      str(tmp_path / "refused")]) == 1

@@ -27,67 +27,16 @@ import sys
 import numpy as np
 import pytest
 
-from cwf import _lib, explicit, pack, pcg, run, scenarios, shard
+import absorbing_common as ac
+import explicit_common as xc
+from cwf import _lib, explicit, pcg, run, scenarios, shard
 from cwf.explicit import ExplicitStepper
-from cwf.physics import RayleighCoefficients, compute_rayleigh, evaluate_curve
+from cwf.physics import RayleighCoefficients, compute_rayleigh
 from cwf.stepper import Stepper
-from helpers import assert_bitwise, dense_stiffness
+from explicit_common import CHECKPOINTS, KINDS, ROOT, VARIANTS, YAML, constrained, deviation, mesh_case, new_system
+from helpers import assert_bitwise
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-YAML = os.path.join(ROOT, "tests", "golden", "data", "cantilever.yaml")
-DOF_BITS = np.array([1, 2, 4], np.uint32)
-KINDS = {
-    "parity": dict(mode=_lib.MODE_PARITY),
-    "lattice": dict(mode=_lib.MODE_FAST),
-    "groups": dict(mode=_lib.MODE_FAST, jitter=True),
-    "hex8": dict(mode=_lib.MODE_FAST, element="hex8"),
-}
-VARIANTS = {
-    "undamped": dict(alpha=0.0, beta=0.0),
-    "damped": dict(alpha=5.0, beta=2e-5),
-    "curve_bc_state": dict(alpha=0.0, beta=0.0, curve=True),
-}
-CHECKPOINTS = (1, 2, 3, 53)  # advance(1) three times, then 50 more in one call
-
-
-@functools.lru_cache(maxsize=None)
-def mesh_case(jitter=False, element="tet4", harmonic=None):
-    return scenarios.block_case(4, 3, 3, h=0.25, jitter=jitter, element=element, harmonic=harmonic)
-
-
-def case_of(kind, harmonic=None):
-    k = KINDS[kind]
-    return mesh_case(k.get("jitter", False), k.get("element", "tet4"), harmonic)
-
-
-def constrained(P):
-    return (np.repeat(P.bc_mask, 3) & np.tile(DOF_BITS, P.node_count)) != 0
-
-
-def new_system(case, kind, scalars=(1.0, 0.0)):
-    return pcg.MatrixFreeSystem.from_packing(case.packing, case.materials, scalars[0], scalars[1],
-                                             mode=KINDS[kind]["mode"])
-
-
-def host_scheme(apply, mass, fixed, bcv, force_at, alpha, beta, dt, u0, v0, first_step, steps):
-    """The header's scheme, step first_step .. first_step + steps - 1: float32 state, float64 math, rounded where
-    stored. apply(w) -> y (float32); force_at(n) -> f_n (float32). Returns (u, v) after the last step."""
-    u, v = u0.astype(np.float32), v0.astype(np.float32)
-    half = alpha * dt / 2.0
-    c1, c2 = (1.0 - half) / (1.0 + half), dt / (1.0 + half)
-    m = mass.astype(np.float64)
-    for n in range(first_step, first_step + steps):
-        w = (u.astype(np.float64) + beta * v.astype(np.float64)).astype(np.float32) if beta != 0.0 else u
-        y = apply(w)
-        f = force_at(n)
-        vn = (c1 * v.astype(np.float64) + c2 * ((f.astype(np.float64) - y.astype(np.float64)) / m)).astype(np.float32)
-        un = (u.astype(np.float64) + dt * vn.astype(np.float64)).astype(np.float32)
-        un[fixed] = bcv[fixed]
-        vn[fixed] = 0.0
-        u, v = un, vn
-    return u, v
 
 
 # ---- 1. the stepper is the scheme -----------------------------------------------------------------------------------
@@ -95,76 +44,14 @@ def host_scheme(apply, mass, fixed, bcv, force_at, alpha, beta, dt, u0, v0, firs
 @pytest.mark.parametrize("kind", list(KINDS))
 def test_stepper_is_the_scheme_bit_for_bit(kind, variant):
     V = VARIANTS[variant]
-    curve = V.get("curve", False)
-    case = case_of(kind, 5.0 if curve else None)
-    P = case.packing
-    D = P.dof_count
-    fixed = constrained(P)
-    mass = np.repeat(P.lumped_mass, 3)
-    rng = np.random.Generator(np.random.PCG64(7))
-    bcv = P.bc_value.copy()
-    u0, v0 = np.zeros(D, np.float32), np.zeros(D, np.float32)
-    if curve:
-        bcv[fixed] = np.float32(1e-4)
-        u0 = (1e-6 * rng.standard_normal(D)).astype(np.float32)
-        v0 = (1e-3 * rng.standard_normal(D)).astype(np.float32)
-        u0[fixed] = bcv[fixed]
-        v0[fixed] = 0.0
-    # the stepper's handle carries a Newmark step's scalars: the stepper must run the operator at (1, 0) regardless
-    sys_a = new_system(case, kind, case.scalars())
-    sys_b = new_system(case, kind, (1.0, 0.0))
-    packing = P if not curve else _with_bc(P, bcv)
-    st = ExplicitStepper(packing, case.materials, RayleighCoefficients(V["alpha"], V["beta"]), system=sys_a)
-    try:
-        tel = st.telemetry()
-        dt = tel.dt
+    with xc.SchemeRun(xc.case_of(kind, 5.0 if V.get("curve") else None), kind, variant) as S:
+        tel = S.st.telemetry()
         assert tel.steps == 0 and tel.time == 0.0 and tel.finite
-        assert dt == 0.9 * tel.critical_dt and tel.critical_dt == explicit.critical_dt(tel.lambda_max, V["beta"])
-        if curve:
-            base, pattern = case.load_pattern()
-            _, c = case.load_curve
-            st.set_load_pattern(base, pattern)
-            st.set_load_curve(c)
-            st.set_state(ExplicitStepper.DISPLACEMENT, u0)
-            st.set_state(ExplicitStepper.VELOCITY, v0)
-
-            def force_at(n):
-                return pack._safe_f32(base + evaluate_curve(c, n * dt) * pattern)
-        else:
-            f = P.external_force.copy()
-
-            def force_at(n):
-                return f
-
-        def apply(w):
-            y = np.zeros(D, np.float32)
-            r = pcg.apply_keff(sys_b, np.ascontiguousarray(w, np.float32), y)
-            assert r.has_value(), r.error()
-            return y
-
-        u, v, done = u0, v0, 0
-        for upto in CHECKPOINTS:
-            r = st.advance(upto - done)
-            assert r.has_value(), r.error()
-            t = r.value()
-            assert t.steps == upto and t.time == upto * dt and t.finite
-            u, v = host_scheme(apply, mass, fixed, bcv, force_at, V["alpha"], V["beta"], dt, u, v, done, upto - done)
-            done = upto
-            what = f"{kind}/{variant} after {upto} steps"
-            assert_bitwise(st.get_state(ExplicitStepper.DISPLACEMENT), u, what + ": u")
-            assert_bitwise(st.get_state(ExplicitStepper.VELOCITY), v, what + ": v")
-        assert np.abs(u[~fixed]).max() > 0.0 and np.abs(v[~fixed]).max() > 0.0
-        assert_bitwise(st.get_state(ExplicitStepper.EXTERNAL_FORCE), force_at(done - 1), "external force of the last step")
-    finally:
-        st.close()
-        sys_a.close()
-        sys_b.close()
-
-
-def _with_bc(P, bcv):
-    from dataclasses import replace
-
-    return replace(P, bc_value=bcv)
+        assert tel.dt == 0.9 * tel.critical_dt and tel.critical_dt == explicit.critical_dt(tel.lambda_max, V["beta"])
+        S.load()
+        S.check(CHECKPOINTS, f"{kind}/{variant}")
+        assert_bitwise(S.st.get_state(ExplicitStepper.EXTERNAL_FORCE), S.force_at(CHECKPOINTS[-1] - 1),
+                       "external force of the last step")
 
 
 # ---- 2. the scheme is the physics -----------------------------------------------------------------------------------
@@ -172,17 +59,7 @@ def _with_bc(P, bcv):
 def dense_reference():
     """K (dense, fp64 geometry), the f32 lumped mass and the constrained DOFs of the tet4 block; lambda_max of
     M^-1/2 K M^-1/2 over the free DOFs. Computed once, shared, never modified."""
-    case = mesh_case()
-    P = case.packing
-    D = P.dof_count
-    K = dense_stiffness(P, case.mesh.coords, case.mesh.tets, case.materials[0].stiffness).reshape(D, D)
-    fixed = constrained(P)
-    mass = np.repeat(P.lumped_mass.astype(np.float64), 3)
-    s = 1.0 / np.sqrt(mass[~fixed])
-    lam = np.linalg.eigvalsh(K[np.ix_(~fixed, ~fixed)] * s[:, None] * s[None, :])
-    for a in (K, fixed, mass):
-        a.setflags(write=False)
-    return dict(K=K, fixed=fixed, mass=mass, lam_max=float(lam[-1]))
+    return ac.dense_of(mesh_case())
 
 
 def numpy_run(dt, steps, round_operator, checkpoints=()):
@@ -205,10 +82,6 @@ def numpy_run(dt, steps, round_operator, checkpoints=()):
         if n + 1 in checkpoints or n + 1 == steps:
             out[n + 1] = (u.copy(), v.copy())
     return out
-
-
-def deviation(a, ref):
-    return float(np.abs(a.astype(np.float64) - ref).max() / np.abs(ref).max())
 
 
 def physics_floor(dt, steps=200):

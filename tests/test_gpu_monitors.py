@@ -1,5 +1,5 @@
 """The explicit stepper's monitors on the GPU (cwf_hip_explicit_set_monitors, include/cwf_hip.h "Monitors"): receiver
-traces, peak maps and the energy ledger against the numpy restatement of the scheme (monitors_common.scheme_steps,
+traces, peak maps and the energy ledger against the numpy restatement of the scheme (explicit_common.scheme_steps,
 y from cwf_hip_apply_keff on a second handle).
 
 1. Receivers are the state, bit for bit, at every recorded step count; a full buffer drops and counts.
@@ -12,37 +12,31 @@ y from cwf_hip_apply_keff on a second handle).
 """
 import functools
 import json
-import math
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import absorbing_common as ac
+import explicit_common as xc
 import monitors_common as mc
-from cwf import _lib, pack, pcg, run, scenarios
+from cwf import _lib, explicit, pcg, run, scenarios
 from cwf.explicit import ExplicitStepper
-from cwf.physics import RayleighCoefficients, compute_rayleigh, evaluate_curve
+from cwf.physics import RayleighCoefficients, compute_rayleigh
+from explicit_common import (CHECKPOINTS, KINDS, U, V, YAML, advance, applier, big_case, check_ledger, group,
+                             new_system, random_spd, run_cli)
 from helpers import assert_bitwise
-from test_gpu_absorbing import KINDS, applier, big_case, group, mesh_case, new_system, random_spd, with_bc
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-YAML = os.path.join(ROOT, "tests", "golden", "data", "cantilever.yaml")
-U, V = ExplicitStepper.DISPLACEMENT, ExplicitStepper.VELOCITY
-CONFIGS = {
-    "undamped": dict(alpha=0.0, beta=0.0),
-    "damped": dict(alpha=5.0, beta=2e-5),
-    "curve_bc_state": dict(alpha=0.0, beta=0.0, curve=True, state=True),
-    "ledger": dict(alpha=0.0, beta=0.0, curve=True),
-    "ledger_alpha": dict(alpha=5.0, beta=0.0, curve=True),
-}
+CONFIGS = dict(  # the shared variants (curve_bc_state also seeds the state here), and two the ledger accepts (beta = 0)
+    xc.VARIANTS,
+    curve_bc_state=dict(xc.VARIANTS["curve_bc_state"], state=True),
+    ledger=dict(alpha=0.0, beta=0.0, curve=True),
+    ledger_alpha=dict(alpha=5.0, beta=0.0, curve=True),
+)
 STATE_VARIANTS = ["undamped", "damped", "curve_bc_state"]
 LEDGER_VARIANTS = ["ledger", "ledger_alpha"]
-CHECKPOINTS = (1, 2, 3, 53)
 STEPS, EXTRA = 53, 5  # the restatement runs STEPS + EXTRA steps: the refill after reset_monitors
 
 
@@ -63,18 +57,11 @@ def build_setup(case, kind, config, dash_ids, receivers, steps):
     S = Setup()
     S.case, S.kind, S.cfg = case, kind, cfg
     S.alpha, S.beta = cfg["alpha"], cfg["beta"]
-    S.fixed = ac.constrained(P)
+    S.fixed = xc.constrained(P)
     S.mass = np.repeat(P.lumped_mass, 3)
     rng = np.random.Generator(np.random.PCG64(7))
-    S.bcv = P.bc_value.copy()
-    S.u0, S.v0 = np.zeros(D, np.float32), np.zeros(D, np.float32)
-    if cfg.get("state"):
-        S.bcv[S.fixed] = np.float32(1e-4)
-        S.u0 = (1e-6 * rng.standard_normal(D)).astype(np.float32)
-        S.v0 = (1e-3 * rng.standard_normal(D)).astype(np.float32)
-        S.u0[S.fixed] = S.bcv[S.fixed]
-        S.v0[S.fixed] = 0.0
-    S.packing = with_bc(P, S.bcv) if cfg.get("state") else P
+    S.bcv, S.u0, S.v0 = xc.seeded_state(P, S.fixed, rng if cfg.get("state") else None)
+    S.packing = xc.with_bc(P, S.bcv) if cfg.get("state") else P
     sys_a, sys_b = new_system(case, kind), new_system(case, kind)
     probe = ExplicitStepper(S.packing, case.materials, RayleighCoefficients(S.alpha, S.beta), system=sys_a)
     try:
@@ -86,24 +73,19 @@ def build_setup(case, kind, config, dash_ids, receivers, steps):
         if cfg.get("curve"):
             S.base, S.pattern = case.load_pattern()
             _, S.curve = case.load_curve
-
-            def force_at(n):
-                return pack._safe_f32(S.base + evaluate_curve(S.curve, n * S.dt) * S.pattern)
+            S.force_at = xc.curve_force(S.base, S.pattern, S.curve, S.dt)
         else:
             S.curve = None
-            f = P.external_force.copy()
-
-            def force_at(n):
-                return f
-
+            S.force_at = xc.constant_force(P)
         S.U, S.V, S.cand, S.terms = [S.u0], [S.v0], [], []
-        for n, u, v, y, f_n, un, vn in mc.scheme_steps(applier(sys_b, D), S.mass, S.fixed, S.bcv, force_at, S.alpha,
-                                                       S.beta, S.dt, S.u0, S.v0, 0, steps, (S.ids, Pm, Qm)):
-            S.U.append(un)
-            S.V.append(vn)
-            S.cand.append(mc.peak_candidates(v, un, vn, S.dt))
+        for s in xc.scheme_steps(applier(sys_b, D), S.mass, S.fixed, S.bcv, S.force_at, S.alpha, S.beta, S.dt, S.u0,
+                                 S.v0, 0, steps, (S.ids, Pm, Qm)):
+            S.U.append(s.un)
+            S.V.append(s.vn)
+            S.cand.append(mc.peak_candidates(s.v, s.un, s.vn, S.dt))
             if S.beta == 0.0:
-                S.terms.append(mc.energy_terms(S.mass, S.fixed, S.alpha, S.dt, v, y, f_n, un, vn, (S.ids, S.Cn)))
+                S.terms.append(mc.energy_terms(S.mass, S.fixed, S.alpha, S.dt, s.v, s.y, s.f, s.un, s.vn,
+                                               (S.ids, S.Cn)))
         assert np.abs(S.U[-1][~S.fixed]).max() > 0.0 and np.abs(S.V[-1][~S.fixed]).max() > 0.0
     finally:
         probe.close()
@@ -113,8 +95,7 @@ def build_setup(case, kind, config, dash_ids, receivers, steps):
 
 
 def small_case(kind, config):
-    k = KINDS[kind]
-    return mesh_case(k.get("jitter", False), k.get("element", "tet4"), 5.0 if CONFIGS[config].get("curve") else None)
+    return xc.case_of(kind, 5.0 if CONFIGS[config].get("curve") else None)
 
 
 @functools.lru_cache(maxsize=None)
@@ -138,13 +119,6 @@ def stepper_of(S, system, dashpots=True):
         st.set_state(U, S.u0)
         st.set_state(V, S.v0)
     return st
-
-
-def advance(st, n):
-    r = st.advance(n)
-    assert r.has_value(), r.error()
-    assert r.value().finite
-    return r.value()
 
 
 def check_rows(S, tr, want_steps, what):
@@ -175,17 +149,6 @@ def ledger_reference(S, first, last, every=1):
     for n in range(first, last):
         led.add(n + 1, S.terms[n], sample=(n + 1) % every == 0)
     return led.arrays()
-
-
-def check_ledger(led, ref, what):
-    steps, rows, bounds = ref
-    assert np.array_equal(led.steps, steps), (what, led.steps, steps)
-    got = np.stack([led.kinetic, led.potential, led.work, led.dissipated], axis=1)
-    err = np.abs(got - rows)
-    worst = float((err / np.maximum(bounds, 1e-300)).max()) if rows.size else 0.0
-    print(f"{what}: ledger error / summation bound, worst of {rows.shape[0]} rows x 4 columns: {worst:.3e}")
-    assert np.all(err <= bounds), (what, np.argwhere(err > bounds)[:5], err.max())
-    return got
 
 
 # ---- 1. receivers are the state -------------------------------------------------------------------------------------
@@ -374,7 +337,7 @@ def test_soil_column_ledger(wave):
     D = P.dof_count
     mass32 = np.repeat(P.lumped_mass, 3)
     mass = mass32.astype(np.float64)
-    fixed = ac.constrained(P)
+    fixed = xc.constrained(P)
     systems = {}
     for name, mode in (("PARITY", _lib.MODE_PARITY), ("FAST lattice", _lib.MODE_FAST)):
         systems[name] = [pcg.MatrixFreeSystem.from_packing(P, case.materials, 1.0, 0.0, mode=mode) for _ in range(2)]
@@ -389,18 +352,16 @@ def test_soil_column_ledger(wave):
         drift_f64 = mc.balance_drift(mc.ledger_of_f64_run(wave, dt))
         Pm, Qm = ac.update_matrices(R["Cn"], P.lumped_mass[R["ids"]], 0.0, dt)
 
-        def force_at(n):
-            return pack._safe_f32(np.zeros(D) + ac_curve(R, n, dt) * R["pattern"])
-
+        force_at = xc.curve_force(np.zeros(D), R["pattern"], R["pts"], dt, explicit.curve_value)  # the stepper's c(t_n)
         c = ac.wave_speed(ac.SOIL, wave)
         n0 = int(4.0 * 6.0 * ac.COLUMN_H / c / dt)  # the pulse's peak enters at t0 = 4 sigma / c
         for name, (sysm, sys_r) in systems.items():
             # the f32 restatement with this kind's operator, and its ledger
             led = mc.LedgerReference()
-            for n, u, v, y, f_n, un, vn in mc.scheme_steps(applier(sys_r, D), mass32, fixed, P.bc_value, force_at, 0.0,
-                                                           0.0, dt, np.zeros(D, np.float32), np.zeros(D, np.float32),
-                                                           0, steps, (R["ids"], Pm, Qm)):
-                led.add(n + 1, mc.energy_terms(mass32, fixed, 0.0, dt, v, y, f_n, un, vn, (R["ids"], R["Cn"])))
+            for s in xc.scheme_steps(applier(sys_r, D), mass32, fixed, P.bc_value, force_at, 0.0, 0.0, dt,
+                                     np.zeros(D, np.float32), np.zeros(D, np.float32), 0, steps, (R["ids"], Pm, Qm)):
+                led.add(s.n + 1, mc.energy_terms(mass32, fixed, 0.0, dt, s.v, s.y, s.f, s.un, s.vn,
+                                                 (R["ids"], R["Cn"])))
             ref_steps, ref_rows, ref_bounds = led.arrays()
             drift_f32 = mc.balance_drift(ref_rows)
             total_max = float((ref_rows[:, 0] + ref_rows[:, 1]).max())
@@ -436,13 +397,6 @@ def test_soil_column_ledger(wave):
         for pair in systems.values():
             for x in pair:
                 x.close()
-
-
-def ac_curve(R, n, dt):
-    """The stepper's c(t_n) of the sampled incident curve."""
-    from cwf import explicit
-
-    return explicit.curve_value(R["pts"], n * dt)
 
 
 # ---- 7. refusals and lifecycle --------------------------------------------------------------------------------------
@@ -482,7 +436,7 @@ def test_refusals_and_lifecycle(kind):
         assert list(tr.steps) == [12, 14, 16]
         assert_bitwise(tr.u[-1].reshape(-1), S.U[16].reshape(-1, 3)[r[:3]].reshape(-1), "the new set's rows")
         check_peaks(st.peaks(), running_peaks(S, 10, 16), f"{kind}: peaks from the set on")
-        check_ledger(st.energy(), ledger_reference_from(S, 10, 16), f"{kind}: ledger from the set on")
+        check_ledger(st.energy(), ledger_reference(S, 10, 16), f"{kind}: ledger from the set on")
         # set_dashpots while a ledger is active: the dissipation follows the new matrices
         rng = np.random.Generator(np.random.PCG64(33))
         C2 = random_spd(rng, S.case.packing.lumped_mass[S.ids], S.dt)
@@ -492,13 +446,12 @@ def test_refusals_and_lifecycle(kind):
         try:
             P2, Q2 = ac.update_matrices(C2, S.case.packing.lumped_mass[S.ids], S.alpha, S.dt)
             led, led_old = mc.LedgerReference(), mc.LedgerReference()
-            for n, u, v, y, f_n, un, vn in mc.scheme_steps(
-                    applier(sys_b, S.case.packing.dof_count), S.mass, S.fixed, S.bcv,
-                    lambda n: pack._safe_f32(S.base + evaluate_curve(S.curve, n * S.dt) * S.pattern), S.alpha, S.beta,
-                    S.dt, S.U[16], S.V[16], 16, 4, (S.ids, P2, Q2)):
-                led.add(n + 1, mc.energy_terms(S.mass, S.fixed, S.alpha, S.dt, v, y, f_n, un, vn, (S.ids, C2)))
-                led_old.add(n + 1, mc.energy_terms(S.mass, S.fixed, S.alpha, S.dt, v, y, f_n, un, vn, (S.ids, S.Cn)))
-            u20, v20 = un, vn
+            for s in xc.scheme_steps(applier(sys_b, S.case.packing.dof_count), S.mass, S.fixed, S.bcv, S.force_at,
+                                     S.alpha, S.beta, S.dt, S.U[16], S.V[16], 16, 4, (S.ids, P2, Q2)):
+                for ledger, Cn in ((led, C2), (led_old, S.Cn)):
+                    ledger.add(s.n + 1, mc.energy_terms(S.mass, S.fixed, S.alpha, S.dt, s.v, s.y, s.f, s.un, s.vn,
+                                                        (S.ids, Cn)))
+            u20 = s.un
         finally:
             sys_b.close()
         advance(st, 4)
@@ -524,10 +477,6 @@ def test_refusals_and_lifecycle(kind):
         st.close()
         plain.close()
         system.close()
-
-
-def ledger_reference_from(S, first, last):
-    return ledger_reference(S, first, last)
 
 
 @pytest.mark.parametrize("kind", ["parity", "lattice"])
@@ -556,11 +505,6 @@ def test_ledger_is_refused_with_stiffness_damping(kind):
 
 
 # ---- 8. the scenario run --------------------------------------------------------------------------------------------
-def run_cli(args):
-    return subprocess.run([sys.executable, "-m", "cwf.run", *args], capture_output=True, text=True, cwd=ROOT,
-                          env=dict(os.environ, PYTHONPATH=os.path.join(ROOT, "civiwave-fem_amd")))
-
-
 def test_run_writes_traces_peaks_and_energy(tmp_path):
     """A scenario's damping always has beta_R > 0 (xi in (0, 1)), for which the ledger is refused: the cantilever runs
     with the traces and the peaks, is refused with all three flags (the next test), and runs with all three under

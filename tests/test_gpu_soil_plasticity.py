@@ -1,7 +1,7 @@
 """Drucker-Prager plasticity of the explicit stepper on the GPU (cwf_hip_explicit_set_soil_plasticity,
 include/cwf_hip.h "Soil plasticity").
 
-1. The stepper is the scheme: tests/test_gpu_plasticity.py's host scheme with the soil pass of soil_plasticity_common
+1. The stepper is the scheme: explicit_common.host_scheme with the soil pass of soil_plasticity_common as its p_at
    (numpy float64 in the header's statement order), each y from cwf_hip_apply_keff on a second handle -- u, v, the
    correction force p, ep, abar and wp bit for bit after 1, 2, 3 and 53 steps, on a PARITY handle, a FAST lattice and
    FAST fan groups (jittered, renumbered nodes), undamped and with Rayleigh damping, with and without a stress at
@@ -24,22 +24,22 @@ import numpy as np
 import pytest
 
 import absorbing_common as ac
+import explicit_common as xc
 import materials_common as MC
 import plasticity_common as pc
 import soil_plasticity_common as spc
 import sources_common as sc
-import test_gpu_plasticity as j2  # its mesh, handles and stepping helpers
 from cwf import _lib, pcg, scenarios, soil
 from cwf.explicit import ExplicitStepper
 from cwf.physics import RayleighCoefficients
+from explicit_common import (CHECKPOINTS, PF, ROOT, U, V, advance, applier, case_of, mesh_case, new_system, refused,
+                             run_cli)
 from helpers import assert_bitwise
+from plasticity_common import KINDS, VARIANTS
 
 pytestmark = pytest.mark.gpu
 
-U, V, PF = ExplicitStepper.DISPLACEMENT, ExplicitStepper.VELOCITY, ExplicitStepper.PLASTIC_FORCE
-KINDS, VARIANTS, CHECKPOINTS = j2.KINDS, j2.VARIANTS, j2.CHECKPOINTS
 ALPHA, BETA, HARDENING = 0.3, 0.1, 1.0e9
-advance, applier, new_system, case_of, refused = j2.advance, j2.applier, j2.new_system, j2.case_of, j2.refused
 
 
 def rest_stress(P, scale):
@@ -59,7 +59,6 @@ def elastic_peaks(case, apply, V_, dt, sig0):
     rest, of J alone), float64."""
     P = case.packing
     D = P.dof_count
-    fixed, mass = ac.constrained(P), np.repeat(P.lumped_mass, 3)
     R = pc.Restatement(P, case.materials, 1.0, 0.0)  # every element a slot: its strain and D
     peak, peak_j = np.full(P.element_count, -np.inf), np.zeros(P.element_count)
     u, v = np.zeros(D, np.float32), np.zeros(D, np.float32)
@@ -70,8 +69,7 @@ def elastic_peaks(case, apply, V_, dt, sig0):
         pm = st[:, :3].sum(1) / 3.0
         J = pc.von_mises(st) / math.sqrt(3.0)
         peak, peak_j = np.maximum(peak, J + 3.0 * ALPHA * pm), np.maximum(peak_j, J)
-        u, v, _ = pc.host_scheme(apply, None, mass, fixed, P.bc_value, lambda n: P.external_force, V_["alpha"],
-                                 V_["beta"], dt, u, v, n, 1)
+        u, v, _ = pc.plastic_scheme(P, apply, None, lambda n: P.external_force, V_["alpha"], V_["beta"], dt, u, v, n, 1)
     return peak, peak_j
 
 
@@ -79,12 +77,11 @@ def restated_run(case, apply, V_, dt, kappa, sig0, upto=CHECKPOINTS):
     """-> ([(steps, u, v, p, (ep, abar, wp))] of the restatement at the checkpoints, the outcomes met per element)."""
     P = case.packing
     D = P.dof_count
-    fixed, mass = ac.constrained(P), np.repeat(P.lumped_mass, 3)
     R = spc.SoilRestatement(P, case.materials, ALPHA, kappa, BETA, HARDENING, sig0)
     u, v, done, out = np.zeros(D, np.float32), np.zeros(D, np.float32), 0, []
     for n in upto:
-        u, v, p = pc.host_scheme(apply, R, mass, fixed, P.bc_value, lambda n: P.external_force, V_["alpha"],
-                                 V_["beta"], dt, u, v, done, n - done)
+        u, v, p = pc.plastic_scheme(P, apply, R, lambda n: P.external_force, V_["alpha"], V_["beta"], dt, u, v, done,
+                                    n - done)
         done = n
         out.append((n, u, v, p, R.full()))
     return out, R.seen
@@ -113,11 +110,7 @@ def assert_against(st, u, v, p, state, what):
     assert_bitwise(st.get_state(U), u, what + ": u")
     assert_bitwise(st.get_state(V), v, what + ": v")
     assert_bitwise(st.get_state(PF), p, what + ": p")
-    ps = st.plasticity()
-    for name, a, b in (("ep", ps.plastic_strain, state[0]), ("abar", ps.equivalent_plastic_strain, state[1]),
-                       ("wp", ps.plastic_work, state[2])):
-        bad = np.flatnonzero(j2.bits64(a) != j2.bits64(b))
-        assert bad.size == 0, (what, name, bad[:5], np.asarray(a).reshape(-1)[bad[:5]], b.reshape(-1)[bad[:5]])
+    pc.assert_state(st, state, what)
 
 
 # ---- 1. the stepper is the scheme -----------------------------------------------------------------------------------
@@ -249,7 +242,7 @@ def test_lifecycle_and_neighbours(kind):
     case = case_of(kind)
     P = case.packing
     D, N, E = P.dof_count, P.node_count, P.element_count
-    fixed, mass = ac.constrained(P), np.repeat(P.lumped_mass, 3)
+    fixed = xc.constrained(P)
     alpha_r = 5.0
     ray = RayleighCoefficients(alpha_r, 0.0)
     sys_a, sys_b, sys_c = (new_system(case, kind) for _ in range(3))
@@ -264,7 +257,7 @@ def test_lifecycle_and_neighbours(kind):
         kappa, sig0 = 0.5e6, rest_stress(P, 2.0e6)
         # either setter replaces the other's set, the state starting at zero
         assert st.plasticity_model() == 0
-        st.set_plasticity(1.0e6, j2.HARDENING)
+        st.set_plasticity(1.0e6, pc.HARDENING)
         assert st.plasticity_model() == 1
         st.set_state(U, u0)
         advance(st, 2)
@@ -273,7 +266,7 @@ def test_lifecycle_and_neighbours(kind):
         assert st.plasticity_model() == 2
         info = st.plasticity_info()
         assert (info.plastic_elements, info.yielded_elements) == (E, 0) and not st.get_state(PF).any()
-        st.set_plasticity(1.0e6, j2.HARDENING)
+        st.set_plasticity(1.0e6, pc.HARDENING)
         assert st.plasticity_model() == 1 and st.plasticity_info().yielded_elements == 0
         # dashpots on the tip face, a one-node source and peak maps alongside the soil set
         tip = case.mesh.node_groups[case.mesh.group_names["TIP"]].astype(np.uint32)
@@ -291,8 +284,8 @@ def test_lifecycle_and_neighbours(kind):
         advance(st, 10)
         R = spc.SoilRestatement(P, case.materials, ALPHA, kappa, BETA, HARDENING, sig0)
         force_at = lambda n: sc.source_force(P.external_force, sources, n, dt)
-        u, v, p = pc.host_scheme(apply, R, mass, fixed, P.bc_value, force_at, alpha_r, 0.0, dt, u0,
-                                 np.zeros(D, np.float32), first, 10, dash=(tip.astype(np.int64), Pm, Qm))
+        u, v, p = pc.plastic_scheme(P, apply, R, force_at, alpha_r, 0.0, dt, u0, np.zeros(D, np.float32), first, 10,
+                                    dash=(tip.astype(np.int64), Pm, Qm))
         assert np.count_nonzero(R.abar > 0.0) > 0
         assert_against(st, u, v, p, R.full(), "combined")
         assert st.peaks()[0].max() > 0.0
@@ -341,7 +334,6 @@ def test_two_layers_only_the_upper_one_plastic_keeps_the_layered_kernel():
     try:
         dt = st.telemetry().dt
         apply = applier(other, P.dof_count)
-        fixed, mass = ac.constrained(P), np.repeat(P.lumped_mass, 3)
         inf = float("inf")
         # a cohesion the soft upper soil's elastic response passes within 20 steps under the block's own loads
         probe = pc.Restatement(P, case.materials, [0.0, 1.0], 0.0)
@@ -349,8 +341,7 @@ def test_two_layers_only_the_upper_one_plastic_keeps_the_layered_kernel():
         peak = np.zeros(probe.elem.size)
         for n in range(20):
             peak = np.maximum(peak, pc.von_mises(pc.iso_row_fold(probe.D, probe.strain(u))) / math.sqrt(3.0))
-            u, v, _ = pc.host_scheme(apply, None, mass, fixed, P.bc_value, lambda n: P.external_force, 0.0, 0.0, dt,
-                                     u, v, n, 1)
+            u, v, _ = pc.plastic_scheme(P, apply, None, lambda n: P.external_force, 0.0, 0.0, dt, u, v, n, 1)
         kappa = 0.5 * float(np.quantile(peak, 0.5))
         assert kappa > 0.0
         st.set_soil_plasticity([0.0, ALPHA], [inf, kappa], [0.0, BETA], [0.0, HARDENING])
@@ -359,8 +350,8 @@ def test_two_layers_only_the_upper_one_plastic_keeps_the_layered_kernel():
         R = spc.SoilRestatement(P, case.materials, [0.0, ALPHA], [inf, kappa], [0.0, BETA], [0.0, HARDENING])
         assert np.array_equal(R.elem, np.flatnonzero(upper)) and np.array_equal(R.affected, affected)
         advance(st, 20)
-        u, v, p = pc.host_scheme(apply, R, mass, fixed, P.bc_value, lambda n: P.external_force, 0.0, 0.0, dt,
-                                 np.zeros(P.dof_count, np.float32), np.zeros(P.dof_count, np.float32), 0, 20)
+        u, v, p = pc.plastic_scheme(P, apply, R, lambda n: P.external_force, 0.0, 0.0, dt,
+                                    np.zeros(P.dof_count, np.float32), np.zeros(P.dof_count, np.float32), 0, 20)
         assert R.abar.max() > 0.0
         assert_against(st, u, v, p, R.full(), "layered")
         ps = st.plasticity()
@@ -374,7 +365,7 @@ def test_two_layers_only_the_upper_one_plastic_keeps_the_layered_kernel():
 
 def test_refusals_leave_the_previous_set_in_force():
     # a hex8 handle
-    hexc = j2.mesh_case(element="hex8")
+    hexc = mesh_case(element="hex8")
     hsys = pcg.MatrixFreeSystem.from_packing(hexc.packing, hexc.materials, 1.0, 0.0, mode=_lib.MODE_FAST)
     hst = ExplicitStepper(hexc.packing, hexc.materials, RayleighCoefficients(0.0, 0.0), system=hsys)
     try:
@@ -383,7 +374,7 @@ def test_refusals_leave_the_previous_set_in_force():
         hst.close()
         hsys.close()
     # two materials, the second one anisotropic
-    base = j2.mesh_case()
+    base = mesh_case()
     mixed = MC.MaterialCase(base, [MC.ISO, MC.ROT], MC.scattered(base, 2), name="mixed")
     P = mixed.packing
     E = P.element_count
@@ -449,9 +440,9 @@ def test_refusals_leave_the_previous_set_in_force():
 
 # ---- 5. the driver --------------------------------------------------------------------------------------------------
 def soil_scenario(tmp_path):
-    """tests/test_gpu_plasticity.py's block scenario with a cohesion and a friction angle in place of its yield stress,
+    """plasticity_common.plastic_scenario with a cohesion and a friction angle in place of its yield stress,
     and a geostatic stress along z with Jaky's K0."""
-    path = j2.plastic_scenario(tmp_path, 100.0)
+    path = pc.plastic_scenario(tmp_path, 100.0)
     text = open(path).read()
     assert text.count("    yield_stress: 100.0\n") == 1
     text = text.replace("    yield_stress: 100.0\n", "    cohesion: 50.0\n    friction_angle: 30.0\n    dilation_angle: 5.0\n")
@@ -468,7 +459,7 @@ def test_run_applies_a_scenarios_soil_model(tmp_path):
 
     scenario = soil_scenario(tmp_path)
     out = tmp_path / "out"
-    p = j2.run_cli([scenario, "--integrator", "explicit", "--steps", "2", "--out", str(out), "--plastic-summary"])
+    p = run_cli([scenario, "--integrator", "explicit", "--steps", "2", "--out", str(out), "--plastic-summary"])
     assert p.returncode == 0, p.stderr
     lines = [json.loads(l) for l in p.stdout.strip().splitlines()]
     summary = lines[-1]["summary"]
@@ -483,13 +474,13 @@ def test_run_applies_a_scenarios_soil_model(tmp_path):
     cells = head[head.index("<CellData"):head.index("</CellData>")]
     names = re.findall(r'Name="([a-z_]+)" NumberOfComponents="(\d)"', cells)
     assert names[-2:] == [("plastic_strain", "6"), ("equivalent_plastic_strain", "1")]
-    q = j2.run_cli([scenario, "--integrator", "newmark", "--steps", "1"])
+    q = run_cli([scenario, "--integrator", "newmark", "--steps", "1"])
     assert q.returncode == 1 and "plastic materials need the explicit integrator" in q.stderr
     # the C++ runner steps by Newmark: the same refusal
     import subprocess
 
-    exe = os.path.join(j2.ROOT, "civiwave-fem_amd", "lib", "cwf_run")
-    r = subprocess.run([exe, scenario, "--steps", "1"], capture_output=True, text=True, cwd=j2.ROOT)
+    exe = os.path.join(ROOT, "civiwave-fem_amd", "lib", "cwf_run")
+    r = subprocess.run([exe, scenario, "--steps", "1"], capture_output=True, text=True, cwd=ROOT)
     assert r.returncode != 0 and "plastic materials need the explicit integrator" in r.stdout + r.stderr
 
 
@@ -547,7 +538,7 @@ def test_the_cooperative_node_pass_gives_the_plain_ones_p(shape):
         P = case.packing
         alpha, kappa, beta, H = [0.0, ALPHA], [float("inf"), 0.5e6], [0.0, BETA], [0.0, HARDENING]
     rng = np.random.Generator(np.random.PCG64(17))
-    fixed = ac.constrained(P)
+    fixed = xc.constrained(P)
     u0 = (1e-4 * rng.standard_normal(P.dof_count)).astype(np.float32)
     u0[fixed] = P.bc_value[fixed]
     sig0 = rest_stress(P, 2.0e6)
@@ -571,8 +562,8 @@ def test_the_cooperative_node_pass_gives_the_plain_ones_p(shape):
     for other in (2, 3):
         for k, name in ((0, "p"), (1, "u"), (2, "v")):
             assert_bitwise(got[1][k], got[other][k], f"{shape}: {name} of node pass {other}")
-        assert np.array_equal(j2.bits64(got[1][3]), j2.bits64(got[other][3])), other
-        assert np.array_equal(j2.bits64(got[1][4]), j2.bits64(got[other][4])), other
+        assert np.array_equal(pc.bits64(got[1][3]), pc.bits64(got[other][3])), other
+        assert np.array_equal(pc.bits64(got[1][4]), pc.bits64(got[other][4])), other
         assert got[1][5] == got[other][5]
     if shape != "n4":  # more corner words than a short round holds: node pass 3 took several rounds
         plastic = np.ones(P.element_count, bool) if shape == "all" else np.asarray(P.material_index) == 1

@@ -1,7 +1,7 @@
 """The explicit stepper's load sources on the GPU (cwf_hip_explicit_set_sources, include/cwf_hip.h "Load sources").
 
 1. The stepper is the scheme with f_n from the header's semantics block, bit for bit: u, v and get_state(4) after 1,
-   2, 3 and 53 steps against the numpy restatement (sources_common.source_force on top of monitors_common.scheme_steps,
+   2, 3 and 53 steps against the numpy restatement (sources_common.source_force on top of explicit_common.scheme_steps,
    y from cwf_hip_apply_keff on a second handle), on the PARITY handle and the three FAST operator kinds, on the
    4 x 3 x 3-cell (80 nodes) and 7 x 7 x 7-cell (512 nodes) blocks, with dashpots throughout.
 2. Sources replaced between two advance calls, set_external_force after set_sources, and removed.
@@ -22,21 +22,20 @@ import numpy as np
 import pytest
 
 import absorbing_common as ac
+import explicit_common as xc
 import monitors_common as mc
 import sources_common as sc
-from cwf import _lib, absorbing, meshgen, pack, pcg, run, scenarios
+from cwf import _lib, absorbing, meshgen, pcg, run, scenarios
 from cwf.explicit import ExplicitStepper, LoadSource
 from cwf.physics import RayleighCoefficients, compute_rayleigh
+from explicit_common import (CHECKPOINTS, KINDS, ROOT, F, U, V, advance, applier, check_ledger, deviation, group,
+                             mesh_case, new_system, random_spd)
 from helpers import assert_bitwise
-from test_gpu_absorbing import KINDS, applier, deviation, group, mesh_case, new_system, random_spd
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-U, V, F = ExplicitStepper.DISPLACEMENT, ExplicitStepper.VELOCITY, ExplicitStepper.EXTERNAL_FORCE
-CHECKPOINTS = (1, 2, 3, 53)
 STEPS = 53
-DAMPING = {"undamped": (0.0, 0.0), "damped": (5.0, 2e-5)}
+DAMPING = {k: (xc.VARIANTS[k]["alpha"], xc.VARIANTS[k]["beta"]) for k in ("undamped", "damped")}
 FLT_MAX = np.float32(3.4028234663852886e38)
 
 
@@ -62,7 +61,7 @@ def build_setup(case, kind, damping, make_sources, steps=STEPS, seed=11):
     D = P.dof_count
     S.case, S.kind = case, kind
     S.alpha, S.beta = DAMPING[damping]
-    S.fixed = ac.constrained(P)
+    S.fixed = xc.constrained(P)
     S.mass = np.repeat(P.lumped_mass, 3)
     S.fext = P.external_force.copy()
     rng = np.random.Generator(np.random.PCG64(seed))
@@ -76,16 +75,17 @@ def build_setup(case, kind, damping, make_sources, steps=STEPS, seed=11):
         S.sources = make_sources(rng, case, S.dt)
         S.apply = None
         S.U, S.V, S.F, S.cand, S.terms = [np.zeros(D, np.float32)], [np.zeros(D, np.float32)], [S.fext], [], []
-        for n, u, v, y, f_n, un, vn in mc.scheme_steps(
+        for s in xc.scheme_steps(
                 applier(sys_b, D), S.mass, S.fixed, P.bc_value,
                 lambda n: sc.source_force(S.fext, S.sources, n, S.dt), S.alpha, S.beta, S.dt, S.U[0], S.V[0], 0, steps,
                 (S.ids, *S.PQ)):
-            S.U.append(un)
-            S.V.append(vn)
-            S.F.append(f_n)
-            S.cand.append(mc.peak_candidates(v, un, vn, S.dt))
+            S.U.append(s.un)
+            S.V.append(s.vn)
+            S.F.append(s.f)
+            S.cand.append(mc.peak_candidates(s.v, s.un, s.vn, S.dt))
             if S.beta == 0.0:
-                S.terms.append(mc.energy_terms(S.mass, S.fixed, S.alpha, S.dt, v, y, f_n, un, vn, (S.ids, S.Cn)))
+                S.terms.append(mc.energy_terms(S.mass, S.fixed, S.alpha, S.dt, s.v, s.y, s.f, s.un, s.vn,
+                                               (S.ids, S.Cn)))
     finally:
         probe.close()
         sys_a.close()
@@ -101,13 +101,6 @@ def stepper_of(S, system, sources=True):
     if sources:
         st.set_sources(S.sources)
     return st
-
-
-def advance(st, n):
-    r = st.advance(n)
-    assert r.has_value(), r.error()
-    assert r.value().finite
-    return r.value()
 
 
 def check_state(st, S, n, what):
@@ -223,10 +216,10 @@ def test_replace_external_force_and_remove(kind):
                 never.set_state(U, u)
                 never.set_state(V, v)
                 never.set_external_force(f2)
-            rec = list(mc.scheme_steps(applier(sys_b, D), A.mass, A.fixed, P.bc_value,
+            rec = list(xc.scheme_steps(applier(sys_b, D), A.mass, A.fixed, P.bc_value,
                                        lambda n: sc.source_force(fext, sources, n, A.dt), A.alpha, A.beta, A.dt, u, v,
                                        done, steps, (A.ids, *A.PQ)))
-            u, v, f_last = rec[-1][5], rec[-1][6], rec[-1][4]
+            u, v, f_last = rec[-1].un, rec[-1].vn, rec[-1].f
             done += steps
             assert advance(st, steps).steps == done
             assert_bitwise(st.get_state(U), u, f"{kind} phase {i}: u")
@@ -254,8 +247,6 @@ def test_replace_external_force_and_remove(kind):
 # ---- 3. monitors ----------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("kind", list(KINDS))
 def test_monitors_see_the_source_forces(kind):
-    from test_gpu_monitors import check_ledger
-
     S = mixed_setup(kind, "undamped")
     N = S.case.packing.node_count
     rng = np.random.Generator(np.random.PCG64(5))

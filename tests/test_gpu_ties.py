@@ -1,6 +1,6 @@
 """Tied (laminar and periodic) lateral boundaries of the explicit stepper on the GPU (cwf_hip_explicit_set_ties).
 
-1. The stepper is the scheme, bit for bit: ties_common.host_scheme (the header's arithmetic and summation order, P_G | Q_G
+1. The stepper is the scheme, bit for bit: explicit_common.host_scheme (the header's arithmetic and summation order, P_G | Q_G
    from cwf_explicit_dashpot_update, y from cwf_hip_apply_keff on a second handle) against ExplicitStepper.advance on a
    PARITY handle and the three FAST operator kinds, undamped, damped, and with a load curve, non-zero constraints and a
    seeded state; the lateral perimeter tied by level, dashpots on the base (the z = 0 level has dashpot members, the
@@ -15,61 +15,27 @@
 9. python -m cwf.run --integrator explicit with a ``tied:`` scenario (both entry forms) and ``absorbing:``; the Newmark
    drivers refuse it.
 """
-import dataclasses
 import math
 
 import numpy as np
 import pytest
 
 import absorbing_common as ac
+import explicit_common as xc
+import monitors_common as mc
 import sources_common as sc
 import ties_common as tc
-from cwf import _lib, pack, pcg, ties
+from cwf import _lib, explicit, pack, pcg, ties
 from cwf.explicit import ExplicitStepper, LoadSource
-from cwf.physics import RayleighCoefficients, evaluate_curve
+from cwf.physics import RayleighCoefficients
+from explicit_common import CHECKPOINTS, KINDS, PF, U, V, VARIANTS, applier, deviation, group, new_system, random_spd
 from helpers import assert_bitwise
 
 pytestmark = pytest.mark.gpu
 
-U, V, PF = ExplicitStepper.DISPLACEMENT, ExplicitStepper.VELOCITY, ExplicitStepper.PLASTIC_FORCE
-KINDS = {
-    "parity": dict(mode=_lib.MODE_PARITY),
-    "lattice": dict(mode=_lib.MODE_FAST),
-    "groups": dict(mode=_lib.MODE_FAST, jitter=True),
-    "hex8": dict(mode=_lib.MODE_FAST, element="hex8"),
-}
-VARIANTS = {
-    "undamped": dict(alpha=0.0, beta=0.0),
-    "damped": dict(alpha=5.0, beta=2e-5),
-    "curve_bc_state": dict(alpha=0.0, beta=0.0, curve=True),
-}
-CHECKPOINTS = (1, 2, 3, 53)
-
-
-def new_system(case, kind, scalars=(1.0, 0.0)):
-    return pcg.MatrixFreeSystem.from_packing(case.packing, case.materials, scalars[0], scalars[1],
-                                             mode=KINDS[kind]["mode"])
-
-
-def applier(sys_b, D):
-    def apply(w):
-        y = np.zeros(D, np.float32)
-        r = pcg.apply_keff(sys_b, np.ascontiguousarray(w, np.float32), y)
-        assert r.has_value(), r.error()
-        return y
-
-    return apply
-
-
-def random_spd(rng, mass32, dt):
-    G = rng.standard_normal((len(mass32), 3, 3))
-    Cn = G @ G.transpose(0, 2, 1) + 0.5 * np.eye(3)
-    Cn = 0.5 * (Cn + Cn.transpose(0, 2, 1))
-    return Cn * (mass32.astype(np.float64) / dt)[:, None, None]
-
 
 def level_ties(case):
-    off, ids = ties.levels(case.mesh.coords, tc.group(case, "SIDE"), 2)
+    off, ids = ties.levels(case.mesh.coords, group(case, "SIDE"), 2)
     return off, ids, ties.groups_of(off, ids)
 
 
@@ -83,94 +49,39 @@ def assert_groups_move_together(st, groups, u_equal, what):
 
 def check_scheme(case, kind, variant, tie_set, dash_ids, checkpoints, what, sources=False):
     """ExplicitStepper with random dashpots on dash_ids and the tie set against the restatement, u and v bitwise."""
-    Vt = VARIANTS[variant]
-    curve = Vt.get("curve", False)
-    P = case.packing
-    D = P.dof_count
-    fixed = ac.constrained(P)
-    mass = np.repeat(P.lumped_mass, 3)
-    rng = np.random.Generator(np.random.PCG64(11))
-    bcv = P.bc_value.copy()
-    u0, v0 = np.zeros(D, np.float32), np.zeros(D, np.float32)
-    if curve:
-        bcv[fixed] = np.float32(1e-4)
-        u0 = (1e-6 * rng.standard_normal(D)).astype(np.float32)
-        v0 = (1e-3 * rng.standard_normal(D)).astype(np.float32)
-        u0[fixed] = bcv[fixed]
-        v0[fixed] = 0.0
     off, tids, groups = tie_set
-    sys_a = new_system(case, kind, case.scalars())
-    sys_b = new_system(case, kind, (1.0, 0.0))
-    st = ExplicitStepper(dataclasses.replace(P, bc_value=bcv) if curve else P, case.materials,
-                         RayleighCoefficients(Vt["alpha"], Vt["beta"]), system=sys_a)
-    try:
-        dt = st.telemetry().dt
+    with xc.SchemeRun(case, kind, variant, seed=11) as S:
+        P, st, rng, dt = case.packing, S.st, S.rng, S.dt
         dash = None
         tie_dash = None
         if len(dash_ids):
             ids = rng.permutation(np.asarray(dash_ids, np.int64))
             Cn = random_spd(rng, P.lumped_mass[ids], dt)
-            Pm, Qm = ac.update_matrices(Cn, P.lumped_mass[ids], Vt["alpha"], dt)
+            Pm, Qm = ac.update_matrices(Cn, P.lumped_mass[ids], S.alpha, dt)
             st.set_dashpots(ids, Cn)
             dash, tie_dash = (ids, Pm, Qm), (ids, Cn)
         st.set_ties(off, tids)
         info = st.tie_info()
         assert (info.group_count, info.member_count) == (len(groups), tids.size) and info.device_bytes > 0
-        MG, PG, QG = tc.group_records(groups, P.lumped_mass, Vt["alpha"], dt, tie_dash)
-        if curve:
-            base, pattern = case.load_pattern()
-            _, c = case.load_curve
-            st.set_load_pattern(base, pattern)
-            st.set_load_curve(c)
-            st.set_state(U, u0)
-            st.set_state(V, v0)
-            v0 = tc.project(v0, groups, P.lumped_mass, fixed)
-            assert_bitwise(st.get_state(V), v0, f"{what}: set_state projects v")
-
-            def force_at(n):
-                return pack._safe_f32(base + evaluate_curve(c, n * dt) * pattern)
+        tie = (groups,) + tc.group_records(groups, P.lumped_mass, S.alpha, dt, tie_dash)
+        S.load()
+        if S.curve:
+            S.v0 = tc.project(S.v0, groups, P.lumped_mass, S.fixed)
+            assert_bitwise(st.get_state(V), S.v0, f"{what}: set_state projects v")
         elif sources:
             f_ext = P.external_force.copy()
             nodes = np.concatenate([groups[0][:5], groups[-1][-3:], [int(np.setdiff1d(np.arange(P.node_count), tids)[0])]])
             pts = [(0.0, 0.0), (2.0 * dt, 1.0), (5.0 * dt, -0.5)]
             src = [LoadSource(pts, nodes, 50.0 * rng.standard_normal((nodes.size, 3)), dt * rng.uniform(0, 2, nodes.size))]
             st.set_sources(src)
-
-            def force_at(n):
-                return sc.source_force(f_ext, src, n, dt)
-        else:
-            f = P.external_force.copy()
-
-            def force_at(n):
-                return f
-
-        apply = applier(sys_b, D)
-        u, v, done = u0, v0, 0
-        for upto in checkpoints:
-            r = st.advance(upto - done)
-            assert r.has_value(), r.error()
-            assert r.value().steps == upto and r.value().finite
-            u, v = tc.host_scheme(apply, mass, fixed, bcv, force_at, Vt["alpha"], Vt["beta"], dt, u, v, done,
-                                  upto - done, dash, (groups, MG, PG, QG))
-            done = upto
-            assert_bitwise(st.get_state(U), u, f"{what} after {upto} steps: u")
-            assert_bitwise(st.get_state(V), v, f"{what} after {upto} steps: v")
-            assert_groups_move_together(st, groups, not curve, f"{what} after {upto} steps")
-        assert np.abs(u[~fixed]).max() > 0.0 and np.abs(v[~fixed]).max() > 0.0
+            S.force_at = lambda n: sc.source_force(f_ext, src, n, dt)
+        S.check(checkpoints, what, dash, tie, lambda at: assert_groups_move_together(st, groups, not S.curve, at))
         # the ties did something: the same scheme without them gives other bits at the tied nodes
-        _, v_plain = tc.host_scheme(apply, mass, fixed, bcv, force_at, Vt["alpha"], Vt["beta"], dt, u0, v0, 0, 1, dash)
-        _, v_tied = tc.host_scheme(apply, mass, fixed, bcv, force_at, Vt["alpha"], Vt["beta"], dt, u0, v0, 0, 1, dash,
-                                   (groups, MG, PG, QG))
+        _, v_plain = S.host(S.u0, S.v0, 0, 1, dash)
+        _, v_tied = S.host(S.u0, S.v0, 0, 1, dash, tie)
         assert not np.array_equal(v_plain.reshape(-1, 3)[tids], v_tied.reshape(-1, 3)[tids])
-        # a constrained component of a tied node: the mask wins
-        held = fixed.reshape(-1, 3)[tids]
-        assert np.array_equal(st.get_state(U).reshape(-1, 3)[tids][held], bcv.reshape(-1, 3)[tids][held])
-        assert np.all(st.get_state(V).reshape(-1, 3)[tids][held] == 0.0)
+        S.check_mask_wins(tids)  # a constrained component of a tied node
         return st.get_state(U), st.get_state(V)
-    finally:
-        st.close()
-        sys_a.close()
-        sys_b.close()
 
 
 # ---- 1. the stepper is the scheme -----------------------------------------------------------------------------------
@@ -182,7 +93,7 @@ def test_stepper_with_ties_is_the_scheme_bit_for_bit(kind, variant):
                        harmonic=5.0 if VARIANTS[variant].get("curve") else None)
     tie_set = level_ties(case)
     assert [len(g) for g in tie_set[2]] == [14, 14, 14, 14]
-    base = tc.group(case, "BASE")
+    base = group(case, "BASE")
     assert np.intersect1d(base, tie_set[2][0]).size == 14 and np.setdiff1d(base, tie_set[1]).size == 6
     check_scheme(case, kind, variant, tie_set, base, CHECKPOINTS, f"{kind}/{variant}")
 
@@ -200,8 +111,8 @@ def test_group_sizes_on_both_sides_of_the_summation_orders(kind):
     case = tc.tie_case(7, 6, 6, 0.1, hold_side=False)
     assert case.packing.node_count == 392
     tie_set = sized_ties(392, [2, 3, 8, 9, 63, 64, 65, 130], 5)
-    first = check_scheme(case, kind, "undamped", tie_set, tc.group(case, "BASE"), (3,), f"{kind}/sizes")
-    again = check_scheme(case, kind, "undamped", tie_set, tc.group(case, "BASE"), (3,), f"{kind}/sizes again")
+    first = check_scheme(case, kind, "undamped", tie_set, group(case, "BASE"), (3,), f"{kind}/sizes")
+    again = check_scheme(case, kind, "undamped", tie_set, group(case, "BASE"), (3,), f"{kind}/sizes again")
     assert_bitwise(first[0], again[0], "two runs: u")
     assert_bitwise(first[1], again[1], "two runs: v")
 
@@ -220,7 +131,7 @@ def test_order_replace_clear_and_refusals(kind):
     case = tc.tie_case()
     P = case.packing
     D, N = P.dof_count, P.node_count
-    fixed = ac.constrained(P)
+    fixed = xc.constrained(P)
     mass = np.repeat(P.lumped_mass, 3)
     bcv, f = P.bc_value, P.external_force.copy()
     rng = np.random.Generator(np.random.PCG64(23))
@@ -231,11 +142,11 @@ def test_order_replace_clear_and_refusals(kind):
         dt = st.telemetry().dt
         apply = applier(sys_b, D)
         off_a, ids_a, groups_a = level_ties(case)
-        side = tc.group(case, "SIDE")
+        side = group(case, "SIDE")
         off_b, ids_b, groups_b = sized_ties(side.size, [3, 5, 9], 3)
         ids_b = side[ids_b].astype(np.uint32)  # perimeter nodes only: one mask
         groups_b = ties.groups_of(off_b, ids_b)
-        base = rng.permutation(tc.group(case, "BASE"))
+        base = rng.permutation(group(case, "BASE"))
         Cn = random_spd(rng, P.lumped_mass[base], dt)
         # No coupling between y, which the base's perimeter nodes hold, and x or z: while such a node is an untied
         # dashpot node (under B, and after the clear) its rows would otherwise read the operator's constrained row,
@@ -247,7 +158,7 @@ def test_order_replace_clear_and_refusals(kind):
             tie = None
             if groups is not None:
                 tie = (groups,) + tc.group_records(groups, P.lumped_mass, 5.0, dt, (base, Cn) if with_dash else None)
-            return tc.host_scheme(apply, mass, fixed, bcv, lambda n: f, 5.0, 0.0, dt, u, v, first, steps,
+            return xc.host_scheme(apply, mass, fixed, bcv, lambda n: f, 5.0, 0.0, dt, u, v, first, steps,
                                   dash if with_dash else None, tie)
 
         # either order of the two sets: the same bits
@@ -335,7 +246,7 @@ def test_ties_with_yielding_plasticity_take_the_correction_force():
     case = tc.tie_case()
     P = case.packing
     D = P.dof_count
-    fixed = ac.constrained(P)
+    fixed = xc.constrained(P)
     mass = np.repeat(P.lumped_mass, 3)
     sy = 40.0e6
     mu = float(np.asarray(case.materials[0].stiffness).reshape(6, 6)[3, 3])
@@ -359,8 +270,8 @@ def test_ties_with_yielding_plasticity_take_the_correction_force():
             assert st.advance(1).has_value()
             p = st.get_state(PF)
             assert np.abs(p.reshape(-1, 3)[tids]).max() > 0.0
-            u, v = tc.host_scheme(apply, mass, fixed, P.bc_value, lambda k: f, 0.0, 0.0, dt, u, v, n, 1, None, tie,
-                                  lambda k: p)
+            u, v = xc.host_scheme(apply, mass, fixed, P.bc_value, lambda k: f, 0.0, 0.0, dt, u, v, n, 1, None, tie,
+                                  lambda k, u_k: p)
             assert_bitwise(st.get_state(U), u, f"plastic step {n}: u")
             assert_bitwise(st.get_state(V), v, f"plastic step {n}: v")
         assert st.plasticity_info().yielded_elements > 0
@@ -374,13 +285,13 @@ def test_ties_with_yielding_plasticity_take_the_correction_force():
 @pytest.mark.parametrize("kind", ["parity", "lattice"])
 def test_ties_see_the_load_sources_force(kind):
     case = tc.tie_case()
-    check_scheme(case, kind, "undamped", level_ties(case), tc.group(case, "BASE"), (3,), f"{kind}/sources", sources=True)
+    check_scheme(case, kind, "undamped", level_ties(case), group(case, "BASE"), (3,), f"{kind}/sources", sources=True)
 
 
 # ---- 6. the tied 3-D column -----------------------------------------------------------------------------------------
 def test_tied_column_doubles_at_the_surface_and_absorbs():
     """The figures are in DESIGN section 3, "Tied boundaries"."""
-    R = column_reference()
+    R = tc.column_reference()
     case = tc.column3d_case()
     P = case.packing
     D = P.dof_count
@@ -388,7 +299,7 @@ def test_tied_column_doubles_at_the_surface_and_absorbs():
     print(f"fp64 reduced run ({steps} steps, dt {dt:.4e}): {R['conditions']}; untied control spread / peak "
           f"{R['control_spread']:.3e}; restatement floors u {R['floor_u']:.2e} v {R['floor_v']:.2e}")
     R["assert_conditions"]()
-    top = 3 * tc.group(case, "TOP")
+    top = 3 * group(case, "TOP")
     sys_p = pcg.MatrixFreeSystem.from_packing(P, case.materials, 1.0, 0.0, mode=_lib.MODE_PARITY)
     sys_b = pcg.MatrixFreeSystem.from_packing(P, case.materials, 1.0, 0.0, mode=_lib.MODE_PARITY)
     apply = applier(sys_b, D)
@@ -435,14 +346,6 @@ def test_tied_column_doubles_at_the_surface_and_absorbs():
     finally:
         sys_p.close()
         sys_b.close()
-
-
-def deviation(a, ref):
-    return float(np.abs(np.asarray(a, np.float64) - ref).max() / np.abs(ref).max())
-
-
-def column_reference():
-    return tc.column_reference()
 
 
 # ---- 8. the step limit ----------------------------------------------------------------------------------------------
@@ -493,30 +396,23 @@ def test_tied_column_ledger(name, mode):
     """The construction and the bound of tests/test_gpu_monitors.py's column ledger test: the device's balance drift
     against the float32 restatement's ledger, whose dissipation uses each base node's own C_i (a copy of C_G per member
     would count the base's dissipation nine times). Peaks of tied members are equal."""
-    import monitors_common as mc
-
     R = tc.column_reference()
     case = tc.column3d_case()
     P = case.packing
     D = P.dof_count
     mass32 = np.repeat(P.lumped_mass, 3)
-    fixed = ac.constrained(P)
+    fixed = xc.constrained(P)
     dt, steps, groups = R["dt"], R["steps"] + 1, R["groups"]
     sysm = pcg.MatrixFreeSystem.from_packing(P, case.materials, 1.0, 0.0, mode=mode)
     sys_r = pcg.MatrixFreeSystem.from_packing(P, case.materials, 1.0, 0.0, mode=mode)
     st = ExplicitStepper(P, case.materials, RayleighCoefficients(0.0, 0.0), system=sysm, dt=dt)
     try:
-        from cwf import explicit
-
-        def force_at(n):
-            return pack._safe_f32(np.zeros(D) + explicit.curve_value(R["pts"], n * dt) * R["pattern"])
-
+        force_at = xc.curve_force(np.zeros(D), R["pattern"], R["pts"], dt, explicit.curve_value)
         tie = (groups,) + tc.group_records(groups, P.lumped_mass, 0.0, dt, (R["ids"], R["Cn"]))
         led = mc.LedgerReference()
-        for n, u, v, y, f_n, un, vn in tc.scheme_steps(applier(sys_r, D), mass32, fixed, P.bc_value, force_at, 0.0, 0.0,
-                                                       dt, np.zeros(D, np.float32), np.zeros(D, np.float32), 0, steps,
-                                                       None, tie):
-            led.add(n + 1, mc.energy_terms(mass32, fixed, 0.0, dt, v, y, f_n, un, vn, (R["ids"], R["Cn"])))
+        for s in xc.scheme_steps(applier(sys_r, D), mass32, fixed, P.bc_value, force_at, 0.0, 0.0, dt,
+                                 np.zeros(D, np.float32), np.zeros(D, np.float32), 0, steps, None, tie):
+            led.add(s.n + 1, mc.energy_terms(mass32, fixed, 0.0, dt, s.v, s.y, s.f, s.un, s.vn, (R["ids"], R["Cn"])))
         ref_steps, ref_rows, ref_bounds = led.arrays()
         drift_f32 = mc.balance_drift(ref_rows)
         slack = 2.0 * float(ref_bounds.sum(1).max()) / float((ref_rows[:, 0] + ref_rows[:, 1]).max())
@@ -538,7 +434,7 @@ def test_tied_column_ledger(name, mode):
               f"restatement's, largest difference / largest entry {worst:.2e}")
         assert drift <= drift_f32 + slack, (drift, drift_f32, slack)
         assert abs(1.0 - ratio) <= R["left"], (ratio, R["left"])  # the work that went in left through the base, once
-        assert_bitwise(st.get_state(U), un, f"{name}: u at the end")
+        assert_bitwise(st.get_state(U), s.un, f"{name}: u at the end")
         for pk in st.peaks():
             for members in groups:
                 assert np.all(pk[members].view(np.uint32) == pk[members[0]].view(np.uint32))

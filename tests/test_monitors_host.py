@@ -7,7 +7,7 @@ import math
 import absorbing_common as ac
 import monitors_common as mc
 from cwf import _lib
-from test_explicit_host import _header_struct
+from explicit_common import header_struct_size
 
 SYMBOLS = {
     "cwf_hip_explicit_set_monitors", "cwf_hip_explicit_reset_monitors", "cwf_hip_explicit_monitor_info",
@@ -24,8 +24,8 @@ def test_library_declares_and_exports_the_monitor_entry_points():
 
 
 def test_monitor_struct_sizes_match_the_header():
-    assert C.sizeof(_lib.ExplicitMonitorDescC) == _header_struct("cwf_explicit_monitor_desc") == 6 * 8 + 2 * 4 == 56
-    assert C.sizeof(_lib.ExplicitMonitorInfoC) == _header_struct("cwf_explicit_monitor_info") == 9 * 8 + 2 * 4 == 80
+    assert C.sizeof(_lib.ExplicitMonitorDescC) == header_struct_size("cwf_explicit_monitor_desc") == 6 * 8 + 2 * 4 == 56
+    assert C.sizeof(_lib.ExplicitMonitorInfoC) == header_struct_size("cwf_explicit_monitor_info") == 9 * 8 + 2 * 4 == 80
     assert _lib.ExplicitMonitorDescC.receiver_nodes.offset == 8 and _lib.ExplicitMonitorDescC.peaks.offset == 48
     assert _lib.ExplicitMonitorInfoC.energy_every.offset == 40 and _lib.ExplicitMonitorInfoC.peaks.offset == 72
     # the structs this feature must not move

@@ -13,7 +13,7 @@ import pytest
 from cwf import _lib, absorbing, config, meshgen, pack, run, scenarios
 from cwf.explicit import LoadSource
 from cwf.physics import AbsorbingBoundary, IncidentWave, compute_lame
-from test_absorbing_host import ABSORBING, BASE_YAML, H, face_geometry, raw_json, speeds
+from explicit_common import ABSORBING, BASE_YAML, H, face_geometry, raw_json, speeds
 
 SYMBOLS = {"cwf_hip_explicit_set_sources", "cwf_hip_explicit_get_sources", "cwf_hip_explicit_source_info",
            "cwf_absorbing_incident_plane"}

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import absorbing_common as ac
+import explicit_common as xc
 import ties_common as tc
 from cwf import ties
 
@@ -152,7 +153,7 @@ def test_tables_program_against_the_library_and_numpy(tmp_path):
     rng = np.random.Generator(np.random.PCG64(4))
     off, ids = ties.levels(case.mesh.coords, tc.perimeter(case.mesh.coords), 2)
     ids = rng.permutation(ids[:14]).tolist() + ids[14:].tolist()
-    dash = rng.permutation(tc.group(case, "BASE")).tolist()
+    dash = rng.permutation(xc.group(case, "BASE")).tolist()
     perm = rng.permutation(N).tolist()
     path = tmp_path / "set.txt"
     path.write_text("\n".join([str(N)] + [" ".join(map(str, [len(v)] + list(v))) for v in (dash, off.tolist(), ids, perm)]))
@@ -181,13 +182,13 @@ def test_gather_sum_orders():
     back = 0.0
     for x in big[::-1]:
         back = back + float(x)
-    assert tc.gather_sum(t).tolist() == [5.0, back, 8.0] and back != 5.0  # ((1e16 + 1) - 1e16) + 5 ones in list order
+    assert xc.gather_sum(t).tolist() == [5.0, back, 8.0] and back != 5.0  # ((1e16 + 1) - 1e16) + 5 ones in list order
     # nine members: lane sums first (every member its own lane), then strides 32 .. 1: lanes 0 and 8 meet at stride 8,
     # ((t0 + t8) + t4) + (t2 + t6) meets ((t1 + t5) + (t3 + t7)) at stride 1
     t9 = np.array([1e16, 1.0, -1e16, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0])
     t = np.stack([t9, np.arange(9.0), np.ones(9)], 1)
     want = (((t9[0] + t9[8]) + t9[4]) + (t9[2] + t9[6])) + ((t9[1] + t9[5]) + (t9[3] + t9[7]))
-    assert tc.gather_sum(t).tolist() == [want, 36.0, 9.0] and want != 7.0
+    assert xc.gather_sum(t).tolist() == [want, 36.0, 9.0] and want != 7.0
     # 130 members: lane l holds t_l + t_(l + 64) (+ t_(l + 128) for l < 2)
     rng = np.random.Generator(np.random.PCG64(1))
     t = rng.standard_normal((130, 3)) * 10.0 ** rng.integers(-8, 8, (130, 1))
@@ -195,7 +196,7 @@ def test_gather_sum_orders():
     L[:2] = L[:2] + t[128:]
     for s in (32, 16, 8, 4, 2, 1):
         L = L[:s] + L[s:2 * s]
-    assert np.array_equal(tc.gather_sum(t), L[0])
+    assert np.array_equal(xc.gather_sum(t), L[0])
 
 
 def test_restatement_against_the_fp64_reduced_system():

@@ -1,16 +1,15 @@
 """Shared by the tied-boundary tests: blocks whose lateral perimeter can be tied (one constraint mask per group), the
-scheme of include/cwf_hip.h "Tied boundaries" in numpy (float32 state, float64 math, the header's summation order,
-P_G | Q_G by the library), the projection of v, and the reduced dense system (T^T K T, T^T M T) for all-fp64 runs."""
+group records P_G | Q_G by the library for explicit_common.scheme_steps (the scheme of include/cwf_hip.h "Tied
+boundaries" in numpy), the projection of v, and the reduced dense system (T^T K T, T^T M T) for all-fp64 runs."""
 import functools
 from dataclasses import replace
 
 import numpy as np
 
 import absorbing_common as ac
+import explicit_common as xc
 from cwf import _lib, meshgen, pack, scenarios, ties
 from cwf.physics import Assignment, DirichletFix
-
-DOF_BITS = ac.DOF_BITS
 
 
 # ---- meshes ---------------------------------------------------------------------------------------------------------
@@ -34,12 +33,8 @@ def tie_case(nx=4, ny=3, nz=3, h=0.25, jitter=False, element="tet4", harmonic=No
     fixes = [DirichletFix("SIDE", (False, True, False), (None, 0.0, None))] if hold_side else []
     cfg = scenarios.make_config(dirichlet=fixes, harmonic=harmonic)
     case = scenarios.Case(f"tie{nx}x{ny}x{nz}", mesh, cfg, pack.build_packed_buffers(mesh, cfg))
-    assert np.array_equal(np.sort(group(case, "SIDE")), perimeter(mesh.coords))
+    assert np.array_equal(np.sort(xc.group(case, "SIDE")), perimeter(mesh.coords))
     return case
-
-
-def group(case, name):
-    return case.mesh.node_groups[case.mesh.group_names[name]].astype(np.int64)
 
 
 @functools.lru_cache(maxsize=None)
@@ -61,27 +56,7 @@ def plane_ties(case):
     return ties.levels(case.mesh.coords, np.arange(case.packing.node_count), 2)
 
 
-# ---- the restatement ------------------------------------------------------------------------------------------------
-def gather_sum(terms):
-    """The header's sum of a group's terms [c, 3] float64, a function of c alone."""
-    terms = np.asarray(terms, np.float64)
-    c = terms.shape[0]
-    if c <= 8:
-        acc = np.zeros(3)
-        for j in range(c):
-            acc = acc + terms[j]
-        return acc
-    L = np.zeros((64, 3))
-    for b in range(0, c, 64):
-        chunk = terms[b:b + 64]
-        L[:chunk.shape[0]] = L[:chunk.shape[0]] + chunk
-    s = 32
-    while s >= 1:
-        L[:s] = L[:s] + L[s:2 * s]
-        s //= 2
-    return L[0].copy()
-
-
+# ---- the restatement's tie records ----------------------------------------------------------------------------------
 def group_records(groups, mass32, alpha, dt, dash=None):
     """M_G [G], P_G, Q_G [G,3,3] by cwf_explicit_dashpot_update(C_G, M_G): M_G and C_G summed in member order (C_G from
     the first member with a dashpot). dash: (ids, C [n,3,3]) or None."""
@@ -117,55 +92,6 @@ def project(v, groups, mass32, fixed):
         mean[fx[members[0]]] = 0.0
         out[members] = mean
     return out.reshape(-1)
-
-
-def scheme_steps(apply, mass, fixed, bcv, force_at, alpha, beta, dt, u0, v0, first_step, steps, dash=None, tie=None,
-                 p_at=None):
-    """absorbing_common.host_scheme with tie groups, one step at a time, as monitors_common.scheme_steps: yields
-    (n, u, v, y, f, un, vn), float32 each. tie = (groups [index arrays], M_G, P_G, Q_G) of group_records; dash: (ids, P,
-    Q) of the dashpot nodes (a tied one's rows are overwritten by its group's); p_at(n) -> plasticity's correction
-    force (float32) or None."""
-    u, v = u0.astype(np.float32), v0.astype(np.float32)
-    half = alpha * dt / 2.0
-    c1, c2 = (1.0 - half) / (1.0 + half), dt / (1.0 + half)
-    m = mass.astype(np.float64)
-    for n in range(first_step, first_step + steps):
-        w = (u.astype(np.float64) + beta * v.astype(np.float64)).astype(np.float32) if beta != 0.0 else u
-        y = apply(w)
-        f = force_at(n)
-        net = f.astype(np.float64) - y.astype(np.float64)
-        if p_at is not None:
-            net = net + p_at(n).astype(np.float64)
-        g = net / m
-        v64 = v.astype(np.float64).reshape(-1, 3)
-        vn = (c1 * v.astype(np.float64) + c2 * g).astype(np.float32)
-        if dash is not None and len(dash[0]):
-            ids, P, Q = dash
-            vn.reshape(-1, 3)[ids] = ac.dashpot_rows(P, Q, v64[ids], g.reshape(-1, 3)[ids]).astype(np.float32)
-        if tie is not None:
-            groups, MG, PG, QG = tie
-            terms = np.where(fixed, 0.0, net).reshape(-1, 3)  # a constrained component adds nothing
-            for k, members in enumerate(groups):
-                gG = gather_sum(terms[members]) / MG[k]
-                c = len(members)
-                rows = ac.dashpot_rows(np.broadcast_to(PG[k], (c, 3, 3)), np.broadcast_to(QG[k], (c, 3, 3)),
-                                       v64[members], np.broadcast_to(gG, (c, 3)))
-                vn.reshape(-1, 3)[members] = rows.astype(np.float32)
-        un = (u.astype(np.float64) + dt * vn.astype(np.float64)).astype(np.float32)
-        un[fixed] = bcv[fixed]
-        vn[fixed] = 0.0
-        yield n, u, v, y, f, un, vn
-        u, v = un, vn
-
-
-def host_scheme(apply, mass, fixed, bcv, force_at, alpha, beta, dt, u0, v0, first_step, steps, dash=None, tie=None,
-                p_at=None):
-    """scheme_steps run to its end -> (u, v) after `steps` steps."""
-    u, v = u0.astype(np.float32), v0.astype(np.float32)
-    for _, _, _, _, _, u, v in scheme_steps(apply, mass, fixed, bcv, force_at, alpha, beta, dt, u0, v0, first_step,
-                                            steps, dash, tie, p_at):
-        pass
-    return u, v
 
 
 # ---- the reduced dense system ---------------------------------------------------------------------------------------
@@ -236,7 +162,7 @@ def column_reference():
     run = list(ac.scheme_f64(red["K"], red["mass"], red["fixed"], dt, steps + 1, lambda n: T.T @ (vals[n] * pattern),
                              red["dash"]))
     E = ac.energies_f64(red["K"], red["mass"], run)
-    top = 3 * group(case, "TOP")
+    top = 3 * xc.group(case, "TOP")
     top_v = np.array([s[2][dof][top].mean() for s in run])
     npk = int(np.abs(top_v).argmax())
     doubling, left = float(np.abs(top_v).max()) / 1e-3, float(E[-1] / E.max())
@@ -247,9 +173,9 @@ def column_reference():
     # the float32 restatement with the dense operator
     mass32 = P.lumped_mass
     MG, PG, QG = group_records(groups, mass32, 0.0, dt, (ids, Cn))
-    u, v = host_scheme(lambda w: (K @ w.astype(np.float64)).astype(np.float32), np.repeat(mass32, 3), fixed,
-                       np.zeros(D, np.float32), lambda n: pack._safe_f32(vals[n] * pattern), 0.0, 0.0, dt,
-                       np.zeros(D, np.float32), np.zeros(D, np.float32), 0, steps, None, (groups, MG, PG, QG))
+    u, v = xc.host_scheme(lambda w: (K @ w.astype(np.float64)).astype(np.float32), np.repeat(mass32, 3), fixed,
+                          np.zeros(D, np.float32), lambda n: pack._safe_f32(vals[n] * pattern), 0.0, 0.0, dt,
+                          np.zeros(D, np.float32), np.zeros(D, np.float32), 0, steps, None, (groups, MG, PG, QG))
     u_end, v_end = run[steps][1][dof], run[steps][2][dof]
 
     def dev(a, b):
