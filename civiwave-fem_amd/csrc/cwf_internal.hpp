@@ -356,6 +356,7 @@ struct ResidentPlan
     unsigned G = 0, npt = 0, nph = 0;  // workgroups; own / halo entries per thread (the instantiation)
     unsigned own_stride = 0, halo_stride = 0, npub = 0;
     size_t lds = 0;                     // dynamic LDS: the largest box image
+    unsigned image[2] = {0, 0};         // box 0's image strides PX, PXY (resident_image.hpp; the trace header prints them)
     unsigned dims[3] = {0, 0, 0};       // boxes along x, y, z
     unsigned max_own = 0, max_halo = 0;
     uint64_t halo_total = 0;            // halo entries over every box (records read per phase)

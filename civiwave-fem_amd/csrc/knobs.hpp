@@ -47,6 +47,9 @@ inline constexpr Knob kKnobs[] = {
     {"CWF_RESIDENT_REDUCER", "0|1, read at every launch: the resident solve's share fold and decision by one extra workgroup on a "
                              "spare CU, never / wherever the plan is eligible (unsharded, >= 2 boxes, one more workgroup "
                              "co-resident); default: eligible and at least kResReducerMinBoxes boxes (resident.hip)"},
+    {"CWF_RESIDENT_IMAGE", "0, read when the resident plan is made: every box's LDS image keeps the dense strides "
+                           "(sx + 2, (sx + 2)(sy + 2)) instead of the ones padded against bank conflicts "
+                           "(resident_image.hpp; tests/test_gpu_resident_image.py: same bits)"},
     {"CWF_FUSED_TRACE_IT","n: the iteration whose launch CWF_FUSED_TRACE records (default 50)"},
     {"CWF_FUSED_MAXWG", "n: cap on the fused launch's grid (default 1024 workgroups; a grid below the work items walks them persistently)"},
     {"CWF_XLAG", "1..4: iterations per lazy x update (tests/test_gpu_parity.py compares 4 with 1)"},

@@ -9,11 +9,18 @@
 // term growing with the grid (2 per workgroup); the image (box + ring, float4)
 // must fit the LDS beside the static tables and the lists the kernel's 4 + 3 entries per thread. C2 (70^3 nodes): 5 x 7 x 7 boxes of
 // 14 x 10 x 10 nodes, 245 workgroups.
+//
+// Image strides: the lists are built on the dense image ((sx + 2) x (sy + 2) x (sz + 2) slots, what the box choice
+// counts), then every box's strides PX, PXY are padded where that takes LDS bank conflicts off its rows' loads and its
+// form's stores (resident_image.hpp: the model and the search; C2's x-face boxes 16 x 192 -> 29 x 354, the others
+// 30 x 364) and the lists' slots are rewritten. Only addresses move: the lists' order, hence every sum, is untouched.
+// CWF_RESIDENT_IMAGE=0 keeps the dense strides.
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
 
 #include "abi_internal.hpp"
+#include "resident_image.hpp"
 
 namespace cwf
 {
@@ -180,8 +187,7 @@ bool plan_resident(cwf_hip_system *h, bool shard)
     {
         const unsigned *q = &B[6 * (size_t)b];
         const unsigned PX = q[1] - q[0] + 2, PXY = PX * (q[3] - q[2] + 2), slots = PXY * (q[5] - q[4] + 2);
-        hdr[b] = uint4{slots, 0u, PX, PXY};
-        max_slots = std::max<size_t>(max_slots, slots);
+        hdr[b] = uint4{slots, 0u, PX, PXY};  // (the dense image: padded below, once the lists stand)
         for (int pass = 0; pass < 2; ++pass)
             for (unsigned k = q[4]; k < q[5]; ++k)
                 for (unsigned j = q[2]; j < q[3]; ++j)
@@ -234,6 +240,35 @@ bool plan_resident(cwf_hip_system *h, bool shard)
             return false;
         hdr[b].y = (uint32_t)(g0 - halol[b].begin());
         ghost_total += ng;
+    }
+    // the image strides of every box (resident_image.hpp), under the cap of the instantiation the plan will take; the
+    // lists' slots follow. A box nothing improves, or whose padded image would not fit, keeps the dense strides
+    {
+        const char *ik = knob("CWF_RESIDENT_IMAGE");
+        const bool pad = !(ik && ik[0] == '0');
+        const uint64_t cap = slot_cap(max_own, max_halo);
+        ImageChooser chooser;
+        std::vector<ImageNode> lo, lh;
+        for (unsigned b = 0; b < G; ++b)
+        {
+            const unsigned *q = &B[6 * (size_t)b];
+            const unsigned PX = hdr[b].z, PXY = hdr[b].w;
+            const auto at = [&](const uint4 &e) {
+                return ImageNode{(uint16_t)(e.y % PX), (uint16_t)(e.y % PXY / PX), (uint16_t)(e.y / PXY)};
+            };
+            lo.clear(), lh.clear();
+            for (const uint4 &e : ownl[b])
+                lo.push_back(at(e));
+            for (const uint4 &e : halol[b])
+                lh.push_back(at(e));
+            const ImageStrides c = chooser.choose(q[1] - q[0], q[3] - q[2], q[5] - q[4], lo, lh, noff, cap, pad);
+            for (size_t e = 0; e < lo.size(); ++e)
+                ownl[b][e].y = image_slot(lo[e], c.px, c.pxy);
+            for (size_t e = 0; e < lh.size(); ++e)
+                halol[b][e].y = image_slot(lh[e], c.px, c.pxy);
+            hdr[b].x = c.slots, hdr[b].z = c.px, hdr[b].w = c.pxy;
+            max_slots = std::max<size_t>(max_slots, c.slots);
+        }
     }
     // the 4-node instantiation (LDS state): each box's boundary types (its block-surface nodes'), in ascending
     // order; the own entry carries the node's index among them in y >> 24 (the kernel's stencil table holds only the
@@ -349,6 +384,7 @@ bool plan_resident(cwf_hip_system *h, bool shard)
     rp.halo_stride = halo_stride;
     rp.npub = std::max<uint32_t>(npub, 1u);
     rp.lds = lds;
+    rp.image[0] = hdr[0].z, rp.image[1] = hdr[0].w;
     std::memcpy(rp.dims, bg, sizeof bg);
     rp.max_own = max_own;
     rp.max_halo = max_halo;
@@ -369,8 +405,9 @@ bool plan_resident(cwf_hip_system *h, bool shard)
     const uint64_t dec = (32ull * rp.npub + 127u) / 128u * 128u;
     rp.dec_off = dec + 256u <= 96ull * rp.npub && dec + 256u < 0xFFFFFF00ull ? (uint32_t)dec : 0u;
     if (knob("CWF_VERBOSE"))
-        fprintf(stderr, "[cwf] resident plan: %u boxes (%u x %u x %u), max_own %u, max_halo %u, %u published nodes\n", G,
-                bg[0], bg[1], bg[2], max_own, max_halo, npub);
+        fprintf(stderr, "[cwf] resident plan: %u boxes (%u x %u x %u), max_own %u, max_halo %u, %u published nodes, "
+                        "image strides of box 0 %u, %u, %zu B of LDS\n", G,
+                bg[0], bg[1], bg[2], max_own, max_halo, npub, hdr[0].z, hdr[0].w, lds);
     return true;
 }
 

@@ -11,7 +11,11 @@
 //     whole solve;
 //   - per iteration (phase j) it forms r_j, z_j, p_j, x_j exactly as lattice_fused.hip's launch j does (fused_form),
 //     writes p_j into an LDS image of the box plus its one-node ring, applies the stencil rows (interior nodes: the
-//     brick rows' difference form; block-surface nodes: the shell's cell form), and leaves the five fp64 dots.
+//     brick rows' difference form; block-surface nodes: the shell's cell form), and leaves the five fp64 dots. The
+//     image's strides are the box's own (ResArgs::hdr), padded by the plan so that the rows' ds_read_b128 and the
+//     form's ds_write_b128 spread over the LDS banks: with dense strides 14 lanes in a line and the next line 16 slots
+//     on put two lanes of a read group on one bank quad, and a block x-face row (x fixed, lanes stepping y by 16
+//     slots) all sixteen (resident_image.hpp; CWF_RESIDENT_IMAGE=0 keeps the dense strides, same bits).
 // The hand-off between boxes is tagged 16-B granules, one synchronisation per iteration, no counter:
 //   - published: per box-surface node that another box reads, ONE granule {Ap_j.xyz, tag} per phase (pub, by phase
 //     parity), and per workgroup five share granules {dot lo, hi, tag, -} (sh). The tag is tag0 + j + 1: a granule of
@@ -86,7 +90,8 @@ struct ResArgs
     Ctl *ctl;
     double *hist;
     const uint4 *hdr;   // [G] {LDS slots, - (the plan's first ghost halo entry: unused here), PX, PXY}: the box's
-                        // (sx + 2)(sy + 2)(sz + 2) image and its strides
+                        // (sx + 2)(sy + 2)(sz + 2) image and its strides PX >= sx + 2, PXY >= PX (sy + 2), padded per
+                        // box against LDS bank conflicts (resident_image.hpp); slots = PXY (sz + 2)
     const uint4 *own;   // [G][own_stride] {node, image slot, publication index or kResNone, -}
     const uint4 *halo;  // [G][halo_stride] {node, slot, publication index of its owner's record, -}
     const float4 *tcoef;  // the stencil of each boundary type (the block-surface rows), padded blocks: [27][nOff][3]
@@ -880,8 +885,9 @@ void launch_pcg_resident(cwf_hip_system *h, uint32_t max_it, hipStream_t st, hip
             if (FILE *f = std::fopen(tp, "a"))
             {
                 // ("reducer 1": the last row is the reducer's five stamps, the boxes' stamps 1, 7, 2 "decision seen")
-                std::fprintf(f, "# resident phase %u grid %u reducer %u boxes %ux%ux%u\n", ra.trace_j, grid, ra.reducer,
-                             rp.dims[0], rp.dims[1], rp.dims[2]);
+                // (the box grid stays the line's last field: tools/resident_trace.py reads it there)
+                std::fprintf(f, "# resident phase %u grid %u reducer %u image %u,%u lds %zu boxes %ux%ux%u\n", ra.trace_j, grid,
+                             ra.reducer, rp.image[0], rp.image[1], rp.lds, rp.dims[0], rp.dims[1], rp.dims[2]);
                 for (unsigned b = 0; b < grid; ++b)
                 {
                     std::fprintf(f, "%u", b);
